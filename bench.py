@@ -22,6 +22,10 @@ child fails.
 512 x 512 @ 64 spp wavefront of round 1's line); ``--two-stage`` / ``--separate-tangent``
 time the reference-shaped pipelines.
 
+``--dump-outputs DIR``: after the timed steps, the parameter-gradient buffer of the last step (what a caller of the timed
+path receives) goes to DIR/<name>.npy, float32, at most 64 MB (a fixed, seeded sample of rows beyond that); the inputs
+depend only on the arguments, so two builds can be compared array for array.
+
 Prints ONE JSON line (rank 0).  ``value`` = paths/s over all ranks for the whole step;
 ``grad_image_ms`` = wall-clock of the step = one gradient image; ``roofline`` prices the
 dominant kernel (one slab's ``epsm_backward_cp_kernel`` launch) against the 8 TB/s HBM
@@ -116,7 +120,13 @@ def parse(argv=None):
                     help="with --gpus N: all N ranks on GPU 0 and the collectives by gloo through the host -- runs the "
                          "sharded path (launcher, slab s -> rank s mod N, scratch buffers, one all-reduce per step) on a "
                          "one-GPU box; the line it prints says so and is not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (the parameter-gradient buffer: "
+                         "pos, nrm, alpha, cam_origin, color) as DIR/<name>.npy, float32, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -432,6 +442,27 @@ def lookup_traffic(kernel, paths, K, variant, profile):
 _T0 = time.perf_counter()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(params, directory):
+    """The arrays a caller of the timed path receives -- the parameter-gradient buffer of the last step, already summed over
+    the ranks -- as float32 .npy files.  Over DUMP_MAX_BYTES in all, every array keeps the same fraction of its rows, a fixed,
+    seeded sample (sorted), so that two builds compare output for output."""
+    import numpy as np
+    arrays = {"pos": params.pos, "nrm": params.nrm, "alpha": params.alpha, "cam_origin": params.cam_origin, "color": params.color}
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items() if v.numel() > 0}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        frac = 0.99 * DUMP_MAX_BYTES / total
+        pick = lambda n: torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, int(n * frac))].sort().values
+        arrays = {k: v[pick(v.shape[0])] for k, v in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, f"{k}.npy"), v.numpy())
+    return sorted(arrays)
+
+
 def _phase(name):
     """Where the wall-clock of a run goes (stderr; the JSON line stays alone on stdout)."""
     print(f"bench.py [{time.perf_counter() - _T0:7.1f} s] {name}", file=sys.stderr, flush=True)
@@ -614,6 +645,7 @@ def main():
         assert rccl_ranks == dist.get_world_size() == world
     # what the last step left in the parameter-gradient buffer (already summed over the ranks): the same image whatever N
     grad_abs_sum = float(params.flat.double().abs().sum())
+    dumped = dump_outputs(params, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     ms_per_step = elapsed / args.steps * 1e3
     value = N_image * args.steps / elapsed
 
@@ -705,6 +737,8 @@ def main():
                          "valu_floor_ms": (valu / 1024 * 4 / 2.4e9 * 1e3) if valu else None,
                          "kernel_source_hash": kernel_source_hash()},
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not distinct:
             result["config"]["note"] = (f"only {len(slabs)} of this rank's {n_my} slabs fit into HBM next to each other; "
                                         f"they are processed round-robin to make up the {n_my} launches of a step")

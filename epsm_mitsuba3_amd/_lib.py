@@ -31,9 +31,25 @@ class build_lock:
     def __init__(self, directory: str):
         self.path = os.path.join(directory, ".build.lock")
 
+    @staticmethod
+    def _open(path: str):
+        try:
+            return os.open(path, os.O_RDWR | os.O_CREAT, 0o666)
+        except OSError:
+            return os.open(path, os.O_RDONLY)          # another user's lock file: flock needs no write access
+
     def __enter__(self):
         import fcntl
-        self.f = open(self.path, "w")
+        try:
+            fd = self._open(self.path)
+        except OSError:
+            # a built checkout the running user may read but not write: make finds nothing stale and writes nothing,
+            # the lock goes to the temporary directory, keyed by the source directory
+            import hashlib
+            import tempfile
+            tag = hashlib.sha256(os.path.dirname(os.path.abspath(self.path)).encode()).hexdigest()[:16]
+            fd = self._open(os.path.join(tempfile.gettempdir(), f"epsm_build_{tag}.lock"))
+        self.f = os.fdopen(fd, "rb")
         fcntl.flock(self.f, fcntl.LOCK_EX)
         return self
 
