@@ -7,9 +7,9 @@
 //           paths of ONE m, each path on max(m,1) adjacent lanes (lane = first lane of the path + k - 1);
 //   rounds  dealt round-robin to the waves, no barrier between them.  A lane loads vertex k and the geometry of its two
 //           neighbours, evaluates its constraint(s) once (unit-seed Jacobians stay in registers), the block recursions
-//           run across the path's lanes with shuffles, and every lane then emits the rows of ITS vertex: wave-level
-//           merge of equal targets (DPP), append to the wave's LDS queue, LDS accumulator table, float atomics on
-//           flush -- the scatter back end of epsm_grad_scatter.hip (epsm_wave_scatter.h), unchanged.
+//           run across the path's lanes with shuffles, and every lane then emits the rows of ITS vertex: append to
+//           the wave's LDS queue, LDS accumulator table, float atomics on flush -- the scatter back end of
+//           epsm_grad_scatter.hip (epsm_wave_scatter.h), unchanged.
 // Against the one-lane-per-path kernel: no per-vertex state (256 -> ~half the VGPRs), every constraint evaluated once
 // instead of twice and its frame once instead of three times, all lanes busy whatever the chain length, vertex loops are
 // run-time loops (one instantiation per variant instead of one per K, a fraction of the code).
@@ -17,18 +17,13 @@
 #include <string.h>
 
 #define EPSM_FAST_RCP64                 // epsm_path_core.h: 1 / x in float64 by v_rcp_f64 + two Newton steps
-// Round 5: ONE trip to memory per record (EPSM_CP_STASH, below) is the product build -- headline slab 1.97 -> 1.90 ms, config 2
-// 2.30 -> 2.25, config 5 0.097 -> 0.092, pool slab 2.61 -> 2.62 (profiles/r05_e_whole_line_ab.txt); -DEPSM_CP_NO_STASH: round 4's
-// second trip after the recursions.  EPSM_CP_DMA / EPSM_CP_DMA_ALIAS / EPSM_CP_COOP: the whole-line request forms, measured slower.
-#if !defined(EPSM_CP_NO_STASH) && !defined(EPSM_CP_STASH)
-#define EPSM_CP_STASH
-#endif
-// ... and the lane's own record of the wave's NEXT round is requested before this round's emission (EPSM_CP_PREFETCH = 1, below):
-// headline slab 1.89 -> 1.81 ms, config 2 2.23 -> 2.19, pool slab 2.61 -> 2.59; = 2 (+ the rays) and = 3 (+ the end-point record)
-// spill 13-16 more registers and are slower (1.89 / 2.09 ms).  -DEPSM_CP_NO_PREFETCH: loads at the start of the round.
-#if defined(EPSM_CP_STASH) && !defined(EPSM_CP_NO_PREFETCH) && !defined(EPSM_CP_PREFETCH)
-#define EPSM_CP_PREFETCH 1
-#endif
+// Round 5: ONE trip to memory per record -- the words only the emission needs travel with the geometry and wait in LDS (the
+// stash, in the round loop) -- headline slab 1.97 -> 1.90 ms, config 2 2.30 -> 2.25, config 5 0.097 -> 0.092, pool slab 2.61 ->
+// 2.62 against round 4's second trip after the recursions (profiles/r05_e_whole_line_ab.txt).  The whole-line request forms
+// (records staged through LDS by LDS-DMA or by cooperative loads) measured slower and were removed: MEASUREMENTS.md 10.3.
+// ... and the lane's own record of the wave's NEXT round is requested before this round's emission (own_issue, below):
+// headline slab 1.89 -> 1.81 ms, config 2 2.23 -> 2.19, pool slab 2.61 -> 2.59; prefetching the rays too, or the rays and the
+// end-point record, spilled 13-16 more registers and was slower (1.89 / 2.09 ms; MEASUREMENTS.md 10.9).
 #include "epsm_fused.h"
 #include "epsm_cp_core.h"
 #include "epsm_wave_scatter.h"
@@ -67,7 +62,7 @@ namespace {
 #endif
 constexpr int kThreads = EPSM_CP_THREADS, kWaves = kThreads / 64, kQueueCap = EPSM_CP_QUEUE;
 constexpr int kKeys = 6;                // m = 0..5
-constexpr int kStashFirstItem = 64;     // EPSM_CP_STASH: queue items [64, 192) = 2 048 bytes hold 32 bytes per lane between a round's loads and its emission
+constexpr int kStashFirstItem = 64;     // the stash: queue items [64, 192) = 2 048 bytes hold 32 bytes per lane between a round's loads and its emission
 static_assert(kQueueCap - kStashFirstItem >= 128, "the stash needs 128 queue items");
 
 // lane -> (path slot j, vertex k) inside a round of c lanes per path: j = lane / c without a division
@@ -80,8 +75,7 @@ __device__ __forceinline__ int div_small(int lane, int c) {
 // them per round with a constraint chain, each waited for inside the recursions' dependency chains, on the same LDS pipe as the other
 // waves' table atomics; the whole-wave shifts of the data-parallel primitives (DPP wave_shr:1 / wave_shl:1, gfx9 only) do the same in
 // ONE vector instruction without leaving the SIMD.  With `old` = the lane's own value and bound_ctrl off, lane 0 / lane 63 keep
-// theirs, as __shfl_up / __shfl_down leave them.  (-DEPSM_CP_NO_DPP_SHIFT: the shuffles.)
-#ifndef EPSM_CP_NO_DPP_SHIFT
+// theirs, as __shfl_up / __shfl_down leave them.  (The shuffles: MEASUREMENTS.md 10.15, profiles/r05_s2_dpp_shift_ab.txt.)
 __device__ __forceinline__ int up1_bits(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }      // wave_shr:1
 __device__ __forceinline__ int down1_bits(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }    // wave_shl:1
 __device__ __forceinline__ float up1(float v) { return __int_as_float(up1_bits(__float_as_int(v))); }
@@ -90,16 +84,12 @@ __device__ __forceinline__ int up1(int v) { return up1_bits(v); }
 __device__ __forceinline__ int down1(int v) { return down1_bits(v); }
 __device__ __forceinline__ uint32_t up1(uint32_t v) { return (uint32_t) up1_bits((int) v); }
 __device__ __forceinline__ uint32_t down1(uint32_t v) { return (uint32_t) down1_bits((int) v); }
-#else
-template <typename T> __device__ __forceinline__ T up1(T v) { return __shfl_up(v, 1); }
-template <typename T> __device__ __forceinline__ T down1(T v) { return __shfl_down(v, 1); }
-#endif
 __device__ __forceinline__ V2<float> up1(V2<float> v) { return mk2<float>(up1(v.x), up1(v.y)); }
 __device__ __forceinline__ M2<float> up1(M2<float> m) { M2<float> o; o.a = up1(m.a); o.b = up1(m.b); o.c = up1(m.c); o.d = up1(m.d); return o; }
 __device__ __forceinline__ V3<float> down1(V3<float> v) { return mk3<float>(down1(v.x), down1(v.y), down1(v.z)); }
 __device__ __forceinline__ V3<float> up1(V3<float> v) { return mk3<float>(up1(v.x), up1(v.y), up1(v.z)); }
 
-// ---- record access on the reference's per-field arrays (the native log is read by geo_issue / addr_issue below); the flag
+// ---- record access on the reference's per-field arrays (the native log is read by own_issue / geo_issue_rest below); the flag
 // word of a path from either
 template <bool PACKED> struct Records {
     const FusedArgs &F;
@@ -148,7 +138,7 @@ template <bool PACKED> struct Records {
 
 // ---- emission: the rows of one vertex into the wave queue (clamp / NaN rule of calc_grad per (N,3) component first,
 // then the linear map of epsm_scatter_core.h: epsm.py:559-562, 622-627, 644-645).  One GROUP of three rows after the other
-// is formed in one reused V3 vals[3], merged over the wave (DPP) and pushed -- positions (with the flat-normal part and
+// is formed in one reused V3 vals[3] and pushed -- positions (with the flat-normal part and
 // diffuse_grad[0] folded in), normals, emitter, alpha, end point, occluder -- so that what a group needed is dead before
 // the next one starts (round 3 held pos[3], nrm[3], vals[6] and the emitter / alpha rows together: part of what pinned the
 // kernel at 256 registers).  All 64 lanes call it.
@@ -167,10 +157,9 @@ template <typename Table> struct Emitter {
     __device__ __forceinline__ static bool tri_ok(const U4 &t, int64_t V) {
         return t.x < (uint64_t) V && t.y < (uint64_t) V && t.z < (uint64_t) V;
     }
-    // three rows on keys (a, b, c), merged over the wave and queued
+    // three rows on keys (a, b, c), queued
     __device__ __forceinline__ void rows3(bool v, V3<float> vals[3], uint32_t a, uint32_t b, uint32_t c) const {
         const uint32_t keys[3] = {a, b, c};
-        merge_equal<3, 2>(v, keys, vals);
         push<3>(v, keys, vals);
     }
     // three rows g w_j
@@ -231,7 +220,6 @@ template <typename Table> struct Emitter {
             if (__ballot(v) != 0ull) {
                 V3<float> val[1] = {mk3<float>(v ? dot(gm, dhf) : 0.f, 0.f, 0.f)};
                 const uint32_t aid[3] = {2u * (uint32_t) F.V + bid, 0u, 0u};
-                merge_equal<1, 4>(v, aid, val);
                 push<1>(v, aid, val);
             }
         }
@@ -383,120 +371,11 @@ __device__ __forceinline__ const float *pixel_grad(const TangentIn &A, const Win
     }
     return A.grad_img + (y * A.img_width + x) * A.img_channels + 3;
 }
-template <int VARIANT, bool LIST>
-__device__ __forceinline__ void geo_issue(GeoFetch &X, const FusedArgs &F, const LaneId &L, const WinBase &B) {
-    const LaneRole R = role_of<LIST>(F, L, B);
-    // (a path WITHOUT a constraint reads its first record only when its first hit is diffuse: diffuse_grad[0] = dldp needs the
-    // triangle; otherwise all it gives is its share of d/d ray.o, which needs the rays alone -- 27 % of the bathroom paths)
-    if (R.live || R.d1) { X.o0 = ldq(R.rec, 0); X.o1 = ldq(R.rec, 1); X.o2 = ldq(R.rec, 2); }
-    if (R.live) {
-        X.o3 = ldq(R.rec, 3); X.o4 = ldq(R.rec, 4); X.o5 = ldq(R.rec, 5);
-#ifndef EPSM_CP_STASH                   // (stash build: light.z arrives with quad 7)
-        if (VARIANT == EPSM_VARIANT_MANIFOLD && cp::plan_a(L.plan, L.k)) X.o_lz = lds_(R.rec, 28);
-#endif
-    }
-    if (R.ok && R.first) {
-        const float *rays = R.rays;
-#ifdef EPSM_CPKO_NORAYS                 // (knock-out build: what reading the rays costs; results are wrong)
-        { const float v = (float) R.loc * 1e-3f; const F4v f4 = {v, 0.5f, -0.25f, 1.f}; X.p0 = f4; X.p1 = f4 * 0.5f; X.p2 = f4 * 0.25f; }
-#elif defined(EPSM_CPKO_RAYS0)          // (knock-out build: every path takes the rays of its window's first path -- realistic values, no gather)
-        X.p0 = ldq(B.rays, 0); X.p1 = ldq(B.rays, 1); X.p2 = ldq(B.rays, 2); (void) rays;
-#else
-        X.p0 = ldq(rays, 0); X.p1 = ldq(rays, 1); X.p2 = ldq(rays, 2);
-#endif
-        const F2v g = ld2(pixel_grad(F.tin, B, R.loc, R.path));
-        X.gx = g.x; X.gy = g.y;
-    }
-    if (R.end_next) {
-        const float *nx = R.rec + kRecWords;
-        X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
-    }
-}
-// ---- EPSM_CP_DMA (round 5): the lane's OWN record through LDS, as whole 128-byte lines.
-// Per-lane loads ask the vector L1 for one 16-byte piece of 64 DIFFERENT lines per instruction -- six instructions per record,
-// plus two more after the recursions for the words the emission needs: the same gathers with this kernel's amount of work
-// beside them run at 3.6-3.9 TB/s (tools/micro/batch_gather.hip, profiles/r05_d_batch_gather.txt), which IS this kernel's
-// measured HBM rate.  Eight lanes x 16 bytes per record in ONE instruction (LDS-DMA, global_load_lds_dwordx4: no register
-// destination) make every request a whole line: 5.5-5.9 TB/s in the same micro-benchmark at the same three waves per SIMD,
-// in BATCHES of 16 records through 2 304 bytes of staging per wave -- two DMA instructions, wait, the 16 owning lanes read
-// their quads back, next batch.  Lane l of instruction j of batch b serves the record of lane `owner` = 16 b + 8 j + l / 8 and
-// fetches its quad (l % 8) ^ (owner % 8) -- the XOR on the SOURCE side, the LDS image being lane-linear -- so that the 16
-// owners' ds_read_b128 of one quad hit 16 different bank groups (slots 1 152 bytes apart: 1 024 + 128 of padding).
-constexpr int kDmaSlotWords = 288, kDmaBatch = 16;
-constexpr int kDmaStageWords = 2 * kDmaSlotWords;           // per wave
+// the stash's LDS accesses (round loop)
 typedef __attribute__((address_space(3))) const F4v LdsF4;
-__device__ __forceinline__ void dma16(const float *src, float *lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) src, (__attribute__((address_space(3))) void *) lds_dst, 16, 0, 0);
-}
-// want: 2 = the whole record (a constraint vertex), 1 = its first sector (a diffuse first hit without a constraint), 0 = nothing
-template <int VARIANT, bool LIST>
-__device__ __forceinline__ void geo_stage_dma(GeoFetch &X, const FusedArgs &F, const LaneId &L, const WinBase &B, float *stage, int lane) {
-    const LaneRole R = role_of<LIST>(F, L, B);
-    const uint32_t want = R.live ? 2u : R.d1 ? 1u : 0u;
-    const uint32_t roff = (uint32_t) (R.loc * (uint32_t) F.pk_path_stride + (uint32_t) (L.k - 1) * (uint32_t) kRecWords) | want;   // (a multiple of 32: the low bits are free)
-    const int s = lane & 7, grp = lane >> 3;
-    const int quad = s ^ (grp & 7);                          // owner % 8 == (l / 8) % 8 in every instruction
-    const bool want_lz = VARIANT == EPSM_VARIANT_MANIFOLD && R.live && cp::plan_a(L.plan, L.k);
-#pragma unroll 1
-    for (int b = 0; b < 64 / kDmaBatch; ++b) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t o = (uint32_t) __shfl((int) roff, kDmaBatch * b + 8 * j + grp);
-            const uint32_t w = o & 3u;
-            if (w == 2u || (w == 1u && quad < 4)) dma16(B.verts + (o & ~31u) + 4 * quad, stage + j * kDmaSlotWords);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int li = lane - kDmaBatch * b;
-        if (li >= 0 && li < kDmaBatch && want != 0u) {
-            const float *p = stage + (li >> 3) * kDmaSlotWords + s * kRecWords;
-            X.o0 = *(LdsF4 *) (p + 4 * (0 ^ s)); X.o1 = *(LdsF4 *) (p + 4 * (1 ^ s)); X.o2 = *(LdsF4 *) (p + 4 * (2 ^ s));
-            if (want == 2u) {
-                X.o3 = *(LdsF4 *) (p + 4 * (3 ^ s)); X.o4 = *(LdsF4 *) (p + 4 * (4 ^ s)); X.o5 = *(LdsF4 *) (p + 4 * (5 ^ s));
-                if (want_lz) X.o_lz = *(__attribute__((address_space(3))) const float *) (p + 4 * (7 ^ s));
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the next batch overwrites the slots
-    }
-}
-// ---- EPSM_CP_COOP: the same whole-line requests with REGISTER staging -- all eight cooperative loads of a round in flight at
-// once (32 registers that nothing else needs at the start of a round), ONE wait, then the transposition through the 2 304-byte
-// staging area in four batches of LDS round trips (~100 cycles each) instead of four trips to memory.
 typedef __attribute__((address_space(3))) F4v LdsF4w;
-template <int VARIANT, bool LIST>
-__device__ __forceinline__ void geo_stage_coop(GeoFetch &X, const FusedArgs &F, const LaneId &L, const WinBase &B, float *stage, int lane) {
-    const LaneRole R = role_of<LIST>(F, L, B);
-    const uint32_t want = R.live ? 2u : R.d1 ? 1u : 0u;
-    const uint32_t roff = (uint32_t) (R.loc * (uint32_t) F.pk_path_stride + (uint32_t) (L.k - 1) * (uint32_t) kRecWords) | want;
-    const int s = lane & 7, grp = lane >> 3;
-    const bool want_lz = VARIANT == EPSM_VARIANT_MANIFOLD && R.live && cp::plan_a(L.plan, L.k);
-    const F4v z4 = {0.f, 0.f, 0.f, 0.f};
-    F4v c0 = z4, c1 = z4, c2 = z4, c3 = z4, c4 = z4, c5 = z4, c6 = z4, c7 = z4;
-    // instruction j: lane l fetches quad l % 8 of the record of lane 8 j + l / 8 (quads 4..7 only of whole records)
-#define EPSM_COOP_LOAD(J, C) { const uint32_t o = (uint32_t) __shfl((int) roff, 8 * J + grp); const uint32_t w = o & 3u; \
-        if (w == 2u || (w == 1u && s < 4)) C = ldq(B.verts + (o & ~31u), s); }
-    EPSM_COOP_LOAD(0, c0) EPSM_COOP_LOAD(1, c1) EPSM_COOP_LOAD(2, c2) EPSM_COOP_LOAD(3, c3)
-    EPSM_COOP_LOAD(4, c4) EPSM_COOP_LOAD(5, c5) EPSM_COOP_LOAD(6, c6) EPSM_COOP_LOAD(7, c7)
-#undef EPSM_COOP_LOAD
-    // transposition: instruction j's lane l holds quad s of local record grp; it goes to slot (j & 1), record grp, position s ^ grp
-    float *const wr0 = stage + grp * kRecWords + 4 * (s ^ grp), *const wr1 = wr0 + kDmaSlotWords;
-#define EPSM_COOP_BATCH(BATCH, CA, CB) { \
-        *(LdsF4w *) wr0 = CA; *(LdsF4w *) wr1 = CB; \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        const int li = lane - kDmaBatch * BATCH; \
-        if (li >= 0 && li < kDmaBatch && want != 0u) { \
-            const float *p = stage + (li >> 3) * kDmaSlotWords + s * kRecWords; \
-            X.o0 = *(LdsF4 *) (p + 4 * (0 ^ s)); X.o1 = *(LdsF4 *) (p + 4 * (1 ^ s)); X.o2 = *(LdsF4 *) (p + 4 * (2 ^ s)); \
-            if (want == 2u) { \
-                X.o3 = *(LdsF4 *) (p + 4 * (3 ^ s)); X.o4 = *(LdsF4 *) (p + 4 * (4 ^ s)); X.o5 = *(LdsF4 *) (p + 4 * (5 ^ s)); \
-                if (want_lz) X.o_lz = *(__attribute__((address_space(3))) const float *) (p + 4 * (7 ^ s)); \
-            } \
-        } \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-    EPSM_COOP_BATCH(0, c0, c1) EPSM_COOP_BATCH(1, c2, c3) EPSM_COOP_BATCH(2, c4, c5) EPSM_COOP_BATCH(3, c6, c7)
-#undef EPSM_COOP_BATCH
-}
-// what stays a per-lane load beside the staged records: the rays + image gradient of a path's first lane, the first sector of
-// the end-point record of its last lane
+// what a round loads at its start (the lane's own record came with the round before it, own_issue): the rays + image gradient
+// of a path's first lane, the first sector of the end-point record of its last lane
 template <bool LIST>
 __device__ __forceinline__ void geo_issue_rest(GeoFetch &X, const FusedArgs &F, const LaneId &L, const WinBase &B) {
     const LaneRole R = role_of<LIST>(F, L, B);
@@ -508,11 +387,7 @@ __device__ __forceinline__ void geo_issue_rest(GeoFetch &X, const FusedArgs &F, 
     }
     if (R.end_next) {
         const float *nx = R.rec + kRecWords;
-#ifdef EPSM_CPKO_NOEND                  // (knock-out build: what reading the end-point records costs; results are wrong)
-        X.n0 = X.o0 * 1.5f; X.n1 = X.o1 * 1.5f; X.n2 = X.o2; (void) nx;
-#else
         X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
-#endif
     }
 }
 template <int VARIANT, bool LIST>
@@ -520,40 +395,24 @@ __device__ __forceinline__ void addr_issue(AddrFetch &A, const FusedArgs &F, con
     const LaneRole R = role_of<LIST>(F, L, B);
     if (R.live) {
         const bool wN = VARIANT == EPSM_VARIANT_MANIFOLD && cp::plan_a(L.plan, L.k);
-#ifdef EPSM_CP_STASH
         if (F.galpha || wN) A.q7 = ldq(R.rec, 7);                  // d hf / d alpha, and light.z of the emitter sample
-#else
-        if (F.galpha) A.q7 = ldq(R.rec, 7);
-#endif
         if (wN) A.q6 = ldq(R.rec, 6);
     }
     if (R.d1 && R.shadow) A.sh = load_u4(R.shadow, 0);
 }
 
-// ---- EPSM_CP_PREFETCH (round 5; the product build): the lane's OWN record of the wave's NEXT round -- quads 0..5 and the
+// ---- round 5: the lane's OWN record of the wave's NEXT round -- quads 0..5 and the
 // emission's words -- requested before this round's emission, into 36 registers that only the emission has to live with (its
 // pressure is ~80 registers below the recursions' peak: no additional spill), so that the trip to memory runs under the LDS work
 // of the emission.  (Round 3 prefetched everything a round reads into 62 registers and paid for it with the third wave per SIMD.)
 template <int VARIANT, bool LIST>
 __device__ __forceinline__ void own_issue(GeoFetch &X, AddrFetch &A, const FusedArgs &F, const LaneId &L, const WinBase &B) {
     const LaneRole R = role_of<LIST>(F, L, B);
+    // (a path WITHOUT a constraint reads its first record only when its first hit is diffuse: diffuse_grad[0] = dldp needs the
+    // triangle; otherwise all it gives is its share of d/d ray.o, which needs the rays alone -- 27 % of the bathroom paths)
     if (R.live || R.d1) { X.o0 = ldq(R.rec, 0); X.o1 = ldq(R.rec, 1); X.o2 = ldq(R.rec, 2); }
     if (R.live) { X.o3 = ldq(R.rec, 3); X.o4 = ldq(R.rec, 4); X.o5 = ldq(R.rec, 5); }
     addr_issue<VARIANT, LIST>(A, F, L, B);
-#if EPSM_CP_PREFETCH >= 2            // ... and the rays + image gradient of a path's first lane
-    if (R.ok && R.first) {
-        const float *rays = R.rays;
-        X.p0 = ldq(rays, 0); X.p1 = ldq(rays, 1); X.p2 = ldq(rays, 2);
-        const F2v g = ld2(pixel_grad(F.tin, B, R.loc, R.path));
-        X.gx = g.x; X.gy = g.y;
-    }
-#endif
-#if EPSM_CP_PREFETCH >= 3            // ... and the end-point record of its last lane
-    if (R.end_next) {
-        const float *nx = R.rec + kRecWords;
-        X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
-    }
-#endif
 }
 __device__ __forceinline__ void fetch_zero(GeoFetch &X, AddrFetch &A) {
     const F4v z4 = {0.f, 0.f, 0.f, 0.f};
@@ -591,9 +450,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
     __shared__ int s_used;
     __shared__ QItem s_queue[kWaves][kQueueCap];
     __shared__ PtrTable s_ptrs;
-#if defined(EPSM_CP_DMA) && !defined(EPSM_CP_DMA_ALIAS)
-    __shared__ __attribute__((aligned(16))) float s_stage[PACKED ? kWaves : 1][PACKED ? kDmaStageWords : 4];
-#endif
     float *const my_rep = F.rep ? F.rep + (blockIdx.x % (unsigned) F.replicas) * F.rep_stride : nullptr;
     const Table T{s_keys, s_vals, &s_used, my_rep ? my_rep : F.gpos, my_rep ? my_rep + 3 * F.V : F.gnrm,
                   my_rep ? my_rep + 6 * F.V : F.galpha, (uint32_t) F.V};
@@ -705,30 +561,20 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             const int c = q > 0 ? q : 1, ppr = 64 / c;
             RS.rb[q + 1] = RS.rb[q] + (RS.cls[q + 1] - RS.cls[q] + ppr - 1) / ppr;
         }
-#ifdef EPSM_CPKO_NOROUNDS                 // (knock-out builds, tools/build_cp_variant.sh: what a stage costs)
-        RS.rb[kKeys] = 0;
-#endif
         // Software pipeline: the records of the wave's NEXT round are requested before this round's rows go into the
         // queue / table, so the HBM round trip of one round runs under the LDS work of the other (measured apart they
         // were 1.6 ms and 1.5 ms per 2^24-path slab, and their sum when a wave did one after the other).
         // (Round r goes to wave r mod 4.  Handing the rounds out dynamically -- a wave takes the next one nobody has, one LDS
         // atomic per round -- measured 2.15 against 2.08 ms; the classes with the longest chains first, so that a window's tail
-        // is made of cheap rounds: 6.3 ms, three times slower -- 9.8 ms in round 5, -DEPSM_CP_REVERSE_ROUNDS.  The reason: the ORDER fills the table.  The light
+        // is made of cheap rounds: 6.3 ms, three times slower -- 9.8 ms in round 5, MEASUREMENTS.md 10.15.  The reason: the ORDER fills the table.  The light
         // rounds come first and bring the rows a window shares -- the first-hit triangles of its pixels -- into their home slots; the deep vertices' rows,
         // which nobody shares, come last and leave for the buffers directly when their neighbourhood is full.  Reversed, the unshared rows take the slots
         // and the SHARED ones overflow: thousands of float atomics on the same few addresses.)
         const int n_rounds = RS.rb[kKeys];
-#ifdef EPSM_CP_REVERSE_ROUNDS            // (A/B build: the rounds of the longest chains first, the window's tail made of light rounds)
-#define EPSM_RR(x) (n_rounds - 1 - (x))
-#else
-#define EPSM_RR(x) (x)
-#endif
-        LaneId L = RS.lane_of(EPSM_RR(wv), lane);
-#ifdef EPSM_CP_PREFETCH
+        LaneId L = RS.lane_of(wv, lane);
         GeoFetch Xp; AddrFetch Ap;
         fetch_zero(Xp, Ap);
         if (PACKED) own_issue<VARIANT, kList>(Xp, Ap, F, L, WB);           // the window's first round: nothing to hide it under
-#endif
 #pragma unroll 1
         for (int r = wv; r < n_rounds; r += kWaves) {
             const int q = L.q, c = L.c, k = L.k;
@@ -743,9 +589,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             const bool act1 = (plan & cp::kPlanActive1) != 0;
 
             asm volatile("; EPSM_MARK round_begin");
-#ifdef EPSM_CP_DRAIN_EACH_ROUND          // (A/B build: what it costs to start every round with an empty queue)
-            Q.drain(T);
-#endif
             // ---- geometry: own vertex; the two neighbours from the lanes that hold them (or from the words fetched for that)
             cp::Own<float> own;
             own.x = own.e1 = own.e2 = own.n = own.dn1 = own.dn2 = own.light = zero3<float>();
@@ -768,33 +611,8 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     X.o0 = X.o1 = X.o2 = X.o3 = X.o4 = X.o5 = X.p0 = X.p1 = X.p2 = X.n0 = X.n1 = X.n2 = z4;
                     X.o_lz = X.gx = X.gy = 0.f;
                 }
-#if defined(EPSM_CP_COOP)
-                geo_issue_rest<kList>(X, F, L, WB);
-                Q.drain(T);                                          // the staging area IS the wave's (now empty) row queue
-                geo_stage_coop<VARIANT, kList>(X, F, L, WB, (float *) s_queue[wv], lane);
-#elif defined(EPSM_CP_DMA)
-                geo_issue_rest<kList>(X, F, L, WB);
-#ifdef EPSM_CP_DMA_ALIAS
-                Q.drain(T);                                          // the staging area IS the wave's (now empty) row queue
-                geo_stage_dma<VARIANT, kList>(X, F, L, WB, (float *) s_queue[wv], lane);
-#else
-                geo_stage_dma<VARIANT, kList>(X, F, L, WB, s_stage[wv], lane);
-#endif
-#else
-#ifdef EPSM_CP_PREFETCH
-#if EPSM_CP_PREFETCH >= 3
-                X = Xp;
-#elif EPSM_CP_PREFETCH >= 2
-                X = Xp;
-                if (role_of<kList>(F, L, WB).end_next) { const float *nx = role_of<kList>(F, L, WB).rec + kRecWords; X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2); }
-#else
                 geo_issue_rest<kList>(X, F, L, WB);
                 X.o0 = Xp.o0; X.o1 = Xp.o1; X.o2 = Xp.o2; X.o3 = Xp.o3; X.o4 = Xp.o4; X.o5 = Xp.o5;
-#endif
-#else
-                geo_issue<VARIANT, kList>(X, F, L, WB);
-#endif
-#ifdef EPSM_CP_STASH
                 // ONE trip to memory per record: the words only the emission needs (quads 6 and 7: the same line as the geometry,
                 // second sector) are requested together with it and parked in LDS until the emission -- 32 bytes per lane in the
                 // TAIL of the wave's row queue (items 64..191), which holds fewer than 64 items at this point: the full groups of
@@ -805,19 +623,13 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     AddrFetch A0;
                     const F4v z4s = {0.f, 0.f, 0.f, 0.f};
                     A0.q6 = A0.q7 = z4s; A0.sh.x = kNoIndex; A0.sh.y = A0.sh.z = A0.sh.w = 0u;
-#ifdef EPSM_CP_PREFETCH
                     A0 = Ap;
-#else
-                    addr_issue<VARIANT, kList>(A0, F, L, WB);
-#endif
                     float *st = (float *) s_queue[wv] + 4 * kStashFirstItem + 8 * lane;
                     const bool has_sh = d1 && F.pk_shadow;
                     const F4v shv = {__uint_as_float(A0.sh.x), __uint_as_float(A0.sh.y), __uint_as_float(A0.sh.z), __uint_as_float(A0.sh.w)};
                     *(LdsF4w *) st = has_sh ? shv : A0.q6; *(LdsF4w *) (st + 4) = A0.q7;
                     X.o_lz = A0.q7.x;                                // light.z: word 28
                 }
-#endif
-#endif
                 if (live) {
                     const Geo<float> g = geo_from(X.o0, X.o1, X.o2);
                     const Nrm<float> nr = nrm_from(X.o3, X.o4, X.o5, g.b0, g.b1);
@@ -898,13 +710,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                 A.q6 = A.q7 = z4;
                 A.sh.x = kNoIndex; A.sh.y = A.sh.z = A.sh.w = 0u;
             }
-#ifdef EPSM_CPKO_NOSOLVE
-            gd_acc.x += own.x.x + own.n.y + own.light.z + own.eta + prev.x.x + prev.e1.y + next.x.z + next.e2.x + dk.x + dp.y;
-            if (PACKED) addr_issue<VARIANT, kList>(A, F, L, WB);
-            if (false) {
-#else
             if (VARIANT == EPSM_VARIANT_MANIFOLD) {
-#endif
                 cp::MSeeds<float> sd;
                 sd.sN = sd.sC = mk2<float>(0.f, 0.f); sd.useN = sd.useC = sd.fC = false;
                 if (q > 0) {
@@ -933,7 +739,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                 }
                 // the words only the emission needs, on their way (vector-cache hits) under the second sweep
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef EPSM_CP_STASH
                 if (PACKED) {
                     const float *st = (const float *) s_queue[wv] + 4 * kStashFirstItem + 8 * lane;
                     const F4v a = *(LdsF4 *) st;
@@ -942,9 +747,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     else A.q6 = a;
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the emission's pushes may overwrite the stash
                 }
-#else
-                if (PACKED) addr_issue<VARIANT, kList>(A, F, L, WB);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 if (q > 0) {
                     // pass 2: the constraint(s) swept once more with the final seeds
@@ -974,7 +776,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     poisoned = (bad & seg) != 0ull;
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef EPSM_CP_STASH
                 if (PACKED) {
                     const float *st = (const float *) s_queue[wv] + 4 * kStashFirstItem + 8 * lane;
                     const F4v a = *(LdsF4 *) st;
@@ -983,9 +784,6 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     else A.q6 = a;
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the emission's pushes may overwrite the stash
                 }
-#else
-                if (PACKED) addr_issue<VARIANT, kList>(A, F, L, WB);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 if (q > 0) {
                     const cp::COut<float> o = cp::caustic_finish(pts, f, first, live && k <= idstar, live && k == idstar, live && cp::plan_b(plan, k));
@@ -1019,21 +817,15 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             // flight, every 64 bytes a wave reads is one of them for as long as its latency, and a touched line is fetched TWICE
             // through that queue -- by the touch at HBM latency, again by the round that uses it at L2 latency, the L1 having lost
             // it in between.  TCP_PENDING_STALL_CYCLES: 65 % of the kernel; without the touch 2.046 -> 1.970 ms.)
-            const LaneId Ln = RS.lane_of(EPSM_RR(r + kWaves), lane);  // (past the last round: no lane has a path)
-#ifdef EPSM_CP_PREFETCH
+            const LaneId Ln = RS.lane_of(r + kWaves, lane);           // (past the last round: no lane has a path)
             // (issued here, behind the table rows' loads -- vmcnt counts in order: waiting for those does not wait for these -- and
             // not earlier: before the solve the same 36 registers spill 117)
             if (PACKED) { fetch_zero(Xp, Ap); own_issue<VARIANT, kList>(Xp, Ap, F, Ln, WB); }
-#endif
             // ---- emission
             asm volatile("; EPSM_MARK emit");
             if (PACKED) bid = (t_own.w >> 8) - 1u;                    // packed log: alpha slot + 1 in the table row
-#ifdef EPSM_CPKO_NOEMIT
-            gd_acc.x += Gx.x + gn.y + gm.x + glight.z + gdiff.x + dp.x + (float) (t_own.x + t_next.y + er.z + bid + t_sh.x) + dhf.x + eb0 + eb1 + ew + (emit_vertex ? 1.f : 0.f);
-#else
             E.vertex(emit_vertex && q > 0, live, d1, Gx, gn, gm, glight, gdiff, dp, pts.n, keep_e1, keep_e2, fb0, fb1,
                      nb0, nb1, bid, dhf, eb0, eb1, ew, t_own, t_next, er, sh, t_sh);
-#endif
             asm volatile("; EPSM_MARK round_end");
             L = Ln;
         }

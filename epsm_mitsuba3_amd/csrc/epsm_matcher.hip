@@ -83,15 +83,6 @@ __global__ __launch_bounds__(256) void softmin_partial_kernel(int64_t n, int64_t
 #pragma unroll
                 for (int k = 0; k < D; ++k) pk[k] = p[k];
                 const float ph = p[7];
-#ifdef EPSM_AB_MATCHER_SCALAR_FMA
-#pragma unroll
-                for (int r = 0; r < kRows; ++r) {
-                    float a = ph;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) a = fmaf(xs[r][k], pk[k], a);
-                    v[r][c] = a;
-                }
-#else
                 // two rows per v_pk_fma_f32 (the point's coordinate goes to both halves through op_sel)
 #pragma unroll
                 for (int r = 0; r < kRows; r += 2) {
@@ -100,7 +91,6 @@ __global__ __launch_bounds__(256) void softmin_partial_kernel(int64_t n, int64_t
                     for (int k = 0; k < D; ++k) a = __builtin_elementwise_fma(F2{xs[r][k], xs[r + 1][k]}, F2{pk[k], pk[k]}, a);
                     v[r][c] = a.x; v[r + 1][c] = a.y;
                 }
-#endif
             }
             float sc[kRows];
 #pragma unroll

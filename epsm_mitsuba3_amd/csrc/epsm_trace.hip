@@ -5,7 +5,6 @@
 #include "epsm_common.h"
 #include "epsm_trace_core.h"
 #include "epsm_trace_wavefront.h"
-#include "epsm_trace_quad.h"
 #include "epsm_trace_packet.h"
 #include "epsm_wave_scatter.h"           // wave_total_lane63 (DPP sums): the first-hit stage
 
@@ -25,16 +24,12 @@ __global__ __launch_bounds__(128, 4) void epsm_trace_kernel(TraceArgs A) {
     const int64_t i = (int64_t) blockIdx.x * 128 + threadIdx.x;
     BvhStack st{s_stack + threadIdx.x, 128};
     st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
-#ifdef EPSM_MEGA_NO_PACKET
-    if (i >= A.N) return;
-    trace_one_path(A, i, st);
-#else
     // trace_one_path with the PRIMARY rays walked by the wave (epsm_trace_packet.h: the lanes of a wave are the samples of one
     // pixel or of a few neighbours); the packet's LDS column is entry 0 of the wave's own per-lane stacks, not yet in use
     const bool has = i < A.N;
     if (__ballot(has) == 0ull) return;
     PathState s = path_begin(A, has ? i : A.N - 1, has);
-    const TriHit th0 = packet_intersect<false>(A.S, s.ray, has, s_stack + (threadIdx.x & ~63));
+    const TriHit th0 = packet_intersect(A.S, s.ray, has, s_stack + (threadIdx.x & ~63));
     if (!has) return;
     InlineVis vis{st};
     const int max_depth = path_max_depth(A);
@@ -45,7 +40,6 @@ __global__ __launch_bounds__(128, 4) void epsm_trace_kernel(TraceArgs A) {
         path_bounce(A, i, iteration, s, th, vis);
     }
     path_end(A, i, s);
-#endif
 }
 
 // ---- the wavefront form (epsm_trace_wavefront.h): queues of live paths, three small kernels per bounce ----
@@ -85,16 +79,8 @@ __global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_kernel(TraceArgs A,
 // backward pass: every path's grad_d into the wave's share of -sum grad_d, and the first-vertex rows of the paths retired at their
 // first hit.  Lanes on the same triangle are summed first (butterfly over the wave, in up to four turns of "the first lane still
 // owing and everybody on its triangle"), one lane adds the sum; what is left after four turns adds for itself.
-#ifdef EPSM_FH_SHUFFLE_SUM                // (A/B build: the butterfly through the LDS crossbar)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-#else
 // sum over the wave by six DPP adds (epsm_wave_scatter.h: the total lands in lane 63) + one readlane: no trip through the LDS crossbar
 __device__ __forceinline__ float wave_sum(float v) { return lane63(wave_total_lane63(v)); }
-#endif
 __device__ __forceinline__ void first_hit_add(float *p, float v) { if (v != 0.f && fabsf(v) < __builtin_inff()) atomicAdd(p, v); }
 __device__ __forceinline__ void first_hit_scatter(const TraceArgs &A, const WfState &W, const WfFirstHit &fh, unsigned wave_index) {
     const int lane = threadIdx.x & 63;
@@ -169,7 +155,7 @@ __global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_packet_kernel(Trace
             const W4 o = W.ray_o[i], d = W.ray_d[i];
             r.o = xyz(o); r.maxt = u2f(o.w); r.d = xyz(d);
         }
-        const TriHit th = packet_intersect<false>(A.S, r, has, s_stack + wv * kPacketStack);
+        const TriHit th = packet_intersect(A.S, r, has, s_stack + wv * kPacketStack);
         bool done = false;
         if (fuse) {
             if (has) {
@@ -193,28 +179,6 @@ __global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_packet_kernel(Trace
         if (has && !done) {
             W4 h; h.x = th.hit ? th.tri : kNoIndex; h.y = f2u(th.t); h.z = f2u(th.u); h.w = f2u(th.v);
             W.hit[i] = h;
-        }
-    }
-}
-// The visibility rays the same way (A/B build).
-__global__ __launch_bounds__(kWfThreads) void epsm_wf_shadow_packet_kernel(TraceArgs A, WfState W, int b) {
-    __shared__ uint32_t s_stack[kPacketStack * (kWfThreads / 64)];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t count = (int64_t) W.counters[8 + b];
-    for (int64_t q0 = (int64_t) blockIdx.x * kWfThreads + wv * 64; q0 < count; q0 += (int64_t) gridDim.x * kWfThreads) {     // wave-uniform
-        const int64_t q = q0 + lane;
-        const bool has = q < count;
-        const int64_t i = (int64_t) W.shadow_queue[has ? q : q0];
-        const W4 o = W.sh_o[i], d = W.sh_d[i];
-        Ray sr; sr.o = xyz(o); sr.maxt = u2f(o.w); sr.d = xyz(d);
-        const TriHit th = packet_intersect<true>(A.S, sr, has, s_stack + wv * kPacketStack);
-        const bool owed = has && wf_shadow_resolve(A, W, i, b, th.hit);
-        if (__ballot(owed) != 0ull) {                                    // (integrators with max_depth <= 3: the occluder record)
-            F3 sip = zero3<float>(), esp = sip;
-            Ray r2; r2.o = r2.d = sip; r2.maxt = 0.f;
-            if (owed) r2 = wf_occluder_ray(A, W, i, sip, esp);
-            const TriHit oh = packet_intersect<false>(A.S, r2, owed, s_stack + wv * kPacketStack);
-            if (owed) write_occluder(A.S, A.rec[0].shadow + 4 * i, r2, oh, sip, esp);
         }
     }
 }
@@ -256,7 +220,7 @@ __global__ __launch_bounds__(kWfChunk) void epsm_wf_shade_kernel(TraceArgs A, Wf
     const int64_t q = chunk * kWfChunk + threadIdx.x;
     bool alive = false, shadow = false;
     // EPSM_TRACE_FUSE_FIRST_HIT: the primary rays' stage (packet kernel) has dealt with the paths that end at their first vertex and
-    // the survivors come here compacted (kWfPreCompact); without that stage (EPSM_WF_NO_PACKET builds) this one does it, wf_shade's `out`
+    // the survivors come here compacted (kWfPreCompact); without that stage (the host harness) this one does it, wf_shade's `out`
     const bool fuse = b == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && !(A.flags & kWfPreCompact);     // (kernel-uniform)
     WfFirstHit fh;
     fh.rows.on = false; fh.rows.key[0] = fh.rows.key[1] = fh.rows.key[2] = kNoIndex;
@@ -336,10 +300,8 @@ __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState
 // (Tried: grouping the survivors of a chunk by the octant of their new direction, 8-bucket counting sort in LDS --
 // 4.95 -> 5.85 ms at 128 k triangles, 8.1 -> 9.3 ms at 512 k: path order keeps the samples of a pixel, which start
 // from almost the same point, next to each other, and that is worth more than a shared direction octant.)
-// Round 4, EPSM_WF_REKEY=<shift>: inside its 256-slot chunk a queue is written grouped by the triangle the
-// rays LEAVE (key = leaf-order triangle id >> shift hashed into 64 buckets, counting sort in LDS) instead of in path order:
-// rays that leave one triangle (or one BVH leaf: ids are leaf-ordered) start together.  Different from the octant sort above:
-// the chunk, and with it the pixel neighbourhood, is kept.
+// (And in round 4: inside its 256-slot chunk, grouped by the triangle the rays LEAVE -- the pixel neighbourhood kept -- slower
+// again, the shade stage's reads lose their coalescing: MEASUREMENTS.md 9.3, profiles/r04_j_tracer_rekey.txt.  Removed.)
 __global__ __launch_bounds__(kWfChunk) void epsm_wf_compact_kernel(TraceArgs A, WfState W, int b) {
     const int64_t count = wf_count(A, W, b);
     if (wf_in_tail(A, b, count)) return;
@@ -347,33 +309,6 @@ __global__ __launch_bounds__(kWfChunk) void epsm_wf_compact_kernel(TraceArgs A, 
     const int64_t q = chunk * kWfChunk + threadIdx.x;
     const uint8_t f = q < count ? W.flags[q] : (uint8_t) 0;
     const uint32_t i = q < count ? (wf_identity(A, b) ? (uint32_t) q : W.queue[b & 1][q]) : 0u;
-#ifdef EPSM_WF_REKEY
-    __shared__ uint32_t s_hist[2][64];
-    if (threadIdx.x < 128) s_hist[threadIdx.x >> 6][threadIdx.x & 63] = 0u;
-    const uint32_t tri = f ? W.hit[i].x : 0u;
-    const uint32_t key = (((tri >> EPSM_WF_REKEY) * 2654435761u) >> 26) & 63u;
-    __syncthreads();
-    uint32_t rank[2] = {0u, 0u};
-#pragma unroll
-    for (int which = 0; which < 2; ++which)
-        if ((f >> which) & 1) rank[which] = atomicAdd(&s_hist[which][key], 1u);
-    __syncthreads();
-    if (threadIdx.x < 128) {                                         // exclusive scan of the 64 buckets of both queues (one wave each)
-        const int which = threadIdx.x >> 6, l = threadIdx.x & 63;
-        const uint32_t c = s_hist[which][l];
-        uint32_t inc = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t) __shfl_up((int) inc, off); if (l >= off) inc += t; }
-        s_hist[which][l] = inc - c;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (!((f >> which) & 1)) continue;
-        const uint32_t off = W.chunk_counts[which * W.chunks + chunk] + s_hist[which][key] + rank[which];
-        (which == 0 ? W.queue[(b + 1) & 1] : W.shadow_queue)[off] = i;
-    }
-#else
     __shared__ uint32_t s_n[2][kWfChunk / 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long m[2] = {__ballot((f & kWfAlive) != 0), __ballot((f & kWfShadow) != 0)};
@@ -388,28 +323,7 @@ __global__ __launch_bounds__(kWfChunk) void epsm_wf_compact_kernel(TraceArgs A, 
         (which == 0 ? W.queue[(b + 1) & 1] : W.shadow_queue)[off] = i;
         if (b < 0 && which == 0 && A.fh.survivors) A.fh.survivors[off] = i;      // (the caller's copy: EpsmFirstHitBackward)
     }
-#endif
     __syncthreads();
-    }
-}
-// EPSM_WF_QUAD (A/B build, round 5): the closest-hit stage of the bounces >= 1 with FOUR LANES PER RAY (epsm_trace_quad.h): a
-// workgroup of 128 lanes takes 32 rays at a time.
-__global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_quad_kernel(TraceArgs A, WfState W, int b) {
-    __shared__ uint32_t s_stack[kQuadStack * (kWfThreads / 4)];
-    const int64_t count = wf_count(A, W, b);
-    if (wf_in_tail(A, b, count)) return;
-    const int lane = threadIdx.x & 63, quad = threadIdx.x >> 2;
-    for (int64_t q0 = (int64_t) blockIdx.x * (kWfThreads / 4); q0 < count; q0 += (int64_t) gridDim.x * (kWfThreads / 4)) {
-        const int64_t q = q0 + quad;
-        const bool has = q < count;
-        const int64_t i = has ? (int64_t) W.queue[b & 1][q] : 0;
-        Ray r; r.o = r.d = zero3<float>(); r.maxt = 0.f;
-        if (has) { const W4 o = W.ray_o[i], d = W.ray_d[i]; r.o = xyz(o); r.maxt = u2f(o.w); r.d = xyz(d); }
-        const TriHit th = quad_intersect<false>(A.S, r, has, s_stack + quad, kWfThreads / 4, lane);
-        if (has && (lane & 3) == 0) {
-            W4 h; h.x = th.hit ? th.tri : kNoIndex; h.y = f2u(th.t); h.z = f2u(th.u); h.w = f2u(th.v);
-            W.hit[i] = h;
-        }
     }
 }
 __global__ __launch_bounds__(kWfThreads) void epsm_wf_shadow_kernel(TraceArgs A, WfState W, int b) {
@@ -708,16 +622,11 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
     const WfState W = wf_carve(workspace, N);
     hipError_t e = hipMemsetAsync(W.counters, 0, wf_zeroed_bytes(N), s);          // the counters and the group counts behind them
     if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_wavefront", e);
-#ifdef EPSM_WF_NO_PACKET
-    if ((A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && A.fh.survivors)
-        return fail(EPSM_EINVAL, "epsm_trace_paths_wavefront: this build (EPSM_WF_NO_PACKET) compacts no survivors: first_hit->survivors must be NULL");
-#else
     if (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) {
         A.flags |= kWfPreCompact;                                                  // (the packet stage ADDS its survivors to the chunk counts)
         e = hipMemsetAsync(W.chunk_counts, 0, (size_t) W.chunks * 8, s);
         if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_wavefront", e);
     }
-#endif
     auto blocks = [&](int threads) { const int64_t b = (N + threads - 1) / threads; return dim3((unsigned) (b < kWfMaxBlocks ? b : kWfMaxBlocks)); };
     const int depth = path_max_depth(A);
     const dim3 shade_short((unsigned) (W.chunks < 16384 ? W.chunks : 16384));
@@ -730,34 +639,20 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
         // (bounces >= 1: the tail first -- it runs once, when the queue has become short, and the stages behind it leave at once)
         if (b >= 1 && !(A.flags & EPSM_TRACE_NO_TAIL)) hipLaunchKernelGGL(epsm_wf_tail_kernel, tail_blocks, dim3(kWfThreads), 0, s, A, W, b);
         if (b == 0) {
-#ifdef EPSM_WF_NO_PACKET
-            hipLaunchKernelGGL(epsm_wf_extend_kernel<true>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
-#else
             hipLaunchKernelGGL(epsm_wf_extend_packet_kernel<true>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
             if (A.flags & kWfPreCompact) {                       // the survivors of the primary rays' stage, compacted: "bounce -1"
                 hipLaunchKernelGGL(epsm_wf_scan_kernel, dim3(2), dim3(1024), 0, s, A, W, -1);
                 hipLaunchKernelGGL(epsm_wf_compact_kernel, chunk_blocks, dim3(kWfChunk), 0, s, A, W, -1);
             }
-#endif
         }
-#if defined(EPSM_WF_QUAD)
-        else hipLaunchKernelGGL(epsm_wf_extend_quad_kernel, blocks(kWfThreads / 4), dim3(kWfThreads), 0, s, A, W, b);
-#elif defined(EPSM_WF_PACKET_BOUNCE)
-        else hipLaunchKernelGGL(epsm_wf_extend_packet_kernel<false>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
-#else
         else hipLaunchKernelGGL(epsm_wf_extend_kernel<false>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
-#endif
         // (the whole grid where every chunk has work -- bounce 0 of an unfused trace --, a capped one where the queue is short)
         hipLaunchKernelGGL(epsm_wf_shade_kernel, (b == 0 && !(A.flags & kWfPreCompact)) ? chunks : shade_short, dim3(kWfChunk), 0, s, A, W, b);
         if (b == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && A.fh.grad_o_sum)
             hipLaunchKernelGGL(epsm_wf_first_hit_finish_kernel, dim3(1), dim3(kWfFirstHitSlots), 0, s, A, W);
         hipLaunchKernelGGL(epsm_wf_scan_kernel, dim3(2), dim3(1024), 0, s, A, W, b);
         hipLaunchKernelGGL(epsm_wf_compact_kernel, chunk_blocks, dim3(kWfChunk), 0, s, A, W, b);
-#ifdef EPSM_WF_PACKET_SHADOW
-        hipLaunchKernelGGL(epsm_wf_shadow_packet_kernel, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
-#else
         hipLaunchKernelGGL(epsm_wf_shadow_kernel, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
-#endif
     }
     // (radiance / valid not asked for and the native log: nothing is left to write -- the gradient-only trace of render_backward)
     if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))

@@ -1,5 +1,5 @@
 // epsm_trace_packet.h -- WAVE-PACKET traversal of the four-wide BVH, device only.  The product uses it for the PRIMARY rays (both
-// tracer forms); for bounce and visibility rays it is an A/B build that lost (-DEPSM_WF_PACKET_BOUNCE / _SHADOW: MEASUREMENTS.md 10.10).
+// tracer forms) and for the reparameterised pass's auxiliary rays; for bounce and visibility rays it lost (MEASUREMENTS.md 10.10).
 //
 // The wavefront is pixel-major, sample-minor (common.py:320-330): the 64 lanes of a wave are the samples of one pixel (spp >= 64) or of
 // a few neighbouring ones -- rays that leave one point within a fraction of a degree.  The per-lane traversal (trav_round,
@@ -33,8 +33,6 @@ typedef const __attribute__((address_space(4))) int32_t *ConstI;
 __device__ __forceinline__ uint32_t packet_key(float t) { return __float_as_uint(t); }      // t >= 0: ordered as integers
 
 // All 64 lanes call it; `has_ray`: this lane carries a ray.  stack: the wave's LDS column (kPacketStack words).
-// ANY_HIT: a lane is done with its first hit (visibility rays); the walk ends when every lane is.
-template <bool ANY_HIT>
 __device__ __forceinline__ TriHit packet_intersect(const EpsmScene &S, const Ray &r0, bool has_ray, uint32_t *stack) {
     Ray r = r0;
     const F3 inv_d = f3(fminf(fmaxf(1.f / r.d.x, -1e18f), 1e18f), fminf(fmaxf(1.f / r.d.y, -1e18f), 1e18f), fminf(fmaxf(1.f / r.d.z, -1e18f), 1e18f));
@@ -95,10 +93,8 @@ __device__ __forceinline__ TriHit packet_intersect(const EpsmScene &S, const Ray
                 if (has_ray && moeller_trumbore(r, p0, p1, p2, tt, uu, vv)) {
                     best.hit = true; best_e = e; best.t = tt; best.u = uu; best.v = vv;
                     r.maxt = tt;
-                    if (ANY_HIT) has_ray = false;
                 }
             }
-            if (ANY_HIT && __ballot(has_ray) == 0ull) break;
             cur = sp > 0 ? (int32_t) stack[--sp] : kBvhNone;
         }
     }

@@ -9,10 +9,9 @@
 //   * stand-alone scatter kernel: runs of adjacent lanes with an identical key
 //     triple are summed with a segmented shuffle scan when the wave has few
 //     runs; only the last lane of a run issues the atomic;
-//   * fused kernel: lanes with the same target (one pixel's samples on the first
-//     triangle, the couple of emitter triangles, a BSDF's alpha slot), adjacent
-//     or not, are summed with DPP adds in bounded leader rounds
-//     (merge_equal below; epsm_grad_scatter.hip, epsm_backward_cp.hip).
+//   * fused kernel (epsm_backward_cp.hip): lanes push their rows to the wave's
+//     LDS queue and table (WaveQueue, LdsTable below), whose integer atomics
+//     take same-address lanes well enough that no merge precedes them.
 // Device-only code.
 #pragma once
 
@@ -310,76 +309,9 @@ __device__ __forceinline__ V3<float> wave_total_lane63(V3<float> v) {
     return mk3<float>(wave_total_lane63(v.x), wave_total_lane63(v.y), wave_total_lane63(v.z));
 }
 
-// Three rows of one merge round: lanes with `mine` are summed, the carrier lane receives the totals, the
-// other merged lanes are zeroed.  Out of line: it is used ~20 times per kernel and the fused kernel has to
-// stay inside the instruction cache.
-struct Rows3 { float v[9]; };
-#ifdef EPSM_MERGE_INLINE
-__device__ __forceinline__ Rows3 merge_rows3(Rows3 r, bool mine, bool carrier) {
-#else
-__device__ __attribute__((noinline)) Rows3 merge_rows3(Rows3 r, bool mine, bool carrier) {
-#endif
-#pragma unroll
-    for (int c = 0; c < 9; ++c) {
-        const float tot = lane63(wave_total_lane63(mine ? r.v[c] : 0.f));
-        r.v[c] = carrier ? tot : (mine ? 0.f : r.v[c]);
-    }
-    return r;
-}
-#ifdef EPSM_MERGE_INLINE
-__device__ __forceinline__ float merge_row1(float v, bool mine, bool carrier) {
-#else
-__device__ __attribute__((noinline)) float merge_row1(float v, bool mine, bool carrier) {
-#endif
-    const float tot = lane63(wave_total_lane63(mine ? v : 0.f));
-    return carrier ? tot : (mine ? 0.f : v);
-}
-
-// fewer lanes than this: the DPP sums (VALU, the kernel's bottleneck) cost more than the LDS atomics they save
-// (measured on the bathroom / specular / pool profiles: 4, 8, 16, 32 for the triangle rows)
-constexpr int kMinMergeLanes = 16, kMinMergeLanesAlpha = 4;
-
-// Lanes whose rows go to the SAME three parameter rows (the samples of one pixel at the first hit, the
-// two triangles of an area light, one BSDF's alpha) are summed over the wave with DPP adds and the first
-// of them alone carries the sum on: the LDS table then sees one row instead of up to 64 same-address
-// atomics, which it executes one after the other.  Up to ROUNDS distinct targets per call; a round that
-// would merge fewer than kMinMergeLanes lanes ends the search.
-template <int ROWS, int ROUNDS>
-__device__ __forceinline__ void merge_equal(bool &any, const uint32_t id[3], V3<float> vals[ROWS], int live_rows = ROWS) {
-    constexpr int kMin = ROWS == 1 ? kMinMergeLanesAlpha : kMinMergeLanes;
-#ifndef EPSM_CP_MERGE       // Round 4: OFF.  With integer LDS rows same-address lanes no longer serialise as float atomics did, and at three
-    return;                 // waves per SIMD the DPP sums cost more issue slots than the table saves: 2.22 -> 2.17 ms without them.
-#endif
-    unsigned long long pending = __ballot(any);
-#pragma unroll 1
-    for (int round = 0; round < ROUNDS; ++round) {
-        if (__popcll(pending) < kMin) return;
-        const int leader = __ffsll((long long) pending) - 1;
-        const uint32_t l0 = (uint32_t) __builtin_amdgcn_readlane((int) id[0], leader),
-                       l1 = (uint32_t) __builtin_amdgcn_readlane((int) id[1], leader),
-                       l2 = (uint32_t) __builtin_amdgcn_readlane((int) id[2], leader);
-        const bool mine = any && id[0] == l0 && id[1] == l1 && id[2] == l2;
-        const unsigned long long mm = __ballot(mine);
-        pending &= ~mm;
-        if (__popcll(mm) < kMin) return;                             // incoherent wave: stop searching
-        const bool carrier = lane_id() == leader;
-        if (ROWS == 1) {
-            vals[0].x = merge_row1(vals[0].x, mine, carrier);        // alpha rows carry one component
-        } else {
-#pragma unroll
-            for (int j = 0; j + 2 < ROWS; j += 3) {
-                if (j >= live_rows) break;                           // wave-uniform: rows nobody has
-                Rows3 r = {{vals[j].x, vals[j].y, vals[j].z, vals[j + 1].x, vals[j + 1].y, vals[j + 1].z,
-                            vals[j + 2].x, vals[j + 2].y, vals[j + 2].z}};
-                r = merge_rows3(r, mine, carrier);
-                vals[j] = mk3<float>(r.v[0], r.v[1], r.v[2]);
-                vals[j + 1] = mk3<float>(r.v[3], r.v[4], r.v[5]);
-                vals[j + 2] = mk3<float>(r.v[6], r.v[7], r.v[8]);
-            }
-        }
-        if (mine && !carrier) any = false;
-    }
-}
+// (Lanes with the SAME target -- one pixel's samples on the first triangle, the couple of emitter triangles, a BSDF's alpha
+// slot -- summed over the wave with DPP adds before the fused kernel's table: removed, measured slower since round 4's integer
+// LDS rows, 2.22 -> 2.17 ms without it: MEASUREMENTS.md 9.1.)
 
 // Direct insertion: LDS atomics merge equal keys natively (same-address lanes serialise
 // at LDS speed), which beats shuffle scans when runs are short.
