@@ -122,6 +122,22 @@ def _declare(lib):
     lib.epsm_get_option.restype = C.c_int64
     lib.epsm_get_option.argtypes = [C.c_int]
     declare_tracer(lib)
+    declare_bvh(lib)
+    return lib
+
+
+def declare_bvh(lib):
+    """Prototypes of the BVH build / refit of include/epsm_trace.h (device library only)."""
+    lib.epsm_bvh_max_nodes.restype = C.c_int64
+    lib.epsm_bvh_max_nodes.argtypes = [C.c_int64]
+    lib.epsm_bvh_workspace_bytes.restype = C.c_size_t
+    lib.epsm_bvh_workspace_bytes.argtypes = [C.c_int64]
+    lib.epsm_bvh_build.restype = C.c_int
+    lib.epsm_bvh_build.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_bvh_refit.restype = C.c_int
+    lib.epsm_bvh_refit.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_int32, C.c_void_p, C.c_void_p]
     return lib
 
 

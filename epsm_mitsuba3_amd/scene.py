@@ -704,7 +704,12 @@ class Scene:
 
     def __init__(self, meshes: Sequence[Mesh], bsdfs: Sequence[dict], emitters: Sequence[dict],
                  sensors: Sequence[Sensor], device="cuda", bsdf_names: Optional[Sequence[str]] = None,
-                 tile_paths: int = _dist.TILE_PATHS):
+                 tile_paths: int = _dist.TILE_PATHS, bvh_builder: str = "host"):
+        if bvh_builder not in ("host", "device"):
+            raise ValueError(f"bvh_builder: 'host' or 'device', not {bvh_builder!r}")
+        # "host": build_bvh (numpy, cached by geometry) + DeviceBvh's torch refit; "device": epsm_bvh_build / epsm_bvh_refit
+        # (bvh.NativeBvh) -- same node format and depth bound, a different tree (an edge tie may report the other triangle)
+        self.bvh_builder = bvh_builder
         self.meshes, self.bsdf_desc, self.emitter_desc, self.sensors = list(meshes), list(bsdfs), list(emitters), list(sensors)
         self.bsdf_names = list(bsdf_names or [f"bsdf{i}" for i in range(len(bsdfs))])
         self.device = torch.device(device)
@@ -741,7 +746,7 @@ class Scene:
 
     # -- construction from the reference's dict shape ---------------------------------------
     @staticmethod
-    def from_dict(d: dict, device="cuda", base_dir: str = ".") -> "Scene":
+    def from_dict(d: dict, device="cuda", base_dir: str = ".", bvh_builder: str = "host") -> "Scene":
         assert d.get("type") == "scene"
         bsdfs, bsdf_names, named = [], [], {}
 
@@ -847,7 +852,7 @@ class Scene:
                 meshes.append(Mesh(key, v, f, n, bsdf=bsdf_id, emitter=emitter_id,
                                    flip_normals=bool(val.get("flip_normals", False)), is_mesh=(t != "rectangle"),
                                    face_normals=face_normals, uv=uv))
-        return Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names)
+        return Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder)
 
     # -- parameters ----------------------------------------------------------------------------
     def mesh(self, name: str) -> Mesh:
@@ -1031,7 +1036,10 @@ class Scene:
             table = np.zeros((1, 4), np.int64)
         self.tri_table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).to(dev)
         self.bvh = None
-        if self.T > 0:
+        if self.T > 0 and self.bvh_builder == "device":
+            from .bvh import NativeBvh
+            self.bvh = NativeBvh(self.positions, self.tri)           # builds and refits on the device: no cache needed
+        elif self.T > 0:
             # the tree's topology depends on the geometry alone: attach() / attach_alpha() / set_color() come back here with the
             # same triangles and must not pay the host-side build again (9 s at 128 k triangles; round 4's bench spent 100 s
             # attaching 34 meshes), nor does a second Scene over the same geometry (bench.py's legs)

@@ -362,6 +362,43 @@ enum { EPSM_PROBE_TEA = 0, EPSM_PROBE_PCG32 = 1, EPSM_PROBE_SAMPLER = 2, EPSM_PR
 #define EPSM_PROBE_OUT 16
 int epsm_probe(int what, int64_t n, const float *in, float *out, const void *cfg, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_bvh_build -- the four-wide BVH of T triangles on the device (csrc/epsm_trace_bvh.hip).  Replaces the native scene
+ *   construction of the reference (src/render/scene.cpp:66-74, scene_native.inl:10-36: the acceleration structure built
+ *   from the shapes) with the rules of the host builder (scene.py build_bvh): a Morton presort of the centroids, binned SAH
+ *   (16 bins per axis) while d + 1 + ceil(log2 n) <= 32 and the middle of the Morton-ordered range otherwise, leaves of <= 6
+ *   triangles, the four-wide collapse that keeps the tree inside 16 wide levels, and the boxes of epsm_bvh_refit.
+ *     positions (V,3) f32, tri (T,3) u32 (every entry < V)         device
+ *     nodes       >= epsm_bvh_max_nodes(T) EpsmBvhNode               device, written in breadth-first order (node 0 the root)
+ *     prim_index  (T) u32, tri_verts (T,9) f32                       device, the leaf order and the triangles in it
+ *     n_nodes, n_levels, level_begin (17 entries)                    HOST: wide level l is nodes [level_begin[l], level_begin[l + 1]),
+ *                                                                    level_begin[n_levels] = n_nodes, n_levels <= 16
+ *     workspace   device, 16-byte aligned, >= epsm_bvh_workspace_bytes(T): about 177 bytes per triangle; scratch
+ *   The build SYNCHRONISES with the host (it reads back the size of every level, about 50 times per build) and returns when
+ *   the tree is complete: it cannot be captured in a graph.  Deterministic: two builds of the same input are bit-identical.
+ *   EPSM_EINVAL for T < 1, T >= 2^28 (a leaf reference holds first << 3 in 31 bits), V < 1, a NULL pointer or a workspace
+ *   that is too small or misaligned -- checked before anything touches the device.
+ * ------------------------------------------------------------------------- */
+int64_t epsm_bvh_max_nodes(int64_t T);
+size_t epsm_bvh_workspace_bytes(int64_t T);
+int epsm_bvh_build(const float *positions, int64_t V, const uint32_t *tri, int64_t T,
+                   EpsmBvhNode *nodes, uint32_t *prim_index, float *tri_verts,
+                   int32_t *n_nodes, int32_t *level_begin, int32_t *n_levels,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * epsm_bvh_refit -- fresh boxes for moved vertices, same topology (the refit of DeviceBvh, scene.py, which replaces the
+ *   reference's Scene::parameters_changed rebuild after a vertex update, src/render/scene.cpp:304-327, scene_native.inl:36-55).  Any breadth-first
+ *   tree of this node format -- the host builder's included -- given its level table (HOST pointer, n_levels + 1 entries,
+ *   1 <= n_levels <= 16): tri_verts is re-gathered in place in prim_index order, then one launch per wide level, deepest
+ *   first, writes every slot's box: absent +-inf; a leaf the min / max of its triangles padded to lo - 1e-6 (1 + |lo|),
+ *   hi + 1e-6 (1 + |hi|), rounded step by step (bit-identical to the torch refit); an inner slot the union of its child's
+ *   four boxes.  Asynchronous on `stream`; no allocation.
+ * ------------------------------------------------------------------------- */
+int epsm_bvh_refit(const float *positions, int64_t V, const uint32_t *tri, const uint32_t *prim_index, int64_t T,
+                   EpsmBvhNode *nodes, int32_t n_nodes, const int32_t *level_begin, int32_t n_levels,
+                   float *tri_verts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
