@@ -123,6 +123,7 @@ def _declare(lib):
     lib.epsm_get_option.argtypes = [C.c_int]
     declare_tracer(lib)
     declare_bvh(lib)
+    declare_scene_tables(lib)
     return lib
 
 
@@ -138,6 +139,30 @@ def declare_bvh(lib):
     lib.epsm_bvh_refit.restype = C.c_int
     lib.epsm_bvh_refit.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_int32, C.c_void_p, C.c_void_p]
+    return lib
+
+
+def declare_scene_tables(lib):
+    """Prototypes of the device scene tables of include/epsm_trace.h (device library only)."""
+    lib.epsm_scene_topology_bytes.restype = C.c_size_t
+    lib.epsm_scene_topology_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.epsm_scene_topology_workspace_bytes.restype = C.c_size_t
+    lib.epsm_scene_topology_workspace_bytes.argtypes = [C.c_int64]
+    lib.epsm_scene_topology.restype = C.c_int
+    lib.epsm_scene_topology.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_vertex_normals.restype = C.c_int
+    lib.epsm_vertex_normals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p]
+    lib.epsm_emitter_tables_bytes.restype = C.c_size_t
+    lib.epsm_emitter_tables_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.epsm_emitter_tables.restype = C.c_int
+    lib.epsm_emitter_tables.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_environment_tables_bytes.restype = C.c_size_t
+    lib.epsm_environment_tables_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.epsm_environment_tables.restype = C.c_int
+    lib.epsm_environment_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]
     return lib
 
 

@@ -48,7 +48,7 @@ def _plate_vertices():
     return v, np.array(f)
 
 
-def load_scene(device="cuda", shift=(0.0, 0.0, 0.0)):
+def load_scene(device="cuda", shift=(0.0, 0.0, 0.0), **scene_kw):
     pv, pf = _plate_vertices()
     fv, ff = _quad(0.0, 4.0)
     lv, lf = _quad(3.0, 0.35)
@@ -61,7 +61,7 @@ def load_scene(device="cuda", shift=(0.0, 0.0, 0.0)):
                    "bsdf": {"type": "diffuse", "reflectance": {"type": "rgb", "value": [0.2, 0.2, 0.2]}}},
          "light": {"type": "mesh", "vertices": lv, "faces": lf[:, ::-1], "face_normals": True,
                    "emitter": {"type": "area", "radiance": {"type": "rgb", "value": 12.0}}}}
-    return Scene.from_dict(d, device=device)
+    return Scene.from_dict(d, device=device, **scene_kw)
 
 
 def gt_scene(device="cuda"):

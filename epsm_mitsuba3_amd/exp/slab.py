@@ -30,7 +30,7 @@ def _sensor(res, spp_):
             "sampler": {"type": "independent", "sample_count": spp_}}
 
 
-def load_scene(device="cuda", shift=(0.0, 0.0, 0.0)):
+def load_scene(device="cuda", shift=(0.0, 0.0, 0.0), **scene_kw):
     fv, ff = _quad(0.0, 5.0)
     tv, tf = _quad(1.0, 2.5, up=True)
     bv, bf = _quad(0.8, 2.5, up=False)
@@ -44,7 +44,7 @@ def load_scene(device="cuda", shift=(0.0, 0.0, 0.0)):
          "slab_bottom": {"type": "mesh", "vertices": bv, "faces": bf, "face_normals": True, "bsdf": glass},
          "light": {"type": "mesh", "vertices": lv + np.asarray(shift), "faces": lf, "face_normals": True,
                    "emitter": {"type": "area", "radiance": {"type": "rgb", "value": 30.0}}}}
-    return Scene.from_dict(d, device=device)
+    return Scene.from_dict(d, device=device, **scene_kw)
 
 
 def gt_scene(device="cuda"):

@@ -346,6 +346,7 @@ class Mesh:
         self.face_normals = face_normals
         self.has_normals = (not face_normals)
         self.n = None
+        self.normals_given = self.has_normals and n is not None       # scene_tables="device" recomputes only the others
         if self.has_normals:
             self.n = np.asarray(n, dtype=np.float64).reshape(-1, 3) if n is not None else vertex_normals(self.v, self.f)
         self.bsdf, self.emitter = bsdf, emitter
@@ -704,12 +705,18 @@ class Scene:
 
     def __init__(self, meshes: Sequence[Mesh], bsdfs: Sequence[dict], emitters: Sequence[dict],
                  sensors: Sequence[Sensor], device="cuda", bsdf_names: Optional[Sequence[str]] = None,
-                 tile_paths: int = _dist.TILE_PATHS, bvh_builder: str = "host"):
+                 tile_paths: int = _dist.TILE_PATHS, bvh_builder: str = "host", scene_tables: str = "host"):
         if bvh_builder not in ("host", "device"):
             raise ValueError(f"bvh_builder: 'host' or 'device', not {bvh_builder!r}")
+        if scene_tables not in ("host", "device"):
+            raise ValueError(f"scene_tables: 'host' or 'device', not {scene_tables!r}")
         # "host": build_bvh (numpy, cached by geometry) + DeviceBvh's torch refit; "device": epsm_bvh_build / epsm_bvh_refit
         # (bvh.NativeBvh) -- same node format and depth bound, a different tree (an edge tie may report the other triangle)
         self.bvh_builder = bvh_builder
+        # "host": vertex normals, emitter CDFs, mesh areas and envmap tables by numpy in _upload; "device": by the HIP entries of
+        # scene_tables (deterministic, fp64 sums from the float32 positions), and set_vertex_positions stays on the device for
+        # every mesh, emitting ones included
+        self.scene_tables = scene_tables
         self.meshes, self.bsdf_desc, self.emitter_desc, self.sensors = list(meshes), list(bsdfs), list(emitters), list(sensors)
         self.bsdf_names = list(bsdf_names or [f"bsdf{i}" for i in range(len(bsdfs))])
         self.device = torch.device(device)
@@ -746,7 +753,7 @@ class Scene:
 
     # -- construction from the reference's dict shape ---------------------------------------
     @staticmethod
-    def from_dict(d: dict, device="cuda", base_dir: str = ".", bvh_builder: str = "host") -> "Scene":
+    def from_dict(d: dict, device="cuda", base_dir: str = ".", bvh_builder: str = "host", scene_tables: str = "host") -> "Scene":
         assert d.get("type") == "scene"
         bsdfs, bsdf_names, named = [], [], {}
 
@@ -852,7 +859,8 @@ class Scene:
                 meshes.append(Mesh(key, v, f, n, bsdf=bsdf_id, emitter=emitter_id,
                                    flip_normals=bool(val.get("flip_normals", False)), is_mesh=(t != "rectangle"),
                                    face_normals=face_normals, uv=uv))
-        return Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder)
+        return Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder,
+                     scene_tables=scene_tables)
 
     # -- parameters ----------------------------------------------------------------------------
     def mesh(self, name: str) -> Mesh:
@@ -873,7 +881,12 @@ class Scene:
             return self._upload()
         for c, m in zip(self._mesh_structs, self.meshes):
             c.flags = m.flags()
-        self._mesh_buf.copy_(torch.frombuffer(bytearray(bytes(self._mesh_structs)), dtype=torch.uint8))
+        if self.scene_tables == "device":
+            # only the flags words: the areas in the device table are the device's (the host copy does not hold them)
+            flags = torch.tensor([m.flags() for m in self.meshes], dtype=torch.int32).to(self.device)
+            self._mesh_buf.view(torch.int32).view(-1, 8)[:len(self.meshes), 2] = flags
+        else:
+            self._mesh_buf.copy_(torch.frombuffer(bytearray(bytes(self._mesh_structs)), dtype=torch.uint8))
         if self.T > 0:
             mode = torch.tensor([(m.flags() & 0xF) | ((self.alpha_slots.get(m.bsdf, -1) + 1) << 8) for m in self.meshes],
                                 dtype=torch.int32, device=self.device)
@@ -955,9 +968,16 @@ class Scene:
         """``params['<mesh>.vertex_positions'] = v; params.update()``: everything stays on the device -- the
         rows of the flat position buffer are overwritten, vertex normals are recomputed like
         Mesh::parameters_changed does, the BVH is refitted (same topology, fresh boxes).  Only an emitting
-        mesh (its area / sampling CDF change) goes through the full host-side upload."""
+        mesh (its area / sampling CDF change) goes through the full host-side upload.
+
+        With ``scene_tables="device"`` every mesh, an emitting one included, stays on the device: its position rows, its vertex
+        normals (epsm_vertex_normals), its area and sampling CDF (epsm_emitter_tables), then the refit of the scene's tree.
+        Limit: the bounding sphere of an environment emitter is not recomputed (nor is it for a non-emitting mesh on the host
+        tables' device path); a move that takes geometry outside it needs a new Scene."""
         m = self.mesh(mesh_name)
         lo, hi = self.mesh_slices[mesh_name]
+        if self.scene_tables == "device" and self.bvh is not None:
+            return self._move_on_device(m, lo, hi, v)
         if m.emitter >= 0 or self.bvh is None:
             m.v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1, 3)
             if m.has_normals:
@@ -973,6 +993,36 @@ class Scene:
             t0, t1 = self.mesh_tri_slices[mesh_name]
             self.normals[lo:hi] = vertex_normals_torch(v_t, self.tri[t0:t1].long() - lo)
         self.bvh.refit(self.positions, self.tri)
+
+    def _move_on_device(self, m: Mesh, lo: int, hi: int, v):
+        from . import scene_tables as st
+        v_t = torch.as_tensor(v, dtype=torch.float32, device=self.device).detach().reshape(-1, 3)
+        if v_t.shape[0] != hi - lo:
+            raise ValueError(f"{m.name}: expected {hi - lo} vertices, got {v_t.shape[0]}")
+        i = self.meshes.index(m)
+        self.positions[lo:hi] = v_t
+        m.host_stale = True                                   # m.v / m.n are refreshed when the host needs them
+        if m.has_normals:
+            m.normals_given = False                           # recomputed on a move, as on the host tables' route
+            st.vertex_normals(self.positions, self._topology, self._mesh_structs, self._vertex_begin, self.normals, first=i, count=1)
+        st.emitter_tables(self.positions, self.tri, self._mesh_structs, self._mesh_buf, self.emitter_cdf, first=i, count=1)
+        self.bvh.refit(self.positions, self.tri)
+
+    def _device_tables(self, mesh_c):
+        """scene_tables="device": vertex normals, emitter CDFs and areas of every mesh from the HIP entries (in place of the
+        numpy ones _upload skipped).  Meshes whose normals came with the geometry keep them."""
+        from . import scene_tables as st
+        self._topology = st.SceneTopology(self.tri, self.V)
+        self._vertex_begin = [0]
+        for m in self.meshes:
+            self._vertex_begin.append(self._vertex_begin[-1] + m.v.shape[0])
+        want = (EpsmMesh * len(self.meshes))()
+        C.memmove(want, mesh_c, C.sizeof(want))
+        for c, m in zip(want, self.meshes):
+            if getattr(m, "normals_given", False):
+                c.flags &= ~MESH_VERTEX_NORMALS
+        st.vertex_normals(self.positions, self._topology, want, self._vertex_begin, self.normals)
+        st.emitter_tables(self.positions, self.tri, mesh_c, self._mesh_buf, self.emitter_cdf)
 
     def _sync_host_meshes(self):
         for m in self.meshes:
@@ -1001,6 +1051,7 @@ class Scene:
         if getattr(self, "positions", None) is not None:
             self._sync_host_meshes()
         pos, nrm, tri, tri_mesh, cdf = [], [], [], [], []
+        device_tables = self.scene_tables == "device"
         self.mesh_slices, self.mesh_tri_slices = {}, {}
         mesh_c = (EpsmMesh * max(1, len(self.meshes)))()
         voff = toff = coff = 0
@@ -1010,12 +1061,16 @@ class Scene:
             self.mesh_tri_slices[m.name] = (toff, toff + nt)
             pos.append(m.v); nrm.append(m.n if m.n is not None else np.zeros_like(m.v))
             tri.append(m.f + voff); tri_mesh.append(np.full(nt, mi_, np.uint32))
-            p = m.v[m.f]
-            areas = 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
             c = mesh_c[mi_]
             c.tri_begin, c.tri_count, c.flags, c.bsdf, c.emitter = toff, nt, m.flags(), m.bsdf, m.emitter
-            c.area, c.cdf_begin = float(areas.sum()), coff
-            cdf.append(np.cumsum(areas) / max(areas.sum(), 1e-30))
+            c.cdf_begin = coff
+            if device_tables:                                   # area and CDF: _device_tables
+                c.area = 0.0
+            else:
+                p = m.v[m.f]
+                areas = 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
+                c.area = float(areas.sum())
+                cdf.append(np.cumsum(areas) / max(areas.sum(), 1e-30))
             voff += nv; toff += nt; coff += nt
         self.V, self.T = voff, toff
         P = np.concatenate(pos) if pos else np.zeros((0, 3))
@@ -1025,7 +1080,10 @@ class Scene:
         self.normals = f32(np.concatenate(nrm) if nrm else np.zeros((0, 3)))
         self.tri = torch.from_numpy(np.ascontiguousarray(TRI, dtype=np.int32)).to(dev)
         self.tri_mesh = torch.from_numpy(np.ascontiguousarray(np.concatenate(tri_mesh) if tri_mesh else np.zeros(0), dtype=np.int32)).to(dev)
-        self.emitter_cdf = f32(np.concatenate(cdf) if cdf else np.zeros(1))
+        if device_tables:
+            self.emitter_cdf = torch.zeros(max(self.T, 1), dtype=torch.float32, device=dev)
+        else:
+            self.emitter_cdf = f32(np.concatenate(cdf) if cdf else np.zeros(1))
         # the triangle table of include/epsm.h: row t = [v0, v1, v2, EPSM_MODE_* of the owning mesh]; the tracer logs
         # triangle ids, the gradient kernels look the vertex rows up here
         # (+ bits 8..: alpha slot of the mesh's BSDF + 1, which the packed log does not carry per vertex)
@@ -1078,6 +1136,8 @@ class Scene:
         as_dev = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         self._mesh_buf, self._bsdf_buf, self._em_buf = as_dev(mesh_c), as_dev(bs), as_dev(em)
         self._mesh_structs = mesh_c                              # host copy: _refresh_attach_flags rewrites the flags in place
+        if device_tables and self.T > 0:
+            self._device_tables(mesh_c)                           # (the host copy's areas stay 0: the device table holds them)
         self._tex_struct_buf = as_dev(tx)
         s = EpsmSceneC()
         s.positions, s.normals = self.positions.data_ptr(), self.normals.data_ptr()
@@ -1112,8 +1172,12 @@ class Scene:
                 R = R / np.cbrt(abs(np.linalg.det(R)))
                 if not np.allclose(R @ R.T, np.eye(3), atol=1e-5):
                     raise ValueError("envmap: to_world must be a rotation")
-                tex, row_cdf, col_cdf, cell_pdf = environment_tables(e["bitmap"])
-                self._env_buf = [torch.from_numpy(a).to(dev) for a in (tex, row_cdf, col_cdf, cell_pdf)]
+                if device_tables:
+                    from . import scene_tables as st
+                    self._env_buf = list(st.environment_tables(f32(e["bitmap"])))
+                else:
+                    tex, row_cdf, col_cdf, cell_pdf = environment_tables(e["bitmap"])
+                    self._env_buf = [torch.from_numpy(a).to(dev) for a in (tex, row_cdf, col_cdf, cell_pdf)]
                 s.env.height, s.env.width = int(e["bitmap"].shape[0]), int(e["bitmap"].shape[1])
                 s.env.texels, s.env.row_cdf, s.env.col_cdf, s.env.cell_pdf = (t.data_ptr() for t in self._env_buf)
             s.env.to_local[:] = [float(x) for x in R.T.reshape(-1)]       # world -> emitter frame

@@ -399,6 +399,54 @@ int epsm_bvh_refit(const float *positions, int64_t V, const uint32_t *tri, const
                    EpsmBvhNode *nodes, int32_t n_nodes, const int32_t *level_begin, int32_t n_levels,
                    float *tri_verts, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Scene tables on the device (csrc/epsm_trace_scene.hip): what Scene._upload computes with numpy, behind the C ABI, so that a
+ * host with no Python builds a traceable scene and moves an emitting mesh without leaving the device.  All four run on `stream`
+ * with no host synchronisation and no allocation (scratch comes from the caller, sized by the *_bytes queries; topology and
+ * workspace 16-byte aligned), use no float atomics and sum in a fixed order: two calls on the same input give identical bits.
+ * EPSM_EINVAL (with epsm_last_error()) for a NULL pointer, a negative count, a too-small workspace or a mesh range outside T /
+ * V / cdf_len -- checked on the HOST copies of the tables before anything touches the device.
+ *
+ * epsm_scene_topology -- the vertex -> (triangle, corner) adjacency of T triangles in CSR form, by a device counting sort
+ *   (stable LSD radix sort of the 3 T corner entries by vertex): each vertex's corners in triangle order.  `topology` (device,
+ *   >= epsm_scene_topology_bytes(V, T)) is what epsm_vertex_normals reads; rebuild it when the triangles change, not when the
+ *   vertices move.  tri (T,3) u32, every entry < V.  1 <= T < 2^28, 1 <= V < 2^31.
+ * ------------------------------------------------------------------------- */
+size_t epsm_scene_topology_bytes(int64_t V, int64_t T);
+size_t epsm_scene_topology_workspace_bytes(int64_t T);
+int epsm_scene_topology(const uint32_t *tri, int64_t V, int64_t T, void *topology, size_t topology_bytes,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* epsm_vertex_normals -- angle-weighted vertex normals (scene.vertex_normals, Mesh::recompute_vertex_normals): per corner the
+ *   normalised face normal times the corner angle acos(clamp(cos, -1, 1)), summed per vertex in triangle order (fp64), then
+ *   normalised; a zero sum gives (0, 0, 1).  Written only for the vertex rows [vertex_begin[m], vertex_begin[m + 1]) of the meshes
+ *   flagged EPSM_MESH_VERTEX_NORMALS; every other row of `normals` is left as it is.  meshes (n_meshes) and vertex_begin
+ *   (n_meshes + 1, non-decreasing, inside 0 .. V) are HOST arrays; a sub-range of a scene's meshes is a valid table.
+ *   positions (V,3) f32, tri (T,3) u32, topology (epsm_scene_topology of the same tri), normals (V,3) f32: device. */
+int epsm_vertex_normals(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
+                        const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, float *normals, void *stream);
+
+/* epsm_emitter_tables -- for every mesh of the table, as Scene._upload does: the triangle areas 0.5 |(p1 - p0) x (p2 - p0)| from
+ *   the float32 positions, their normalised running sum written to emitter_cdf[cdf_begin .. cdf_begin + tri_count) and their sum
+ *   written IN PLACE to meshes_device[m].area (no other field is touched).  fp64 throughout, rounded to float32 once; the last
+ *   CDF entry of a mesh of non-zero area is exactly 1.  Chunks of 1024 triangles per workgroup: a mesh of any size spreads over
+ *   the whole device.  meshes: HOST copy of meshes_device (same ranges; the kernels read the device table and clip its ranges
+ *   to T and cdf_len); a sub-range of a scene's table (pointer and count) updates those meshes only.  The triangle ranges of
+ *   the non-empty meshes must not overlap, nor must their CDF ranges (EPSM_EINVAL). */
+size_t epsm_emitter_tables_bytes(int64_t T, int32_t n_meshes);
+int epsm_emitter_tables(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const EpsmMesh *meshes,
+                        EpsmMesh *meshes_device, int32_t n_meshes, float *emitter_cdf, int64_t cdf_len,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* epsm_environment_tables -- the EpsmEnvironment arrays of an (height, width, 3) lat-long map `bitmap` (scale applied), the rule
+ *   of scene.environment_tables: texels (height, width + 1, 3) with column `width` a copy of column 0; cell weights (mean over a
+ *   cell's four corners of luminance x sin theta, fp64); row_cdf (height - 1) and col_cdf (height - 1, width) normalised running
+ *   sums with the last entries exactly 1, uniform (linspace) for a zero row or a zero total; cell_pdf (height - 1, width) =
+ *   weight / total x width (height - 1), zero for a zero total.  width, height >= 2; all arrays device. */
+size_t epsm_environment_tables_bytes(int32_t width, int32_t height);
+int epsm_environment_tables(const float *bitmap, int32_t width, int32_t height, float *texels, float *row_cdf, float *col_cdf,
+                            float *cell_pdf, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
