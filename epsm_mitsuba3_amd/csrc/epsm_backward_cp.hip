@@ -476,7 +476,9 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
     V3<float> gd_acc = zero3<float>();                               // kTangentsInKernel: sum of grad_d over this lane's paths
     const int64_t n_slots = (kList && F.pk_list) ? (int64_t) lds_(F.pk_list_count, (int64_t) 0) : F.g.N;      // paths the windows run over
     const int64_t n_windows = (n_slots + window - 1) / window;
-    if (kList && (int64_t) blockIdx.x * windows_per_block >= n_windows) return;      // (workgroup-uniform: a launch sized for all N)
+    // (workgroup-uniform: a launch sized for all N).  Under EPSM_OPT_ONE_LAUNCH every workgroup of the grid is a member of its
+    // replica (`members` below): one without a window goes on -- through an empty window loop and an empty flush -- to be counted
+    if (kList && !F.rep_done && (int64_t) blockIdx.x * windows_per_block >= n_windows) return;
     T.clear();                                                       // ends with a barrier: the table of pointers is visible too
 #pragma unroll 1
     for (int64_t wi = 0; wi < windows_per_block; ++wi) {

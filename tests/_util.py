@@ -165,3 +165,18 @@ def select_paths(trace, idx):
     si = [{k: deep(v) for k, v in r.items()} for r in trace.scatter_info]
     return epsm.PathTrace(res=trace.res, spp=trace.spp, ray_o=cut(trace.ray_o), ray_d=cut(trace.ray_d), ray_dx=cut(trace.ray_dx),
                           ray_dy=cut(trace.ray_dy), path_info=pi, scatter_info=si, path_offset=0, n_paths_total=int(idx.numel()))
+
+
+def launch_form(N, V, B, small_wavefront_paths=1 << 20, replicas=True):
+    """-> (window, workgroups, replicas) of the accumulating backward kernel on N paths with V vertex rows and B alpha slots:
+    the arithmetic of ``launch`` in csrc/epsm_backward_cp.hip, restated so that a test can say which form it runs.  A small
+    wavefront (N <= small_wavefront_paths) is cut into windows of 128 .. 1024 paths, one per workgroup of 768 slots, and flushed
+    into R = workgroups / 16 (at most 32, at most 48 MiB) replicas of the buffers -- none below four; a large one walks windows
+    of 2048 paths and has no replicas."""
+    if N > small_wavefront_paths:
+        return 2048, -(-N // 2048), 0
+    window = min(max(-(-(-(-N // 768)) // 64) * 64, 128), 1024)
+    blocks = -(-N // window)
+    stride = -(-(6 * V + B + 3) // 64) * 64
+    R = min(blocks // 16, 32, (48 << 20) // (4 * stride))
+    return window, blocks, R if R >= 4 and replicas else 0

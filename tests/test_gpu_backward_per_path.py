@@ -89,3 +89,71 @@ def test_unbounded_emitter_weights_leave_finite_rows():
     assert live.any() and bool((got.sign() == want.sign()).all())
     assert float(got.abs().min()) > 5e5
     assert bool((b[1][:, big_paths][~live] == 0).all())
+
+
+# Launch forms of the small wavefront (_lib.options).  At N = 20 000 paths launch() cuts windows of 128 paths -- ceil(N / 768
+# workgroup slots) = 27, rounded up to 64 and raised to the minimum of 128 -- so 157 workgroups and R = 157 // 16 = 9 replicas of
+# 6 V + B + 3 floats with V = 6 N K, B = N K, as far as 48 MiB hold them: K = 1, 2.96 MB each -> 9 (157 is no multiple of 9: the
+# replicas have 17 or 18 members); K = 3, 8.9 MB -> 5; K = 5, 14.8 MB -> 3, fewer than 4, so no replicas -- the direct form.
+# "windows of 2048" moves the switch below N: the large form, no replicas either.
+LIST_FORMS = {"replicas": {}, "one launch": {"one_launch": True}, "direct": {"replicas": False},
+              "windows of 2048": {"small_wavefront_paths": 0}}
+
+
+@pytest.mark.parametrize("form", list(LIST_FORMS))
+@pytest.mark.parametrize("kind,profile", [("manifold", "bathroom"), ("manifold", "mixed"), ("manifold_caustic", "pool")])
+@pytest.mark.parametrize("K", [1, 3, 5])
+def test_path_list_per_path(kind, profile, K, form):
+    """The windows over a LIST of paths (EpsmPackedLog.path_list / path_count: what the tracer hands over under
+    EPSM_TRACE_FUSE_FIRST_HIT, the default traced route), path by path against the float64 oracle in every launch form.  ~15 % of
+    the paths are kept, path 0 and path N-1 among them, in random order; the others' flag words are 0.  The list has the capacity
+    N the tracer allocates, and its tail beyond the count repeats kept paths that carry terms: a kernel that reads past the count
+    counts one of them twice.  Dropped paths' rows must stay exactly 0, and the rows of the kept ones must equal, row by row, those
+    of the same launch over the whole log -- a path counted twice fails that, however few there are."""
+    import epsm_mitsuba3_amd as epsm
+    from epsm_mitsuba3_amd import _lib
+    from epsm_mitsuba3_amd.records import PackedLog
+    from epsm_mitsuba3_amd.tangent_scatter import backward_pass_packed
+    from _util import launch_form
+    dev = torch.device("cuda", 0)
+    res, spp = 50, 8
+    N = res * res * spp                      # 20 000 paths
+    V, B = 6 * N * K, N * K
+    window, _, replicas = launch_form(N, V, B, **{k: v for k, v in LIST_FORMS[form].items() if k != "one_launch"})
+    assert (window, replicas) == {"windows of 2048": (2048, 0), "direct": (128, 0)}.get(form, (128, {1: 9, 3: 5, 5: 0}[K]))
+    scene = epsm.SyntheticScene(res=res, n_vertices=K, n_scene_vertices=3000, n_bsdfs=4, profile=profile, device=dev, tile_paths=N)
+    trace = scene.tile(0, 0, N, seed=17 + K, spp=spp, K=K)
+    gen = torch.Generator().manual_seed(3)
+    table, si = private_addressing(N, K, dev, gen)
+    trace.scatter_info = si
+    grad_in = (torch.randn((res, res, 5), generator=gen) * 2e-5).to(dev)      # small tangents: few components near the +-0.1 clamp
+    log = PackedLog.from_trace(trace)
+    keep = torch.rand(N, generator=gen) < 0.15
+    keep[0] = keep[-1] = True
+    log.flags[~keep.to(dev)] = 0
+
+    def run():
+        p = epsm.ParamGrads(V, B, device=dev)
+        with _lib.options(**LIST_FORMS[form]):
+            backward_pass_packed(kind, log, grad_in, spp, res, p.pos, p.nrm, p.alpha, None, clip=0.1, path_offset=0)
+        torch.cuda.synchronize()
+        return p
+
+    whole = run()                                                # the same launch over all N paths
+    rows = lambda p: torch.cat([p.pos.view(2, K, N, 9).permute(2, 0, 1, 3).reshape(N, -1), p.nrm.view(2, K, N, 9).permute(2, 0, 1, 3).reshape(N, -1),
+                                p.alpha.view(K, N).t()], dim=1).double().cpu()      # (N, everything of the path)
+    w = rows(whole)
+    m = float(w.abs().max())
+    assert m > 0
+    ids = torch.nonzero(keep).flatten()
+    ids = ids[torch.randperm(ids.numel(), generator=gen)]
+    heavy = torch.nonzero(keep & (w.abs().amax(dim=1) > 1e-3 * m)).flatten()
+    assert heavy.numel() > 0
+    lst = torch.cat([ids, heavy.repeat(-(-(N - ids.numel()) // heavy.numel()))[:N - ids.numel()]]).to(torch.int32)
+    log.set_path_list(lst.to(dev), torch.tensor([ids.numel()], dtype=torch.int32, device=dev))
+    p = run()
+    check_private_rows(kind, trace, si, p, grad_in, K, label=f"{profile} path list, {form}", keep=keep, origin=False)
+    got = rows(p)
+    assert float(got[~keep].abs().max()) == 0.0
+    bad = (got - w).abs() > 1e-5 * w.abs() + 1e-7 * m
+    assert not bool(bad.any()), ("paths off the launch over the whole log", torch.nonzero(bad.any(dim=1)).flatten()[:8].tolist())

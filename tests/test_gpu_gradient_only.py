@@ -146,3 +146,51 @@ def test_first_hit_fusion_gives_the_same_gradients(scenes, variant):
         assert float(o0.abs().max()) > 0, name
         assert float((o0 - o1).abs().max()) <= 2e-5 * float(o0.abs().max()) + 1e-12, (name, o0, o1)
     assert fused_somewhere >= 3
+
+
+@pytest.mark.parametrize("variant", ["manifold", "manifold_caustic"])
+def test_first_hit_fusion_in_every_launch_form(scenes, variant):
+    """The default traced route (fuse_first_hit: the backward kernel runs its windows over the tracer's LIST of survivors,
+    EpsmPackedLog.path_list) in the other forms of a small wavefront (_lib.options): in ONE launch (EPSM_OPT_ONE_LAUNCH, the replicas
+    summed by their last workgroup) and without replicas -- the gradients of the default form (float order aside), the
+    camera-origin sum on its own scale.  Clutter at 128 x 128 x 8 = 131 072 paths is a small wavefront with replicas
+    (tests/_util.py, launch_form: windows of 192, 683 workgroups, 32 replicas as far as 48 MiB hold them -- at least 4)."""
+    import epsm_mitsuba3_amd as epsm
+    from epsm_mitsuba3_amd import _lib
+    from _util import launch_form
+    dev = torch.device("cuda", 0)
+    listed = 0
+    for name, sc, max_depth in scenes:
+        sc.tracer = "wavefront"
+        res = sc.sensors[2].width
+        g = torch.Generator().manual_seed(7)
+        grad_in = (torch.randn((res, res, 5), generator=g) * 1e-3).to(dev)
+        out = {}
+        for form, opts in (("default", {}), ("one launch", {"one_launch": True}), ("direct", {"replicas": False})):
+            integ = epsm.load_dict({"type": variant, "max_depth": max_depth})
+            assert integ.fuse_first_hit
+            p = sc.param_grads()
+            with _lib.options(**opts):
+                integ.render_backward(sc, p, grad_in, seed=11)
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(p.flat).all()), (name, form)
+            out[form] = (p.flat.double().cpu(), p.cam_origin.double().cpu())
+        tiles = list(sc.iter_traces(sensor=2, seed=11, spp=integ.backward_spp, max_depth=integ.tracer_depth(), sparse_log=True,
+                                    packed_log=True, gradient_only=variant,
+                                    first_hit=(grad_in, sc.param_grads(), 0.1, True)))
+        if all(t.log.first_hit_done and t.log.path_list is not None for t in tiles):
+            listed += 1
+        if name == "clutter":
+            p = sc.param_grads()
+            assert [t.log.N for t in tiles] == [128 * 128 * 8], name
+            window, _, replicas = launch_form(tiles[0].log.N, p.pos.shape[0], p.alpha.numel())
+            assert window == 192 and replicas >= 4, (window, replicas)
+        ref, ref_o = out["default"]
+        m = float(ref.abs().max())
+        assert m > 0 or variant == "manifold_caustic", name
+        assert float(ref_o.abs().max()) > 0, name
+        for form in ("one launch", "direct"):
+            f, o = out[form]
+            assert float((f - ref).abs().max()) <= 2e-5 * m + 1e-12, (name, form, m, float((f - ref).abs().max()))
+            assert float((o - ref_o).abs().max()) <= 2e-5 * float(ref_o.abs().max()) + 1e-12, (name, form, ref_o, o)
+    assert listed >= 3

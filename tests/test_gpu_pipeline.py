@@ -455,3 +455,225 @@ def test_path_list_gives_the_sums_of_the_whole_log(kind, profile, res, spp):
     assert m > 0 and float((out[0] - out[1]).abs().max()) <= 1e-5 * m
     with pytest.raises(Exception):                                   # the list form takes no grad_o_sum
         backward_pass_packed(kind, log, grad_in, spp, res, p.pos, p.nrm, p.alpha, p.cam_origin, clip=0.1, path_offset=0)
+
+
+# ---- the windows over a path list (EpsmPackedLog.path_list / path_count) against the float64 oracle, in every launch form
+# (_lib.options).  The synthetic log of test_path_list_gives_the_sums_of_the_whole_log: at 24 x 24 x 16 = 9216 paths launch() cuts
+# windows of 128 paths, 72 workgroups, 72 // 16 = 4 replicas (tests/_util.py, launch_form); 64 x 64 x 512 = 2^21 paths is the large
+# form, windows of 2048 and no replicas.
+LIST_FORMS = {"replicas": {}, "one launch": {"one_launch": True}, "direct": {"replicas": False},
+              "windows of 2048": {"small_wavefront_paths": 0}}
+
+
+@pytest.fixture(scope="module")
+def list_cases():
+    cache = {}
+    yield cache
+    cache.clear()
+
+
+def _list_case(cache, kind, profile, res, spp):
+    """(scene, trace, log with 85 % of its flag words zeroed, keep, grad_in, oracle sums over the kept paths + allowances) -- the
+    oracle once per log, for every form."""
+    key = (kind, profile, res, spp)
+    if key not in cache:
+        import epsm_mitsuba3_amd as epsm
+        from epsm_mitsuba3_amd.records import PackedLog
+        from _pipeline_oracle import oracle_backward
+        dev = torch.device("cuda", 0)
+        K, V, B = 4, 3000, 3
+        N = res * res * spp
+        scene = epsm.SyntheticScene(res=res, n_vertices=K, n_scene_vertices=V, n_bsdfs=B, profile=profile, device=dev, tile_paths=N)
+        g = torch.Generator().manual_seed(9)
+        grad_in = (torch.randn((res, res, 5), generator=g) * 1e-3).to(dev)
+        (trace,) = scene.trace_paths(seed=4, spp=spp, max_depth=8)
+        log = PackedLog.from_trace(trace)
+        flags = log.flags.clone()
+        keep = torch.rand(N, generator=g) < 0.15
+        keep[:5] = True; keep[-3:] = True
+        log.flags[~keep.to(dev)] = 0
+        ref = oracle_backward(kind, [trace], grad_in.cpu(), V, B, straddle_band=0.02, keep=keep, cond_limit=1e6)
+        cache.clear()                                            # (one log of 2^21 paths at a time)
+        cache[key] = dict(scene=scene, trace=trace, log=log, flags=flags, keep=keep, grad_in=grad_in, ref=ref, N=N, V=V, B=B, K=K)
+    return cache[key]
+
+
+def _set_list(log, ids, N, tail, gen, dev):
+    """The list as the tracer leaves it: ``ids`` in random order in an int32 tensor of capacity N, the count on the device; the
+    slots beyond the count hold ``tail`` repeated -- paths a kernel reading past the count would sum a second time."""
+    ids = ids[torch.randperm(ids.numel(), generator=gen)] if ids.numel() > 1 else ids
+    rest = N - ids.numel()
+    fill = tail.repeat(-(-rest // max(tail.numel(), 1)))[:rest] if rest and tail.numel() else torch.zeros(rest, dtype=torch.int64)
+    log.set_path_list(torch.cat([ids, fill]).to(torch.int32).to(dev), torch.tensor([ids.numel()], dtype=torch.int32, device=dev))
+
+
+def _clear_list(log):
+    log.path_list = log.path_count = None
+    log.c.path_list = log.c.path_count = None
+
+
+def _run_packed(case, opts, kind):
+    import epsm_mitsuba3_amd as epsm
+    from epsm_mitsuba3_amd import _lib
+    from epsm_mitsuba3_amd.tangent_scatter import backward_pass_packed
+    dev = torch.device("cuda", 0)
+    p = epsm.ParamGrads(case["V"], case["B"], device=dev)
+    res = case["trace"].res
+    with _lib.options(**opts):
+        backward_pass_packed(kind, case["log"], case["grad_in"], case["trace"].spp, res, p.pos, p.nrm, p.alpha, None, clip=0.1, path_offset=0)
+    torch.cuda.synchronize()
+    return p
+
+
+def _assert_oracle_sums(p, ref, what, few=False):
+    """test_render_backward_matches_oracle_pipeline's yardstick: 2e-3 of the buffer's magnitude plus the oracle's allowance, which
+    must stay the exception (pos, nrm) -- here with the few paths beyond cond_2 = 1e6 in it (tests/_pipeline_oracle.py: at 2^21
+    paths five of them move one sum of 9000 by 3 % of the buffer's magnitude, the same in every form and without a list); the list
+    form takes no camera-origin sum.  ``few``: a list of a handful of paths, which may
+    leave a buffer without a term (it must then stay zero up to the allowance) and whose allowance may be a whole path's."""
+    gp, gn, ga, _, allow = ref
+    for mine, r, slack, name in ((p.pos, gp, allow[0], "pos"), (p.nrm, gn, allow[1], "nrm"), (p.alpha, ga, allow[2], "alpha")):
+        m = float(r.abs().max())
+        assert m > 0 or few, (what, name)
+        err = (mine.cpu().double() - r).abs()
+        assert bool((err <= 2e-3 * m + slack).all()), (what, name, float((err - slack).max()) / max(m, 1e-30))
+        if name in ("pos", "nrm") and not few:
+            assert float(slack.sum() / r.abs().sum()) < 0.1, (what, name)
+
+
+@pytest.mark.parametrize("form", list(LIST_FORMS))
+@pytest.mark.parametrize("res,spp", [(24, 16), (64, 512)], ids=["9216 paths", "2^21 paths"])
+@pytest.mark.parametrize("kind,profile", [("manifold", "bathroom"), ("manifold_caustic", "pool")])
+def test_path_list_matches_the_oracle(list_cases, kind, profile, res, spp, form):
+    """The launch over a path list of ~15 % of the paths, in random order, the list's tail repeating kept paths, against the
+    float64 oracle summed over the kept paths alone."""
+    from _util import launch_form
+    case = _list_case(list_cases, kind, profile, res, spp)
+    N = case["N"]
+    small = {k: v for k, v in LIST_FORMS[form].items() if k != "one_launch"}
+    assert launch_form(N, case["V"], case["B"], **small)[2] == (4 if N == 9216 and form in ("replicas", "one launch") else 0)
+    gen = torch.Generator().manual_seed(21)
+    ids = torch.nonzero(case["keep"]).flatten()
+    _set_list(case["log"], ids, N, ids, gen, case["log"].flags.device)
+    _assert_oracle_sums(_run_packed(case, LIST_FORMS[form], kind), case["ref"], form)
+
+
+@pytest.mark.parametrize("threshold", ["N", "N - 1"])
+@pytest.mark.parametrize("kind,profile", [("manifold", "bathroom"), ("manifold_caustic", "pool")])
+def test_path_list_at_the_form_switch(list_cases, kind, profile, threshold):
+    """small_wavefront_paths = N takes the small form (N <= threshold: windows of 128, 4 replicas), N - 1 the large one
+    (windows of 2048): both the oracle's sums."""
+    from _util import launch_form
+    case = _list_case(list_cases, kind, profile, 24, 16)
+    N = case["N"]
+    t = N if threshold == "N" else N - 1
+    assert launch_form(N, case["V"], case["B"], small_wavefront_paths=t)[::2] == ((128, 4) if t == N else (2048, 0))
+    gen = torch.Generator().manual_seed(22)
+    ids = torch.nonzero(case["keep"]).flatten()
+    _set_list(case["log"], ids, N, ids, gen, case["log"].flags.device)
+    _assert_oracle_sums(_run_packed(case, {"small_wavefront_paths": t}, kind), case["ref"], threshold)
+
+
+def test_path_list_leaves_a_clean_workspace():
+    """The replicas of a small wavefront and their counters (EPSM_OPT_ONE_LAUNCH) are the library's, one workspace per stream,
+    kept zero between launches.  After a release, four launches on one stream, each into fresh buffers: a list under one launch,
+    a list by default, a whole scene (SyntheticScene.render_backward) under one launch, and by default.  Each must give what the
+    same input gives by default right after a release -- a launch that loses its replicas, or leaves them behind for the next,
+    fails here."""
+    import epsm_mitsuba3_amd as epsm
+    from epsm_mitsuba3_amd import _lib
+    from _util import launch_form
+    dev = torch.device("cuda", 0)
+    res, spp, K, V, B = 24, 16, 4, 3000, 3
+    N = res * res * spp
+    assert launch_form(N, V, B) == (128, 72, 4)
+    scene = epsm.SyntheticScene(res=res, n_vertices=K, n_scene_vertices=V, n_bsdfs=B, profile="bathroom", device=dev, tile_paths=N)
+    g = torch.Generator().manual_seed(9)
+    grad_in = (torch.randn((res, res, 5), generator=g) * 1e-3).to(dev)
+    case = {"trace": scene.trace_paths(seed=4, spp=spp, max_depth=8)[0], "grad_in": grad_in, "V": V, "B": B}
+    from epsm_mitsuba3_amd.records import PackedLog
+    case["log"] = log = PackedLog.from_trace(case["trace"])
+    keep = torch.rand(N, generator=g) < 0.15
+    keep[0] = keep[-1] = True
+    log.flags[~keep.to(dev)] = 0
+    ids = torch.nonzero(keep).flatten()
+    _set_list(log, ids, N, ids, g, dev)
+
+    def whole(opts):
+        integ = epsm.load_dict({"type": "manifold", "max_depth": 8})
+        integ.backward_spp = spp
+        p = epsm.ParamGrads(V, B, device=dev)
+        with _lib.options(**opts):
+            integ.render_backward(scene, p, grad_in, seed=7)
+        torch.cuda.synchronize()
+        return p.flat.double().cpu()
+
+    def listed(opts):
+        return _run_packed(case, opts, "manifold").flat.double().cpu()
+
+    def released(fn):
+        assert _lib.lib().epsm_release_workspace() == 0
+        return fn({})
+
+    ref_list, ref_whole = released(listed), released(whole)
+    assert float(ref_list.abs().max()) > 0 and float(ref_whole.abs().max()) > 0
+    assert _lib.lib().epsm_release_workspace() == 0
+    errs = {}
+    for name, fn, opts, ref in (("list, one launch", listed, {"one_launch": True}, ref_list), ("list, default", listed, {}, ref_list),
+                                ("whole, one launch", whole, {"one_launch": True}, ref_whole), ("whole, default", whole, {}, ref_whole)):
+        errs[name] = float((fn(opts) - ref).abs().max()) / float(ref.abs().max())
+    assert all(e <= 2e-4 for e in errs.values()), errs
+
+
+@pytest.mark.parametrize("form", ["windows of 128", "windows of 2048"])
+@pytest.mark.parametrize("kind,profile", [("manifold", "bathroom"), ("manifold_caustic", "pool")])
+def test_path_list_edge_counts(list_cases, kind, profile, form):
+    """path_count at its edges, in the small form (windows of 128 at N = 9216, replicas) and in the large one (windows of 2048):
+    0 -- the buffers stay exactly zero, under one launch too, and the next launch is still right; 1, as path 0 and as path N-1;
+    a window less one, a window, a window and one, two windows and one; N -- the identity list, which must give the launch without
+    a list.  Each list's tail repeats its own paths (for count 0: paths whose flag words are live), and each result is held to
+    the oracle's sums over the listed paths."""
+    import epsm_mitsuba3_amd as epsm
+    from _pipeline_oracle import oracle_backward
+    from _util import launch_form
+    case = _list_case(list_cases, kind, profile, 24, 16)
+    N, V, B = case["N"], case["V"], case["B"]
+    log, flags, trace = case["log"], case["flags"], case["trace"]
+    dev = flags.device
+    base = {"windows of 128": {}, "windows of 2048": {"small_wavefront_paths": 0}}[form]
+    window = launch_form(N, V, B, **base)[0]
+    assert window == {"windows of 128": 128, "windows of 2048": 2048}[form]
+    gen = torch.Generator().manual_seed(23)
+    saved = log.flags.clone()
+    try:
+        # count 0: nothing is summed, whatever the tail holds
+        log.flags.copy_(flags)
+        _set_list(log, torch.zeros(0, dtype=torch.int64), N, torch.randperm(N, generator=gen)[:64], gen, dev)
+        for opts in (base, {**base, "one_launch": True}):
+            p = _run_packed(case, opts, kind)
+            assert float(p.flat.abs().max()) == 0.0, opts
+        counts = [("path 0", torch.tensor([0])), ("path N-1", torch.tensor([N - 1]))]
+        for c in (window - 1, window, window + 1, 2 * window + 1):
+            counts.append((str(c), torch.randperm(N, generator=gen)[:c]))
+        for i, (what, ids) in enumerate(counts):
+            keep = torch.zeros(N, dtype=torch.bool)
+            keep[ids] = True
+            log.flags.copy_(torch.where(keep.to(dev), flags, torch.zeros_like(flags)))
+            _set_list(log, ids, N, ids, gen, dev)
+            opts = {**base, "one_launch": True} if i == 0 else base              # (the first right after the count-0 launches)
+            p = _run_packed(case, opts, kind)
+            ref = oracle_backward(kind, [trace], case["grad_in"].cpu(), V, B, straddle_band=0.02, keep=keep, cond_limit=1e6)
+            _assert_oracle_sums(p, ref, f"{form}, count {what}", few=ids.numel() < 8)
+        # count N, the identity list: the launch without a list
+        log.flags.copy_(flags)
+        out = []
+        for use_list in (False, True):
+            if use_list:
+                log.set_path_list(torch.arange(N, dtype=torch.int32, device=dev), torch.tensor([N], dtype=torch.int32, device=dev))
+            else:
+                _clear_list(log)
+            out.append(_run_packed(case, base, kind).flat.double().cpu())
+        m = float(out[0].abs().max())
+        assert m > 0 and float((out[0] - out[1]).abs().max()) <= 1e-5 * m
+    finally:
+        log.flags.copy_(saved)
