@@ -12,7 +12,7 @@ import ctypes as C
 import os
 import subprocess
 
-import torch  # noqa: F401  (must be loaded before libepsm_hip.so, see above)
+import torch  # loaded before libepsm_hip.so on purpose, see above
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 7          # EPSM_ABI_VERSION of include/epsm.h
@@ -121,6 +121,9 @@ def _declare(lib):
     lib.epsm_set_option.argtypes = [C.c_int, C.c_int64]
     lib.epsm_get_option.restype = C.c_int64
     lib.epsm_get_option.argtypes = [C.c_int]
+    lib.epsm_film_adjoint_reparam.restype = C.c_int
+    lib.epsm_film_adjoint_reparam.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
     declare_tracer(lib)
     declare_bvh(lib)
     declare_scene_tables(lib)
@@ -167,7 +170,8 @@ def declare_scene_tables(lib):
 
 
 def declare_tracer(lib):
-    """Prototypes of include/epsm_trace.h (also applied to the host build of the tracer in tests/host_harness)."""
+    """Prototypes of the tracer entry points of include/epsm_trace.h that the HIP library and the host build of the tracer
+    (tests/host_harness) both export; tests/_scenes.py applies them to the latter."""
     trace_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_uint32]
@@ -180,11 +184,14 @@ def declare_tracer(lib):
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.epsm_trace_workspace_bytes.restype = C.c_size_t
     lib.epsm_trace_workspace_bytes.argtypes = [C.c_int64]
+    lib.epsm_trace_reparam_workspace_bytes.restype = C.c_size_t
+    lib.epsm_trace_reparam_workspace_bytes.argtypes = [C.c_int64]
+    lib.epsm_trace_paths_reparam.restype = C.c_int
+    lib.epsm_trace_paths_reparam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.epsm_film_adjoint_reparam.restype = C.c_int
-    lib.epsm_film_adjoint_reparam.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int
     lib.epsm_film_develop.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
@@ -201,6 +208,13 @@ def lib():
         if _lib.epsm_abi_version() != ABI_VERSION:
             raise EpsmError("libepsm_hip.so ABI version mismatch")
     return _lib
+
+
+def stream(device):
+    """The handle of ``device``'s current stream for the ``void *stream`` argument of the C ABI; None (the null stream) for a
+    CPU device, which only the host build of the tracer (tests/host_harness) is called with."""
+    device = torch.device(device)
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
 
 
 def check(rc: int, what: str):

@@ -16,10 +16,6 @@ MAX_WIDE_LEVELS = 16            # scene.kMaxWideDepth
 ABSENT = 0x7fffffff
 
 
-def _stream(device: torch.device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _checked_inputs(positions: torch.Tensor, tri: torch.Tensor):
     if positions.device.type != "cuda" or tri.device.type != "cuda":
         raise ValueError("the device BVH needs positions and triangles on a GPU")
@@ -53,7 +49,7 @@ def refit(nodes: torch.Tensor, prim_index: torch.Tensor, tri_verts: torch.Tensor
     n_levels = len(level_begin) - 1
     lb = (C.c_int32 * (n_levels + 1))(*level_begin)
     rc = _lib.lib().epsm_bvh_refit(positions.data_ptr(), positions.shape[0], tri.data_ptr(), prim_index.data_ptr(), tri.shape[0],
-                                   nodes.data_ptr(), nodes.shape[0], lb, n_levels, tri_verts.data_ptr(), _stream(positions.device))
+                                   nodes.data_ptr(), nodes.shape[0], lb, n_levels, tri_verts.data_ptr(), _lib.stream(positions.device))
     _lib.check(rc, "epsm_bvh_refit")
 
 
@@ -79,7 +75,7 @@ class NativeBvh:
         lb = (C.c_int32 * (MAX_WIDE_LEVELS + 1))()
         rc = L.epsm_bvh_build(positions.data_ptr(), V, tri.data_ptr(), T, nodes.data_ptr(), self.prim_index.data_ptr(),
                               self.tri_verts.data_ptr(), C.byref(n_nodes), lb, C.byref(n_levels), ws.data_ptr(), ws_bytes,
-                              _stream(dev))
+                              _lib.stream(dev))
         _lib.check(rc, "epsm_bvh_build")
         del ws
         self.nodes = nodes[:n_nodes.value].clone()

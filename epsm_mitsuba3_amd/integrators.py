@@ -290,7 +290,7 @@ def film_adjoint_reparam(film_pos: torch.Tensor, radiance: torch.Tensor, grad_im
         g, acc = grad_img.detach().float().contiguous(), accum.detach().float().contiguous()
         dL = torch.empty((n, 3), device=film_pos.device, dtype=torch.float32)
         adj = torch.empty((n, 3), device=film_pos.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(film_pos.device).cuda_stream
+        stream = _lib.stream(film_pos.device)
         _lib.check(_lib.lib().epsm_film_adjoint_reparam(n, fp.data_ptr(), rad.data_ptr(), g.data_ptr(), int(g.shape[-1]), acc.data_ptr(),
                                                          int(acc.shape[1]), int(acc.shape[0]), dL.data_ptr(), adj.data_ptr(),
                                                          C.c_void_p(stream)), "epsm_film_adjoint_reparam")
@@ -387,21 +387,12 @@ class PRBIntegrator:
         si = min(sensor, len(scene.sensors) - 1)
         s = scene.sensors[si]
         spp = spp or s.spp
-        n_total = s.wavefront_size(spp)
         rank, world = _dist.world()
-        import ctypes as C
-        from . import _lib
-        lib = scene._backend if scene._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(scene.device).cuda_stream if scene.device.type == "cuda" else None
         accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
-        tiles = _dist.tile_ranges(n_total, scene.tile_paths)
         kept = []
-        for t in _dist.my_tiles(len(tiles), rank, world):
-            lo, hi = tiles[t]
+        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
-            rc = lib.epsm_film_splat(C.c_int64(hi - lo), C.c_void_p(film_pos.data_ptr()), C.c_void_p(radiance.data_ptr()),
-                                     s.width, s.height, s.rfilter, C.c_void_p(accum.data_ptr()), C.c_void_p(stream))
-            assert rc == 0, "epsm_film_splat failed"
+            scene.film_splat(accum, s, film_pos, radiance)
             kept.append((film_pos, sums))
         if world > 1:
             _dist.allreduce_param_grads(accum)
@@ -486,39 +477,23 @@ class PRBReparamIntegrator(PRBIntegrator):
                             "currently used. Please specify a smooth reconstruction filter in your scene description (e.g. "
                             "'gaussian', which is actually the default)")          # common.py:379-388
         spp = spp or s.spp
-        n_total = s.wavefront_size(spp)
         rank, world = _dist.world()
-        import ctypes as C
-        from . import _lib
-        lib = scene._backend if scene._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(scene.device).cuda_stream if scene.device.type == "cuda" else None
         # pass 1 (common.py:872-882): the primal estimate of every sample and the film they make
         accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
-        # tiles as large as the sharding allows, up to 2^23 paths (7 GB of warp requests): the later stages of a tile carry
-        # a fraction of its paths and under-fill the chip in 2^20-path tiles (4.26 M paths: 62 ms in five tiles, 57 ms in one)
-        # ... unless the caller set Scene.tile_paths: that is their memory bound and stays an upper bound
-        per_rank = -(-n_total // world)
-        tile = min(1 << 23, int(scene.tile_paths)) if getattr(scene, "tile_paths_explicit", False) else \
-            min(1 << 23, max(int(scene.tile_paths), per_rank))
-        tiles = _dist.tile_ranges(n_total, tile)
-        mine = list(_dist.my_tiles(len(tiles), rank, world))
-        kept = {}
-        for t in mine:
-            lo, hi = tiles[t]
+        tiles = scene.tile_plan(s.wavefront_size(spp), "reparam", rank, world)
+        kept = []
+        for lo, hi in tiles:
             with _prof.phase("epsm.prb_reparam.primal_pass"):
                 tr = scene._trace(si, seed, spp, self._depth(), 0, lo, hi)
-                rc = lib.epsm_film_splat(C.c_int64(hi - lo), C.c_void_p(tr.film_pos.data_ptr()), C.c_void_p(tr.radiance.data_ptr()),
-                                         s.width, s.height, s.rfilter, C.c_void_p(accum.data_ptr()), C.c_void_p(stream))
-            assert rc == 0, "epsm_film_splat failed"
-            kept[t] = (tr.film_pos, tr.radiance.contiguous())
+                scene.film_splat(accum, s, tr.film_pos, tr.radiance)
+            kept.append((tr.film_pos, tr.radiance.contiguous()))
         if world > 1:
             _dist.allreduce_param_grads(accum)
         # pass 2 (common.py:944-955): adjoint radiance, adjoint film position / determinant, the reparameterised replay
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         out = params.scratch() if world > 1 else params
-        for t in mine:
-            lo, hi = tiles[t]
-            film_pos, radiance = kept.pop(t)
+        for lo, hi in tiles:
+            film_pos, radiance = kept.pop(0)
             with _prof.phase("epsm.prb_reparam.film_adjoint"):
                 dL, adj = film_adjoint_reparam(film_pos, radiance, g, accum)
             with _prof.phase("epsm.prb_reparam.reparam_pass"):

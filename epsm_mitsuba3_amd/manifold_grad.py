@@ -19,10 +19,6 @@ from .records import PackedRecords, VARIANTS, num_param_grads
 OUTLIER_CLIP = 0.1   # epsm.py:932-944
 
 
-def _stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def manifold_grad_packed(variant: str, rec: PackedRecords, dlduv: torch.Tensor, dldp: torch.Tensor,
                          clip: float = OUTLIER_CLIP, dlduv_cols: Optional[int] = None,
                          out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
@@ -68,7 +64,7 @@ def manifold_grad_packed(variant: str, rec: PackedRecords, dlduv: torch.Tensor, 
         rc = _lib.lib().epsm_manifold_grad(
             VARIANTS[variant], N, K, rec.cam.data_ptr(), C.addressof(rec.records),
             d.data_ptr(), width, int(dlduv_cols), p.data_ptr(), float(clip),
-            out_p.data_ptr(), out_l.data_ptr(), out_d.data_ptr(), _stream_ptr(dev))
+            out_p.data_ptr(), out_l.data_ptr(), out_d.data_ptr(), _lib.stream(dev))
     _lib.check(rc, "epsm_manifold_grad")
     return out_p, out_l, out_d
 

@@ -88,7 +88,7 @@ def softmin_hip(eps: float, x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, w
         sc = _scratch[key] = torch.empty((max(need, 4) + 3) // 4, dtype=torch.float32, device=x.device)
     out = torch.empty((n,), dtype=torch.float32, device=x.device)
     w = torch.empty((n, D), dtype=torch.float32, device=x.device) if want_wsum else None
-    stream = torch.cuda.current_stream(x.device).cuda_stream
+    stream = _lib.stream(x.device)
     _lib.check(lib.epsm_sinkhorn_softmin(n, m, D, x.data_ptr(), y.data_ptr(), h.data_ptr(), float(eps), out.data_ptr(),
                                          w.data_ptr() if want_wsum else None, sc.data_ptr(), sc.numel() * 4, C.c_void_p(stream)),
                "epsm_sinkhorn_softmin")
@@ -112,7 +112,7 @@ def update_hip(eps: float, x: torch.Tensor, y: torch.Tensor, dual, log_weight: f
         sc = _scratch[key] = torch.empty((max(need, 4) + 3) // 4, dtype=torch.float32, device=x.device)
     out = torch.empty((n,), dtype=torch.float32, device=x.device)
     w = torch.empty((n, D), dtype=torch.float32, device=x.device) if want_wsum else None
-    stream = torch.cuda.current_stream(x.device).cuda_stream
+    stream = _lib.stream(x.device)
     _lib.check(lib.epsm_sinkhorn_update(n, m, D, x.data_ptr(), y.data_ptr(), dual.data_ptr() if dual is not None else None,
                                         float(log_weight), float(eps), prev.data_ptr() if prev is not None else None, out.data_ptr(),
                                         w.data_ptr() if want_wsum else None, sc.data_ptr(), sc.numel() * 4, C.c_void_p(stream)),

@@ -3,7 +3,7 @@ experiments use (EPSM/exp/*.py): ``obj`` / inline meshes / ``rectangle``, ``diff
 ``conductor``, ``roughconductor``, ``dielectric``, ``twosided``, ``area`` / ``point`` / ``constant`` / ``envmap`` emitters,
 ``perspective`` sensors with ``hdrfilm`` (+ ``box`` / ``gaussian`` rfilter) and an
 ``independent`` sampler.  Geometry is flattened into the arrays of ``EpsmScene``
-(include/epsm_trace.h); a median-split BVH is built on the host with numpy.
+(include/epsm_trace.h); a binned-SAH BVH is built on the host with numpy (or on the device: bvh.py).
 
     scene = Scene.from_dict({...})                       # mi.load_dict shape
     scene.attach("glass", positions=True)                # dr.enable_grad(params['glass.vertex_positions'])
@@ -721,12 +721,12 @@ class Scene:
         self.bsdf_names = list(bsdf_names or [f"bsdf{i}" for i in range(len(bsdfs))])
         self.device = torch.device(device)
         self._tile_paths = int(tile_paths)
-        self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it is an UPPER bound everywhere
+        self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it bounds prb_reparam's tiles (tile_plan)
         self.alpha_slots: Dict[int, int] = {}
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
         self.rr_depth = 5
         # test hook: tests/host_harness compiles the tracer's per-path code for the CPU and plugs
-        # its entry points in here; the product path (None) is the HIP library and needs a GPU
+        # its entry points in here; the product path (None) is the HIP library and needs a GPU (_runtime)
         self._backend = None
         # "mega": one launch, a lane carries its path through all bounces; "wavefront": queues of live paths,
         # three kernels per bounce; "auto": wavefront from WAVEFRONT_MIN_TRIANGLES triangles on (where the
@@ -741,9 +741,8 @@ class Scene:
 
     @property
     def tile_paths(self) -> int:
-        """Paths per tile of a pass (the sharding unit).  The wavefront tracer works in tiles of up to WAVEFRONT_TILE_PATHS
-        whatever this says (its workspace is 236 B per path); prb_reparam raises the DEFAULT to as much as the sharding allows
-        (7 GB of warp requests at 2^23 paths) but never exceeds a value the caller ASSIGNED -- their memory bound."""
+        """Paths per tile of a pass (the sharding unit); what each pass makes of it, and of a value the caller ASSIGNED:
+        tile_plan."""
         return self._tile_paths
 
     @tile_paths.setter
@@ -1196,6 +1195,10 @@ class Scene:
     # reference's own backward size; 0.62 / 0.80 at 2^20; 1.22 / 1.02 at 2^21 -- MEASUREMENTS.md 10.10)
     WAVEFRONT_MIN_PATHS = (1 << 20) + 1
 
+    # prb_reparam's tiles: up to 2^23 paths (7 GB of warp requests); the later stages of a tile carry a fraction of its paths
+    # and under-fill the chip in 2^20-path tiles (4.26 M paths: 62 ms in five tiles, 57 ms in one)
+    REPARAM_TILE_PATHS = 1 << 23
+
     def use_wavefront(self, n_paths=None) -> bool:
         """The tracer form of a launch over ``n_paths`` paths (None: of a large one -- what sizes the tiles)."""
         if self.tracer not in ("auto", "mega", "wavefront"):
@@ -1204,13 +1207,42 @@ class Scene:
             return False
         return self.tracer == "wavefront" or (self.tracer == "auto" and self.T >= self.WAVEFRONT_MIN_TRIANGLES)
 
+    def tile_plan(self, n_paths: int, pass_: str, rank: int, world_size: int):
+        """This rank's [lo, hi) tiles of a pass over ``n_paths`` paths: the wavefront cut into tiles, dealt round robin over the
+        ranks (dist.my_tiles).  The passes size their tiles differently, and an ASSIGNED tile_paths bounds prb_reparam's
+        alone (ADVICE: the wavefront form of "trace" widens past it):
+          "trace"    iter_traces, render_primal: tile_paths; the wavefront form widens it to as large as the sharding allows
+                     -- every rank still gets a tile -- up to WAVEFRONT_TILE_PATHS
+          "color"    prb's colour pass (one-launch tracer only): tile_paths
+          "reparam"  prb_reparam: as large as the sharding allows up to REPARAM_TILE_PATHS, but never above a tile_paths
+                     the caller assigned -- their memory bound"""
+        tile, per_rank = self.tile_paths, -(-n_paths // max(1, world_size))
+        if pass_ == "trace":
+            if self.use_wavefront():
+                tile = max(tile, min(self.WAVEFRONT_TILE_PATHS, per_rank))
+        elif pass_ == "reparam":
+            tile = min(self.REPARAM_TILE_PATHS, tile if self.tile_paths_explicit else max(tile, per_rank))
+        elif pass_ != "color":
+            raise ValueError(f"tile_plan: pass 'trace', 'color' or 'reparam', not {pass_!r}")
+        tiles = _dist.tile_ranges(n_paths, tile)
+        return [tiles[t] for t in _dist.my_tiles(len(tiles), rank, world_size)]
+
+    def _runtime(self):
+        """(library, stream) of a launch: the HIP library on the device's current stream, or the test backend ``_backend``
+        (tests/host_harness: the tracer's per-path code built for the CPU) on host memory."""
+        if self._backend is None and self.device.type != "cuda":
+            raise _lib.EpsmError("the tracer runs on the GPU only (no CPU fallback)")
+        return (_lib.lib() if self._backend is None else self._backend), _lib.stream(self.device)
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc != 0 and self._backend is not None:
+            raise RuntimeError(f"host tracer rc={rc}")
+        _lib.check(rc, what)
+
     def trace_color(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int):
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
+        lib, stream = self._runtime()
         dev = self.device
-        if dev.type != "cuda" and self._backend is None:
-            raise _lib.EpsmError("the tracer runs on the GPU only (no CPU fallback)")
-        lib = self._backend if self._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         n, Cn = hi - lo, len(self.color_slots)
         if Cn == 0:
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
@@ -1219,13 +1251,11 @@ class Scene:
         valid = torch.empty((n,), device=dev, dtype=torch.uint8)
         sums = torch.empty((n, Cn, 3), device=dev, dtype=torch.float32)
         cs = self.sensors[sensor_index].c_struct()
-        fn = lib.epsm_trace_paths_color
-        fn.restype = C.c_int
-        rc = fn(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-                C.c_int64(lo), C.c_int64(n), C.c_void_p(film_pos.data_ptr()), C.c_void_p(radiance.data_ptr()),
-                C.c_void_p(valid.data_ptr()), C.c_void_p(sums.data_ptr()), int(Cn), C.c_void_p(stream))
-        if rc != 0:
-            _lib.check(rc, "epsm_trace_paths_color") if self._backend is None else (_ for _ in ()).throw(RuntimeError(f"host tracer rc={rc}"))
+        rc = lib.epsm_trace_paths_color(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
+                                        int(self.rr_depth), C.c_int64(lo), C.c_int64(n), C.c_void_p(film_pos.data_ptr()),
+                                        C.c_void_p(radiance.data_ptr()), C.c_void_p(valid.data_ptr()), C.c_void_p(sums.data_ptr()),
+                                        int(Cn), C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_color")
         return film_pos, radiance, sums
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
@@ -1235,32 +1265,41 @@ class Scene:
         positions (and normals) into ``grad_pos`` / ``grad_nrm`` (V,3) given, per path, the radiance of the primal pass under
         the same seed, its adjoint and the adjoint of the film position + determinant (integrators.film_adjoint_reparam).
         ``antithetic``: EPSM_REPARAM_ANTITHETIC (auxiliary rays in mirrored pairs, reparam.py:82-84)."""
+        lib, stream = self._runtime()
         dev = self.device
-        if dev.type != "cuda" and self._backend is None:
-            raise _lib.EpsmError("the tracer runs on the GPU only (no CPU fallback)")
-        lib = self._backend if self._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         n = hi - lo
         for t_, w in ((radiance, 3), (adj_radiance, 3), (adj_film, 3)):
             assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, w) and t_.device.type == dev.type
         for t_ in (grad_pos, grad_nrm):
             assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (self.V, 3) and t_.device.type == dev.type
         cs = self.sensors[sensor_index].c_struct()
-        wsb = lib.epsm_trace_reparam_workspace_bytes
-        wsb.restype, wsb.argtypes = C.c_size_t, [C.c_int64]
-        need = int(wsb(C.c_int64(n)))
+        need = int(lib.epsm_trace_reparam_workspace_bytes(C.c_int64(n)))
         ws = getattr(self, "_reparam_ws", None)
         if ws is None or ws.numel() < max(need, 16) or ws.device != radiance.device:
             ws = self._reparam_ws = torch.empty(max(need, 16), device=radiance.device, dtype=torch.uint8)
-        fn = lib.epsm_trace_paths_reparam
-        fn.restype = C.c_int
-        rc = fn(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-                C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()),
-                C.c_void_p(adj_film.data_ptr()), int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
-                C.c_uint32(1 if antithetic else 0), C.c_void_p(grad_pos.data_ptr()), C.c_void_p(grad_nrm.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-                C.c_void_p(stream))
-        if rc != 0:
-            _lib.check(rc, "epsm_trace_paths_reparam") if self._backend is None else (_ for _ in ()).throw(RuntimeError(f"host tracer rc={rc}"))
+        rc = lib.epsm_trace_paths_reparam(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()),
+            C.c_void_p(adj_film.data_ptr()), int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
+            C.c_uint32(1 if antithetic else 0), C.c_void_p(grad_pos.data_ptr()), C.c_void_p(grad_nrm.data_ptr()), C.c_void_p(ws.data_ptr()),
+            C.c_size_t(ws.numel()), C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_reparam")
+
+    def film_splat(self, accum: torch.Tensor, sensor: Sensor, film_pos: torch.Tensor, radiance: torch.Tensor) -> None:
+        """``epsm_film_splat``: adds the samples of a tile -- film positions (n,2), radiance (n,3) -- into the film accumulator
+        ``accum`` (H,W,4) [r,g,b,w] of ``sensor`` with its reconstruction filter."""
+        lib, stream = self._runtime()
+        self._check(lib.epsm_film_splat(C.c_int64(film_pos.shape[0]), C.c_void_p(film_pos.data_ptr()), C.c_void_p(radiance.data_ptr()),
+                                        sensor.width, sensor.height, sensor.rfilter, C.c_void_p(accum.data_ptr()), C.c_void_p(stream)),
+                    "epsm_film_splat")
+
+    def film_develop(self, accum: torch.Tensor, sensor: Sensor) -> torch.Tensor:
+        """``epsm_film_develop``: the (H,W,3) image of a film accumulator (the weight division)."""
+        lib, stream = self._runtime()
+        img = torch.empty((sensor.height, sensor.width, 3), device=self.device, dtype=torch.float32)
+        self._check(lib.epsm_film_develop(sensor.width, sensor.height, C.c_void_p(accum.data_ptr()), C.c_void_p(img.data_ptr()),
+                                          C.c_void_p(stream)), "epsm_film_develop")
+        return img
 
     @staticmethod
     def _gradient_only_flags(gradient_only) -> int:
@@ -1282,12 +1321,34 @@ class Scene:
         """Paths alive into bounce 0..5 and visibility rays of bounce 0..5 of the LAST wavefront trace on the current stream
         (the counters the stages keep on the device; a host read, for reports).  Complete only with ``wavefront_tail = False``:
         the counters of the bounces the tail launch carried stay 0."""
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
-        ws = self._wf_workspace.get(stream)
+        ws = self._wf_workspace.get(_lib.stream(self.device))
         if ws is None:
             return None
         c = ws[:64].view(torch.int32).cpu().tolist()
         return {"alive": c[0:6], "shadow": c[8:14]}
+
+    def _launch_trace(self, sensor: Sensor, seed: int, spp: int, max_depth: int, K: int, lo: int, n: int, rays, film_pos, radiance,
+                      valid, recs, flags: int, gradient_only) -> None:
+        """The trace of paths [lo, lo + n) into the log ``recs`` and the given outputs (``rays``: the four ray arrays; None:
+        not written), ``flags`` completed by the gradient-only and tail bits.  The form is the one use_wavefront(n) picks: queues
+        of live paths, three small kernels per bounce (include/epsm_trace.h), with a scratch kept per stream -- launches on one
+        stream are ordered, two streams are not -- or the one launch."""
+        lib, stream = self._runtime()
+        wavefront = self.use_wavefront(n)
+        flags |= (self._gradient_only_flags(gradient_only) if K >= 1 else 0) | (self._tail_flag() if wavefront else 0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        args = [C.byref(self.c_scene), C.byref(sensor.c_struct()), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
+                int(self.rr_depth), C.c_int64(lo), C.c_int64(n), K, *map(ptr, rays), ptr(film_pos), ptr(radiance), ptr(valid),
+                C.c_void_p(C.addressof(recs)), C.c_uint32(flags)]
+        if wavefront and n > 0:
+            need = int(lib.epsm_trace_workspace_bytes(C.c_int64(n)))
+            ws = self._wf_workspace.get(stream)
+            if ws is None or ws.numel() < need:
+                ws = self._wf_workspace[stream] = torch.empty(need, device=self.device, dtype=torch.uint8)
+            rc = lib.epsm_trace_paths_wavefront(*args, C.c_void_p(ws.data_ptr()), C.c_size_t(need), C.c_void_p(stream))
+        else:
+            rc = lib.epsm_trace_paths(*args, C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths")
 
     def _trace_packed(self, sensor_index: int, seed: int, spp: int, max_depth: int, K: int, lo: int, hi: int, gradient_only=None,
                       first_hit=None):
@@ -1296,10 +1357,6 @@ class Scene:
         from .integrators import PathTrace
         from .records import PackedLog, alloc_log
         dev = self.device
-        if dev.type != "cuda" and self._backend is None:
-            raise _lib.EpsmError("the tracer runs on the GPU only (no CPU fallback)")
-        lib = self._backend if self._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         sensor = self.sensors[sensor_index]
         n = hi - lo
         assert K >= 1
@@ -1334,24 +1391,8 @@ class Scene:
                                       survivors.data_ptr() if survivors is not None else None,
                                       survivor_count.data_ptr() if survivor_count is not None else None)
             recs[0].first_hit = C.addressof(fh)
-        cs = sensor.c_struct()
-        args = [C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-                C.c_int64(lo), C.c_int64(n), K, C.c_void_p(rays.data_ptr()), None, None, None,
-                C.c_void_p(film_pos.data_ptr()) if want_image else None, C.c_void_p(radiance.data_ptr()) if want_image else None,
-                C.c_void_p(valid.data_ptr()) if want_image else None,
-                C.c_void_p(C.addressof(recs)),
-                C.c_uint32(EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | self._gradient_only_flags(gradient_only) |
-                           (self._tail_flag() if self.use_wavefront(n) else 0) | (EPSM_TRACE_FUSE_FIRST_HIT if fuse else 0))]
-        if self.use_wavefront(n) and n > 0:
-            need = int(lib.epsm_trace_workspace_bytes(C.c_int64(n)))
-            ws = self._wf_workspace.get(stream)
-            if ws is None or ws.numel() < need:
-                ws = self._wf_workspace[stream] = torch.empty(need, device=dev, dtype=torch.uint8)
-            rc = lib.epsm_trace_paths_wavefront(*args, C.c_void_p(ws.data_ptr()), C.c_size_t(need), C.c_void_p(stream))
-        else:
-            rc = lib.epsm_trace_paths(*args, C.c_void_p(stream))
-        if rc != 0:
-            _lib.check(rc, "epsm_trace_paths") if self._backend is None else (_ for _ in ()).throw(RuntimeError(f"host tracer rc={rc}"))
+        self._launch_trace(sensor, seed, spp, max_depth, K, lo, n, (rays, None, None, None), film_pos, radiance, valid, recs,
+                           EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | (EPSM_TRACE_FUSE_FIRST_HIT if fuse else 0), gradient_only)
         tr = PathTrace(res=sensor.width, spp=spp, ray_o=rays[:, 0:3], ray_d=rays[:, 3:6], ray_dx=rays[:, 6:9], ray_dy=rays[:, 9:12],
                        path_info=None, scatter_info=None, path_offset=lo, n_paths_total=sensor.wavefront_size(spp))
         tr.film_pos, tr.radiance, tr.valid = film_pos, radiance, valid
@@ -1366,10 +1407,6 @@ class Scene:
                want_radiance: bool = True, sparse_log: bool = False, gradient_only=None):
         from .integrators import PathTrace
         dev = self.device
-        if dev.type != "cuda" and self._backend is None:
-            raise _lib.EpsmError("the tracer runs on the GPU only (no CPU fallback)")
-        lib = self._backend if self._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         sensor = self.sensors[sensor_index]
         n = hi - lo
         # One allocation per element type, carved into the per-vertex arrays with unbind(): ~10 tensor
@@ -1407,26 +1444,8 @@ class Scene:
                          "eta": t["eta"], "hf": t["hf"]})
             sinfo.append({"tri": t["tri"], "aux": t["aux"] if self.alpha_slots else None, "emit": t["emit"], "shadow": shadow,
                           "table": self.tri_table})
-        cs = sensor.c_struct()
-        args = [C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-                C.c_int64(lo), C.c_int64(n), K, C.c_void_p(ray[0].data_ptr()), C.c_void_p(ray[1].data_ptr()),
-                C.c_void_p(ray[2].data_ptr()), C.c_void_p(ray[3].data_ptr()),
-                C.c_void_p(film_pos.data_ptr()), C.c_void_p(radiance.data_ptr()), C.c_void_p(valid.data_ptr()),
-                C.c_void_p(C.addressof(recs)),
-                C.c_uint32((EPSM_TRACE_SPARSE_LOG if sparse_log else 0) | (self._gradient_only_flags(gradient_only) if K >= 1 else 0) |
-                           (self._tail_flag() if self.use_wavefront(n) else 0))]
-        if self.use_wavefront(n) and n > 0:
-            # queues of live paths, three small kernels per bounce (include/epsm_trace.h); the workspace is scratch
-            # and is kept between calls
-            need = int(lib.epsm_trace_workspace_bytes(C.c_int64(n)))
-            ws = self._wf_workspace.get(stream)               # per stream: launches on one stream are ordered, two streams are not
-            if ws is None or ws.numel() < need:
-                ws = self._wf_workspace[stream] = torch.empty(need, device=dev, dtype=torch.uint8)
-            rc = lib.epsm_trace_paths_wavefront(*args, C.c_void_p(ws.data_ptr()), C.c_size_t(need), C.c_void_p(stream))
-        else:
-            rc = lib.epsm_trace_paths(*args, C.c_void_p(stream))
-        if rc != 0:
-            _lib.check(rc, "epsm_trace_paths") if self._backend is None else (_ for _ in ()).throw(RuntimeError(f"host tracer rc={rc}"))
+        self._launch_trace(sensor, seed, spp, max_depth, K, lo, n, ray, film_pos, radiance, valid, recs,
+                           EPSM_TRACE_SPARSE_LOG if sparse_log else 0, gradient_only)
         tr = PathTrace(res=sensor.width, spp=spp, ray_o=ray[0], ray_d=ray[1], ray_dx=ray[2], ray_dy=ray[3],
                        path_info=info, scatter_info=sinfo, path_offset=lo,
                        n_paths_total=sensor.wavefront_size(spp))
@@ -1458,17 +1477,11 @@ class Scene:
                              "set sample_border = False); sample_border is for the sensor prb_reparam renders with")
         max_depth = 6 if max_depth < 0 else min(int(max_depth), 6)       # -1 = no limit; the path loop stops at 6 (epsm.py:549)
         K = min(max_log_depth, max_depth, 5)
-        n_total = s.wavefront_size(spp)
-        tile = self.tile_paths
-        if self.use_wavefront():       # as large as the sharding allows: every rank still gets a tile, none larger than 2^24 paths
-            per_rank = -(-n_total // max(1, world_size))
-            tile = max(self.tile_paths, min(self.WAVEFRONT_TILE_PATHS, per_rank))
-        tiles = _dist.tile_ranges(n_total, tile)
-        for t in _dist.my_tiles(len(tiles), rank, world_size):
+        for lo, hi in self.tile_plan(s.wavefront_size(spp), "trace", rank, world_size):
             if packed_log and K >= 1:
-                yield self._trace_packed(si, seed, spp, max_depth, K, *tiles[t], gradient_only=gradient_only, first_hit=first_hit)
+                yield self._trace_packed(si, seed, spp, max_depth, K, lo, hi, gradient_only=gradient_only, first_hit=first_hit)
             else:
-                yield self._trace(si, seed, spp, max_depth, K, *tiles[t], sparse_log=sparse_log, gradient_only=gradient_only)
+                yield self._trace(si, seed, spp, max_depth, K, lo, hi, sparse_log=sparse_log, gradient_only=gradient_only)
 
     def trace_paths(self, *args, **kw):
         """All of this rank's tiles at once (``list(iter_traces(...))``): for small wavefronts and the tests."""
@@ -1482,25 +1495,12 @@ class Scene:
         si = min(sensor, len(self.sensors) - 1)
         s = self.sensors[si]
         spp = spp or s.spp
-        n_total = s.wavefront_size(spp)
         accum = torch.zeros((s.height, s.width, 4), device=self.device, dtype=torch.float32)
-        lib = self._backend if self._backend is not None else _lib.lib()
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
         if rank is None or world_size is None:
             rank, world_size = _dist.world()
-        tile = self.tile_paths
-        if self.use_wavefront():       # as iter_traces: launches as large as the sharding allows
-            tile = max(tile, min(self.WAVEFRONT_TILE_PATHS, -(-n_total // max(1, world_size))))
-        tiles = _dist.tile_ranges(n_total, tile)
-        for t in _dist.my_tiles(len(tiles), rank, world_size):
-            lo, hi = tiles[t]
+        for lo, hi in self.tile_plan(s.wavefront_size(spp), "trace", rank, world_size):
             tr = self._trace(si, seed, spp, max_depth, 0, lo, hi)
-            rc = lib.epsm_film_splat(C.c_int64(hi - lo), C.c_void_p(tr.film_pos.data_ptr()), C.c_void_p(tr.radiance.data_ptr()),
-                                     s.width, s.height, s.rfilter, C.c_void_p(accum.data_ptr()), C.c_void_p(stream))
-            assert rc == 0, "epsm_film_splat failed"
+            self.film_splat(accum, s, tr.film_pos, tr.radiance)
         if world_size > 1:
             _dist.allreduce_param_grads(accum)
-        img = torch.empty((s.height, s.width, 3), device=self.device, dtype=torch.float32)
-        rc = lib.epsm_film_develop(s.width, s.height, C.c_void_p(accum.data_ptr()), C.c_void_p(img.data_ptr()), C.c_void_p(stream))
-        assert rc == 0, "epsm_film_develop failed"
-        return img
+        return self.film_develop(accum, s)

@@ -16,10 +16,6 @@ from . import _lib
 MESH_BYTES = 32                 # sizeof(EpsmMesh)
 
 
-def _stream(device: torch.device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _check(t: torch.Tensor, name: str, dtype, cols: int):
     if t.device.type != "cuda":
         raise ValueError(f"{name}: the device scene tables need tensors on a GPU")
@@ -48,7 +44,7 @@ class SceneTopology:
         ws_bytes = int(L.epsm_scene_topology_workspace_bytes(self.T))
         ws = _scratch(ws_bytes, tri.device)
         _lib.check(L.epsm_scene_topology(tri.data_ptr(), self.V, self.T, self.buf.data_ptr(), self.buf.numel(), ws.data_ptr(),
-                                         ws.numel(), _stream(tri.device)), "epsm_scene_topology")
+                                         ws.numel(), _lib.stream(tri.device)), "epsm_scene_topology")
 
 
 def vertex_normals(positions: torch.Tensor, topology: SceneTopology, meshes, vertex_begin: Sequence[int], normals: torch.Tensor,
@@ -62,7 +58,7 @@ def vertex_normals(positions: torch.Tensor, topology: SceneTopology, meshes, ver
     vb = (C.c_int64 * (count + 1))(*[int(x) for x in vertex_begin[first:first + count + 1]])
     _lib.check(_lib.lib().epsm_vertex_normals(positions.data_ptr(), positions.shape[0], topology.tri.data_ptr(), topology.T,
                                               topology.buf.data_ptr(), _meshes_at(meshes, first), vb, count, normals.data_ptr(),
-                                              _stream(positions.device)), "epsm_vertex_normals")
+                                              _lib.stream(positions.device)), "epsm_vertex_normals")
 
 
 def emitter_tables(positions: torch.Tensor, tri: torch.Tensor, meshes, mesh_buf: torch.Tensor, emitter_cdf: torch.Tensor,
@@ -82,7 +78,7 @@ def emitter_tables(positions: torch.Tensor, tri: torch.Tensor, meshes, mesh_buf:
     ws = _scratch(L.epsm_emitter_tables_bytes(T, count), positions.device)
     _lib.check(L.epsm_emitter_tables(positions.data_ptr(), positions.shape[0], tri.data_ptr(), T, _meshes_at(meshes, first),
                                      mesh_buf.data_ptr() + first * MESH_BYTES, count, emitter_cdf.data_ptr(), emitter_cdf.numel(),
-                                     ws.data_ptr(), ws.numel(), _stream(positions.device)), "epsm_emitter_tables")
+                                     ws.data_ptr(), ws.numel(), _lib.stream(positions.device)), "epsm_emitter_tables")
 
 
 def environment_tables(bitmap: torch.Tensor):
@@ -100,5 +96,5 @@ def environment_tables(bitmap: torch.Tensor):
     L = _lib.lib()
     ws = _scratch(L.epsm_environment_tables_bytes(W, H), dev)
     _lib.check(L.epsm_environment_tables(bitmap.data_ptr(), W, H, texels.data_ptr(), row_cdf.data_ptr(), col_cdf.data_ptr(),
-                                         cell_pdf.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "epsm_environment_tables")
+                                         cell_pdf.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream(dev)), "epsm_environment_tables")
     return texels, row_cdf, col_cdf, cell_pdf

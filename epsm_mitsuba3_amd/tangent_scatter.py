@@ -50,7 +50,7 @@ def first_vertex_tangent(ray_o, ray_d, ray_dx, ray_dy, grad_in: torch.Tensor, sp
             N, int(path_offset), int(spp), int(res), o.data_ptr(), d.data_ptr(), dx.data_ptr(), dy.data_ptr(),
             g.data_ptr(), int(g.shape[1]), int(g.shape[2]), q0.data_ptr(), q1.data_ptr(), q2.data_ptr(),
             a.data_ptr(), dlduv.data_ptr(), int(dlduv_width), dldp.data_ptr(),
-            go.data_ptr() if go is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+            go.data_ptr() if go is not None else None, _lib.stream(dev))
     _lib.check(rc, "epsm_first_vertex_tangent")
     return dlduv, dldp, go
 
@@ -78,7 +78,7 @@ def scatter(variant: str, rec: PackedRecords, sc: PackedScatter,
             VARIANTS[variant], N, K, C.addressof(rec.records), C.addressof(sc.records), sc.table_ptr(), sc.T,
             out_param.data_ptr(), out_light.data_ptr(), out_diffuse.data_ptr(),
             grad_pos.data_ptr(), grad_nrm.data_ptr(), grad_alpha.data_ptr() if grad_alpha is not None else None,
-            V, B, torch.cuda.current_stream(dev).cuda_stream)
+            V, B, _lib.stream(dev))
     _lib.check(rc, "epsm_scatter")
 
 
@@ -107,7 +107,7 @@ def manifold_grad_scatter(variant: str, rec: PackedRecords, sc: PackedScatter, d
             VARIANTS[variant], N, K, rec.cam.data_ptr(), C.addressof(rec.records), C.addressof(sc.records),
             sc.table_ptr(), sc.T, d.data_ptr(), d.shape[1], int(dlduv_cols), p.data_ptr(), float(clip),
             grad_pos.data_ptr(), grad_nrm.data_ptr(), grad_alpha.data_ptr() if grad_alpha is not None else None,
-            V, B, torch.cuda.current_stream(dev).cuda_stream)
+            V, B, _lib.stream(dev))
     _lib.check(rc, "epsm_manifold_grad_scatter")
 
 
@@ -143,7 +143,7 @@ def backward_pass(variant: str, rec: PackedRecords, sc: PackedScatter, ray_o, ra
             sc.table_ptr(), sc.T, float(clip), grad_pos.data_ptr(), grad_nrm.data_ptr(),
             grad_alpha.data_ptr() if grad_alpha is not None else None,
             grad_origin.data_ptr() if grad_origin is not None else None, V, B,
-            torch.cuda.current_stream(dev).cuda_stream)
+            _lib.stream(dev))
     _lib.check(rc, "epsm_backward_pass")
 
 
@@ -172,5 +172,5 @@ def backward_pass_packed(variant: str, log: PackedLog, grad_in: torch.Tensor, sp
             VARIANTS[variant], log.N, log.K, int(path_offset), int(spp), int(res), C.addressof(log.c), g.data_ptr(),
             int(g.shape[1]), int(g.shape[2]), log.table_ptr(), log.T, float(clip), grad_pos.data_ptr(), grad_nrm.data_ptr(),
             grad_alpha.data_ptr() if grad_alpha is not None else None,
-            grad_origin.data_ptr() if grad_origin is not None else None, V, B, torch.cuda.current_stream(dev).cuda_stream)
+            grad_origin.data_ptr() if grad_origin is not None else None, V, B, _lib.stream(dev))
     _lib.check(rc, "epsm_backward_pass_packed")

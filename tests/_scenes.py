@@ -17,14 +17,10 @@ _lib = None
 def host_tracer():
     global _lib
     if _lib is None:
-        from epsm_mitsuba3_amd._lib import build_lock
+        from epsm_mitsuba3_amd._lib import build_lock, declare_tracer
         with build_lock(_DIR):
             subprocess.run(["make", "-C", _DIR, "-s", _SO], check=True)            # make decides what is stale
-        _lib = C.CDLL(_SO)
-        for n in ("epsm_trace_paths", "epsm_trace_paths_wavefront", "epsm_film_splat", "epsm_film_develop"):
-            getattr(_lib, n).restype = C.c_int
-        _lib.epsm_trace_workspace_bytes.restype = C.c_size_t
-        _lib.epsm_trace_workspace_bytes.argtypes = [C.c_int64]
+        _lib = declare_tracer(C.CDLL(_SO))
     return _lib
 
 
