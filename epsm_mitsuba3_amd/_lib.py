@@ -124,6 +124,9 @@ def _declare(lib):
     lib.epsm_film_adjoint_reparam.restype = C.c_int
     lib.epsm_film_adjoint_reparam.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.epsm_film_splat_tangent.restype = C.c_int
+    lib.epsm_film_splat_tangent.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p]
     declare_tracer(lib)
     declare_bvh(lib)
     declare_scene_tables(lib)
@@ -190,6 +193,14 @@ def declare_tracer(lib):
     lib.epsm_trace_paths_reparam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    if hasattr(lib, "epsm_trace_paths_reparam_forward"):   # (the HIP library; of the host builds, tests/host_harness/trace_fwd_host.cpp)
+        lib.epsm_trace_reparam_forward_workspace_bytes.restype = C.c_size_t
+        lib.epsm_trace_reparam_forward_workspace_bytes.argtypes = [C.c_int64]
+        lib.epsm_trace_paths_reparam_forward.restype = C.c_int
+        lib.epsm_trace_paths_reparam_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                         C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int

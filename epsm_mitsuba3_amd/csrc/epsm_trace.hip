@@ -485,6 +485,78 @@ __global__ __launch_bounds__(256) void epsm_film_adjoint_reparam_kernel(int64_t 
     dL[3 * i] = lr; dL[3 * i + 1] = lg; dL[3 * i + 2] = lb;
     adj[3 * i] = ax; adj[3 * i + 1] = ay; adj[3 * i + 2] = ad;
 }
+// Forward mode of the splat + weight division (common.py:880-920), the transpose of epsm_film_adjoint_reparam_kernel: one lane per
+// sample, its 5 x 5 window (the box filter: the pixel under it).  Per pixel p, with w_ip = f(p - pos_i) and its gradient,
+//   dA_p += (grad w . dpos_i + w ddet_i) L_i + w dL_i,    dW_p += grad w . dpos_i + w ddet_i
+// into d_accum (H,W,4); the image's tangent is (dA - image dW) / W with the primal film.  d_film may be NULL (colour tangents:
+// the samples do not move).  Lanes whose samples share a pixel sum over the group before the atomics, as epsm_film_splat_kernel
+// does (one atomic per lane and pixel: 10.9 ms at 4.26 M samples, against 0.73 ms for the primal splat).
+struct TangentWindow { float wx[5], wy[5], dwx[5], dwy[5]; int X, Y; };
+template <int G> __device__ __forceinline__ float group_total_or_own(float v) {
+    if constexpr (G == 1) return v;
+    else return group_total<G>(v);
+}
+template <int G>
+__device__ __forceinline__ void splat_tangent_groups(const TangentWindow &w, const float *L, const float *T, const float *F, int W, int H,
+                                                     float *d_accum) {
+    const bool carrier = (threadIdx.x & (G - 1)) == G - 1;
+#pragma unroll
+    for (int jy = 0; jy < 5; ++jy) {
+        const int y = w.Y + jy - 2;
+#pragma unroll
+        for (int jx = 0; jx < 5; ++jx) {
+            const int x = w.X + jx - 2;
+            const float w2 = w.wy[jy] * w.wx[jx];
+            const float dw = w.wy[jy] * w.dwx[jx] * F[0] + w.dwy[jy] * w.wx[jx] * F[1] + w2 * F[2];      // d (w det)
+            const float sr = group_total_or_own<G>(dw * L[0] + w2 * T[0]), sg = group_total_or_own<G>(dw * L[1] + w2 * T[1]),
+                        sb = group_total_or_own<G>(dw * L[2] + w2 * T[2]), sw = group_total_or_own<G>(dw);
+            if (carrier && x >= 0 && y >= 0 && x < W && y < H && (sr != 0.f || sg != 0.f || sb != 0.f || sw != 0.f)) {
+                float *a = d_accum + 4 * ((int64_t) y * W + x);
+                atomicAdd(a + 0, sr); atomicAdd(a + 1, sg); atomicAdd(a + 2, sb);
+                if (sw != 0.f) atomicAdd(a + 3, sw);
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void epsm_film_splat_tangent_kernel(int64_t N, const float *pos, const float *rad, const float *d_rad,
+                                                                      const float *d_film, int W, int H, int rfilter, float *d_accum) {
+    const int64_t i0 = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    const bool live = i0 < N;
+    const int64_t i = live ? i0 : N - 1;                // lanes past the end take part in the sums with weight 0
+    const float px = pos[2 * i], py = pos[2 * i + 1];
+    const float T[3] = {d_rad[3 * i], d_rad[3 * i + 1], d_rad[3 * i + 2]};
+    if (rfilter == EPSM_RFILTER_BOX) {                                    // (a box weight does not move with the sample)
+        const int x = (int) floorf(px), y = (int) floorf(py);
+        if (!live || x < 0 || y < 0 || x >= W || y >= H) return;
+        float *a = d_accum + 4 * ((int64_t) y * W + x);
+        atomicAdd(a + 0, T[0]); atomicAdd(a + 1, T[1]); atomicAdd(a + 2, T[2]);
+        return;
+    }
+    const float L[3] = {rad[3 * i], rad[3 * i + 1], rad[3 * i + 2]};
+    const float F[3] = {d_film ? d_film[3 * i] : 0.f, d_film ? d_film[3 * i + 1] : 0.f, d_film ? d_film[3 * i + 2] : 0.f};
+    const float radius = 2.f, alpha = -1.f / (2.f * 0.5f * 0.5f), bias = expf(alpha * radius * radius);
+    TangentWindow w;
+    w.X = (int) floorf(px); w.Y = (int) floorf(py);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int x = w.X + j - 2, y = w.Y + j - 2;
+        const float dx = (x + 0.5f) - px, dy = (y + 0.5f) - py;
+        const float ex = expf(alpha * dx * dx), ey = expf(alpha * dy * dy);
+        const bool lx = live && fabsf(dx) <= radius && x >= 0 && x < W && ex - bias > 0.f;
+        const bool ly = live && fabsf(dy) <= radius && y >= 0 && y < H && ey - bias > 0.f;
+        w.wx[j] = lx ? ex - bias : 0.f; w.dwx[j] = lx ? -2.f * alpha * dx * ex : 0.f;
+        w.wy[j] = ly ? ey - bias : 0.f; w.dwy[j] = ly ? -2.f * alpha * dy * ey : 0.f;
+    }
+    // largest aligned group size whose lanes all sit in one pixel, the same for the whole wave (epsm_film_splat_kernel)
+    const int lane = threadIdx.x & 63;
+    const int X8 = __shfl(w.X, lane & ~7), Y8 = __shfl(w.Y, lane & ~7);
+    const int X16 = __shfl(w.X, lane & ~15), Y16 = __shfl(w.Y, lane & ~15);
+    const int X64 = __builtin_amdgcn_readfirstlane(w.X), Y64 = __builtin_amdgcn_readfirstlane(w.Y);
+    if (__ballot(w.X != X64 || w.Y != Y64) == 0ull) { splat_tangent_groups<64>(w, L, T, F, W, H, d_accum); return; }
+    if (__ballot(w.X != X16 || w.Y != Y16) == 0ull) { splat_tangent_groups<16>(w, L, T, F, W, H, d_accum); return; }
+    if (__ballot(w.X != X8 || w.Y != Y8) == 0ull) { splat_tangent_groups<8>(w, L, T, F, W, H, d_accum); return; }
+    splat_tangent_groups<1>(w, L, T, F, W, H, d_accum);
+}
 __global__ __launch_bounds__(256) void epsm_film_develop_kernel(int64_t n, const float *accum, float *image) {
     const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -695,5 +767,19 @@ extern "C" int epsm_film_develop(int width, int height, const float *accum, floa
                        n, accum, image);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_develop", e);
+    return EPSM_OK;
+}
+extern "C" int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radiance, const float *d_radiance,
+                                       const float *d_film, int width, int height, int rfilter, float *d_accum, void *stream) {
+    epsm_host::err_buf()[0] = 0;
+    if (N == 0) return EPSM_OK;
+    if (N < 0 || !film_pos || !radiance || !d_radiance || !d_accum || width < 1 || height < 1)
+        return fail(EPSM_EINVAL, "epsm_film_splat_tangent: bad argument");
+    if (rfilter == EPSM_RFILTER_BOX && d_film)
+        return fail(EPSM_EINVAL, "epsm_film_splat_tangent: a box filter has no derivative in the film position (d_film must be NULL)");
+    hipLaunchKernelGGL(epsm_film_splat_tangent_kernel, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
+                       N, film_pos, radiance, d_radiance, d_film, width, height, rfilter, d_accum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_splat_tangent", e);
     return EPSM_OK;
 }

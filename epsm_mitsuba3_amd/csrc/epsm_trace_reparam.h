@@ -33,34 +33,36 @@ constexpr int kMaxAux = 64;              // reparam_rays <= 64 (the reference's 
 constexpr int kD = 6;                    // partials carried per dual evaluation
 
 // ---------------------------------------------------------------------------
-// dual numbers: value + kD partial derivatives
+// dual numbers: value + K partial derivatives (the backward pass carries kD basis partials per evaluation, the forward pass
+// one directional derivative: DualN<1>)
 // ---------------------------------------------------------------------------
-struct Dual {
+template <int K> struct DualN {
     float v;
-    float d[kD];
-    EPSM_HD Dual() {}
-    EPSM_HD Dual(float x) : v(x) {
+    float d[K];
+    EPSM_HD DualN() {}
+    EPSM_HD DualN(float x) : v(x) {
 #pragma unroll
-        for (int i = 0; i < kD; ++i) d[i] = 0.f;
+        for (int i = 0; i < K; ++i) d[i] = 0.f;
     }
 };
-EPSM_HD Dual operator+(Dual a, Dual b) { Dual r; r.v = a.v + b.v; for (int i = 0; i < kD; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
-EPSM_HD Dual operator-(Dual a, Dual b) { Dual r; r.v = a.v - b.v; for (int i = 0; i < kD; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
-EPSM_HD Dual operator-(Dual a) { Dual r; r.v = -a.v; for (int i = 0; i < kD; ++i) r.d[i] = -a.d[i]; return r; }
-EPSM_HD Dual operator*(Dual a, Dual b) { Dual r; r.v = a.v * b.v; for (int i = 0; i < kD; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
-EPSM_HD Dual operator/(Dual a, Dual b) {
-    Dual r; const float ib = 1.f / b.v; r.v = a.v * ib;
-    for (int i = 0; i < kD; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * ib;
+using Dual = DualN<kD>;
+template <int K> EPSM_HD DualN<K> operator+(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v + b.v; for (int i = 0; i < K; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
+template <int K> EPSM_HD DualN<K> operator-(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v - b.v; for (int i = 0; i < K; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
+template <int K> EPSM_HD DualN<K> operator-(DualN<K> a) { DualN<K> r; r.v = -a.v; for (int i = 0; i < K; ++i) r.d[i] = -a.d[i]; return r; }
+template <int K> EPSM_HD DualN<K> operator*(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v * b.v; for (int i = 0; i < K; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
+template <int K> EPSM_HD DualN<K> operator/(DualN<K> a, DualN<K> b) {
+    DualN<K> r; const float ib = 1.f / b.v; r.v = a.v * ib;
+    for (int i = 0; i < K; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * ib;
     return r;
 }
-EPSM_HD Dual t_sqrt(Dual a) { Dual r; r.v = sqrtf(a.v); const float k = r.v > 0.f ? 0.5f / r.v : 0.f; for (int i = 0; i < kD; ++i) r.d[i] = a.d[i] * k; return r; }
-EPSM_HD Dual t_exp(Dual a) { Dual r; r.v = expf(a.v); for (int i = 0; i < kD; ++i) r.d[i] = a.d[i] * r.v; return r; }
+template <int K> EPSM_HD DualN<K> t_sqrt(DualN<K> a) { DualN<K> r; r.v = sqrtf(a.v); const float k = r.v > 0.f ? 0.5f / r.v : 0.f; for (int i = 0; i < K; ++i) r.d[i] = a.d[i] * k; return r; }
+template <int K> EPSM_HD DualN<K> t_exp(DualN<K> a) { DualN<K> r; r.v = expf(a.v); for (int i = 0; i < K; ++i) r.d[i] = a.d[i] * r.v; return r; }
 EPSM_HD float t_sqrt(float a) { return sqrtf(a); }
 EPSM_HD float t_exp(float a) { return expf(a); }
 EPSM_HD float val(float a) { return a; }
-EPSM_HD float val(Dual a) { return a.v; }
+template <int K> EPSM_HD float val(DualN<K> a) { return a.v; }
 // dr.replace_grad(primal, x): x's derivative on the stored primal value
-EPSM_HD Dual replace_value(Dual a, float primal) { a.v = primal; return a; }
+template <int K> EPSM_HD DualN<K> replace_value(DualN<K> a, float primal) { a.v = primal; return a; }
 EPSM_HD float replace_value(float, float primal) { return primal; }
 
 template <class T> EPSM_HD V3<T> lift3(F3 a) { return mk3<T>(T(a.x), T(a.y), T(a.z)); }
@@ -358,6 +360,50 @@ EPSM_HD void warp_backward(const EpsmScene &S, const GradOut &G, const Warp &W, 
     g_o = f3((float) go[0], (float) go[1], (float) go[2]);
 }
 
+// The forward pass reads tangents where the backward adds gradients: (V,3) vertex-position / vertex-normal tangents of the
+// meshes flagged EPSM_MESH_POS_ATTACHED / EPSM_MESH_NRM_ATTACHED (the rows of other meshes are not read); nrm may be null.
+struct TanIn { const float *pos, *nrm; };
+EPSM_HD F3 tan_vertex(const float *buf, uint32_t row) { return ld3(buf + 3 * (int64_t) row); }
+// The motion of a point glued to triangle `tri` at barycentrics b1, b2: the gather that add_follow_point scatters
+EPSM_HD F3 follow_tangent(const EpsmScene &S, const TanIn &T, uint32_t tri, float b1, float b2) {
+    const EpsmMesh m = S.meshes[S.tri_mesh[tri]];
+    if (!(m.flags & EPSM_MESH_POS_ATTACHED)) return zero3<float>();
+    const uint32_t *iv = S.tri + 3 * (int64_t) tri;
+    return tan_vertex(T.pos, iv[0]) * (1.f - b1 - b2) + tan_vertex(T.pos, iv[1]) * b1 + tan_vertex(T.pos, iv[2]) * b2;
+}
+// The tangent of V_direct of one auxiliary ray: the motion of its hit (glued to the triangle, b detached) minus that of the
+// ray's origin `t_o`, projected by normalize(si.p - ray.o); a miss follows ray.d, which moves only for an emitter ray
+// (em_inv_dist != 0: ray.d = normalize(ds.p - o)).  Transpose of the per-ray step of warp_backward.
+EPSM_HD F3 aux_tangent(const EpsmScene &S, const TanIn &T, const Aux &A, F3 d, F3 t_o, float em_inv_dist) {
+    if (A.tri == kNoIndex) return em_inv_dist != 0.f ? (t_o - d * dot(d, t_o)) * (-em_inv_dist) : zero3<float>();
+    const F3 dp = follow_tangent(S, T, A.tri, A.b1, A.b2) - t_o;
+    return (dp - A.v * dot(A.v, dp)) * A.inv_dist;
+}
+// Forward mode of one reparameterize_ray call (reparam.py:155-221) -- the transpose of warp_backward: from the tangent of
+// every auxiliary ray's V_direct, the tangent of the reparameterised direction and of the divergence,
+//   d' = iZ P(sum_i w_i v_i'),   div' = iZ sum_i (dw_i - w_i dZ / Z) . v_i'     (P = 1 - d d^T)
+// with the terms that cancel over the rays (dw_i against w_i dZ / Z, each ~sqrt(kappa) times their sum) combined per ray and
+// summed in double, as warp_backward sums its per-triangle shares.
+struct WarpTan { F3 dir; float div; };
+EPSM_HD WarpTan warp_forward(const EpsmScene &S, const TanIn &T, const Warp &W, F3 t_o, float em_inv_dist) {
+    WarpTan r; r.dir = zero3<float>(); r.div = 0.f;
+    if (W.n <= 0) return r;
+    const float Z = fmaxf(W.Z, 1e-8f), iZ = 1.f / Z;
+    const F3 dZn = W.dZ * iZ;
+    double V[3] = {0.0, 0.0, 0.0}, div = 0.0;
+    for (int it = 0; it < W.n; ++it) {
+        const Aux &A = W.a[it];
+        const F3 tv = aux_tangent(S, T, A, W.d, t_o, em_inv_dist);
+        const F3 c = A.dw - dZn * A.w;
+        V[0] += (double) A.w * tv.x; V[1] += (double) A.w * tv.y; V[2] += (double) A.w * tv.z;
+        div += (double) dot(c, tv);
+    }
+    const F3 Vf = f3((float) V[0], (float) V[1], (float) V[2]);
+    r.dir = (Vf - W.d * dot(W.d, Vf)) * iZ;
+    r.div = (float) div * iZ;
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // what the differential step of a vertex needs to know about a vertex (captured from path_bounce, detached)
 // ---------------------------------------------------------------------------
@@ -394,8 +440,8 @@ struct Capture {
     }
 };
 
-// Per-slot seeds of one dual evaluation: which input carries partial k (all others are constants)
-struct Seeds { int d, dem, P[3], Nn[3]; };                                 // first partial index of each 3-vector, -1 = constant
+// The inputs of one dual evaluation of eval_lo, by index: d', d_em', P0, P1, P2, N0, N1, N2
+enum { kInD = 0, kInDem = 1, kInP = 2, kInN = 5, kInputs = 8 };
 template <class T> EPSM_HD V3<T> seed3(F3 a, int first) {
     V3<T> r = lift3<T>(a);
     if constexpr (!std::is_same<T, float>::value) {
@@ -403,6 +449,26 @@ template <class T> EPSM_HD V3<T> seed3(F3 a, int first) {
     }
     return r;
 }
+// Per-slot seeds of one dual evaluation of the backward pass: which input carries partials k .. k + 2 (all others are constants)
+struct Seeds {
+    int d, dem, P[3], Nn[3];                                               // first partial index of each 3-vector, -1 = constant
+    EPSM_HD int slot(int w) const { return w == kInD ? d : w == kInDem ? dem : w < kInN ? P[w - kInP] : Nn[w - kInN]; }
+    EPSM_HD bool live(int w) const { return slot(w) >= 0; }
+    template <class T> EPSM_HD V3<T> in(F3 a, int w) const { return seed3<T>(a, slot(w)); }
+};
+// The forward pass's seeds: every live input carries its TANGENT in the one partial of a DualN<1>
+struct TanSeeds {
+    bool on[kInputs];
+    F3 t[kInputs];
+    EPSM_HD bool live(int w) const { return on[w]; }
+    template <class T> EPSM_HD V3<T> in(F3 a, int w) const {
+        V3<T> r = lift3<T>(a);
+        if constexpr (!std::is_same<T, float>::value) {
+            if (on[w]) { r.x.d[0] = t[w].x; r.y.d[0] = t[w].y; r.z.d[0] = t[w].z; }
+        }
+        return r;
+    }
+};
 template <class T> EPSM_HD T dot3c(F3 a, V3<T> b) { return b.x * T(a.x) + b.y * T(a.y) + b.z * T(a.z); }
 template <class T> EPSM_HD V3<T> ratio3(F3 num, V3<T> f, F3 den, float floor_) {
     // num * f / max(floor, den) per channel (prb_reparam.py:541-542); zero where the detached value is zero
@@ -412,15 +478,15 @@ template <class T> EPSM_HD V3<T> ratio3(F3 num, V3<T> f, F3 den, float floor_) {
 
 // delta_L . [ (Le + Lr_dir + Lr_ind) + extra ] of vertex `cur` as a function of the seeded inputs (prb_reparam.py:362-572;
 // the two determinants multiply terms whose values are known: handled by the caller).
-template <class T>
-EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, const Vertex *next, F3 dL, const Seeds &sd) {
+template <class T, class SD>
+EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, const Vertex *next, F3 dL, const SD &sd) {
     const SurfHit &c = cur.si;
     const V3<T> o = lift3<T>(cur.ray.o);
-    const V3<T> d = seed3<T>(cur.ray.d, sd.d);
-    const V3<T> P0 = seed3<T>(c.p0, sd.P[0]), P1 = seed3<T>(c.p1, sd.P[1]), P2 = seed3<T>(c.p2, sd.P[2]);
+    const V3<T> d = sd.template in<T>(cur.ray.d, kInD);
+    const V3<T> P0 = sd.template in<T>(c.p0, kInP), P1 = sd.template in<T>(c.p1, kInP + 1), P2 = sd.template in<T>(c.p2, kInP + 2);
     // the stored normals are post-flip (surface_interaction); surf_t flips after interpolating, as mesh.cpp does
     const float fl = (c.mesh_flags & EPSM_MESH_FLIP_NORMALS) ? -1.f : 1.f;
-    const V3<T> N0 = seed3<T>(c.n0 * fl, sd.Nn[0]), N1 = seed3<T>(c.n1 * fl, sd.Nn[1]), N2 = seed3<T>(c.n2 * fl, sd.Nn[2]);
+    const V3<T> N0 = sd.template in<T>(c.n0 * fl, kInN), N1 = sd.template in<T>(c.n1 * fl, kInN + 1), N2 = sd.template in<T>(c.n2 * fl, kInN + 2);
     const SurfT<T> h = surf_t<T>(o, d, P0, P1, P2, N0, N1, N2, c.mesh_flags, cur.th.u, cur.th.v, cur.th.t);
     T s = T(0.f);
     // ---- a `bitmap` reflectance follows the point the ray sees: rho(uv') / rho(uv) per channel multiplies both BSDF values below
@@ -441,18 +507,18 @@ EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, con
     }
     // ---- Lr_dir = beta * mis * bsdf(wi, to_local(d_em')) * em_weight (prb_reparam.py:413-418)
     if (cur.active_em && (cur.Lr_dir.x != 0.f || cur.Lr_dir.y != 0.f || cur.Lr_dir.z != 0.f)) {
-        const V3<T> wo = to_local_t(h, seed3<T>(cur.es.d, sd.dem));
+        const V3<T> wo = to_local_t(h, sd.template in<T>(cur.es.d, kInDem));
         const V3<T> f0_ = bsdf_eval_t<T>(cur.bsdf, h.wi, wo);
         const V3<T> f = mk3<T>(f0_.x * tex.x, f0_.y * tex.y, f0_.z * tex.z);
         const F3 k = mul3(mul3(cur.beta, cur.es.weight), dL) * cur.mis_em;
         T em = T(1.f);
         const bool env_sample = cur.es.emitter >= 0 && !cur.es.delta && cur.es.tri == kNoIndex && has_environment(S) && cur.es.emitter == S.env.emitter;
-        if (env_sample && sd.dem >= 0) {
+        if (env_sample && sd.live(kInDem)) {
             // envmap.cpp:438-443 eval_direction at the reparameterised direction: L(d_em') / L(d_em) per channel, folded into
             // one factor weighted by what each channel contributes (k . f): d/d d_em of sum_c k_c f_c L_c(d') / L_c
             F3 g[3];
             const F3 L0 = env_eval_grad(S, cur.es.d, g);
-            const V3<T> dd = seed3<T>(cur.es.d, sd.dem);
+            const V3<T> dd = sd.template in<T>(cur.es.d, kInDem);
             const float Lc[3] = {L0.x, L0.y, L0.z};
             const float kc[3] = {k.x, k.y, k.z};
             const T fc[3] = {f.x, f.y, f.z};
@@ -486,7 +552,7 @@ EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, con
     // ---- extra: the neighbours' BSDFs as the point moves along the reparameterised ray over the DETACHED triangle
     //      (prb_reparam.py:515-542; the emission at the next vertex has no directional derivative for area lights)
     const bool want_prev = prev && prev->valid, want_next = next && next->valid;
-    if (sd.d >= 0 && (want_prev || want_next)) {
+    if (sd.live(kInD) && (want_prev || want_next)) {
         const V3<T> e1 = lift3<T>(c.p1 - c.p0), e2 = lift3<T>(c.p2 - c.p0);
         const V3<T> pvec = cross(d, e2);
         const V3<T> qvec = lift3<T>(cross(cur.ray.o - c.p0, c.p1 - c.p0));
@@ -541,6 +607,22 @@ EPSM_HD F3 film_to_direction(const EpsmSensor &C, const PrimaryRay &pr, float gx
     return c0 * gq.x + c1 * gq.y + c2 * gq.z;
 }
 
+// Transpose of film_to_direction: the tangent of the reparameterised primary direction -> that of the film position (pixels)
+EPSM_HD void direction_to_film(const EpsmSensor &C, const PrimaryRay &pr, F3 td, float &fx, float &fy) {
+    const float *W = C.to_world;
+    const F3 c0 = f3(W[0], W[4], W[8]), c1 = f3(W[1], W[5], W[9]), c2 = f3(W[2], W[6], W[10]);
+    const F3 origin = f3(W[3], W[7], W[11]);
+    const F3 r = (pr.ray.o - origin) + pr.ray.d;
+    const F3 q = f3(dot(c0, r), dot(c1, r), dot(c2, r));
+    const F3 base = xform_point(C.sample_to_camera, f3(0.f, 0.f, 0.f));
+    const float s = base.z / q.z;
+    const float a = C.dx[0], b = C.dy[0], c = C.dx[1], d = C.dy[1], idet = 1.f / (a * d - b * c);
+    const F3 tq = f3(dot(c0, td), dot(c1, td), dot(c2, td));
+    const float th = tq.z * s / q.z;
+    const float hx = s * tq.x - q.x * th, hy = s * tq.y - q.y * th;
+    fx = (d * hx - b * hy) * idet; fy = (-c * hx + a * hy) * idet;
+}
+
 // What happens to a warp once its ray and the adjoints of its direction / divergence are known.
 //   o, d            the ray; g_dir, g_div: d loss / d direction, d loss / d divergence of its reparameterisation
 //   ftri, fb1, fb2  the triangle + barycentrics its ORIGIN is glued to (kNoIndex: the camera)
@@ -591,7 +673,7 @@ EPSM_HD void differential(const ReparamArgs &R, Sink &sink, const Vertex *prev, 
         else if (chunk == 1) { if (!want_pos) continue; sd.P[0] = 0; sd.P[1] = 3; }
         else if (chunk == 2) { if (!want_pos && !want_nrm) continue; sd.P[2] = 0; sd.Nn[0] = 3; }
         else { if (!want_nrm) continue; sd.Nn[1] = 0; sd.Nn[2] = 3; }
-        const Dual s = eval_lo<Dual>(S, prev, cur, next, dL, sd);
+        const Dual s = eval_lo<Dual, Seeds>(S, prev, cur, next, dL, sd);
         for (int k = 0; k < kD; ++k) g[6 * chunk + k] = s.d[k];
     }
     if (want_pos) {
@@ -683,6 +765,178 @@ EPSM_HD void reparam_one_path(const ReparamArgs &R, int64_t i, const BvhStack &s
         }
         sink.warp(pr.ray.o, pr.ray.d, g_film + g_env, g_det_film, kNoIndex, 0.f, 0.f, 0.f);
     }
+}
+
+// ---------------------------------------------------------------------------
+// the forward pass (epsm_trace_paths_reparam_forward): the transpose of reparam_one_path, statement by statement.  A warp is
+// needed BEFORE the vertex it serves (its d' tangent feeds the dual evaluation), so a sink returns the warp's tangents:
+//   InlineFwdSink  traced and evaluated on the spot (the host build)
+//   RecordSink     stage 1 of the device: the request is written (ray, glued origin, em_inv_dist), nothing is evaluated
+//   ReadSink       stage 3 of the device: the tangents stage 2 left in the request (gdir, gdiv) are read back
+// Requests are numbered as QueueSink numbers them, so every warp draws the auxiliary rays the backward pass draws.
+// ---------------------------------------------------------------------------
+struct ReparamFwdArgs {
+    TraceArgs A;
+    ReparamCfg cfg;
+    const float *radiance;       // (N,3) L of the primal pass under the same seed
+    TanIn T;                     // (V,3) tangents of the vertex positions / normals
+    float *d_radiance;           // (N,3) out: dL
+    float *d_film;               // (N,3) out: d film position (x, y) and d det of the primary ray
+};
+struct InlineFwdSink {
+    static constexpr bool kEval = true;
+    const EpsmScene &S; const ReparamCfg &cfg; const TanIn &T; const BvhStack &st; Warp &W; WarpId id;
+    EPSM_HD WarpTan warp(F3 o, F3 d, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
+        warp_collect(S, cfg, id, o, d, st, W);
+        id.n += 1;
+        const F3 t_o = ftri != kNoIndex ? follow_tangent(S, T, ftri, fb1, fb2) : zero3<float>();
+        return warp_forward(S, T, W, t_o, em_inv_dist);
+    }
+};
+struct RecordSink {
+    static constexpr bool kEval = false;
+    WarpReq *req; int64_t N, i; int n;
+    EPSM_HD WarpTan warp(F3 o, F3 d, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
+        WarpTan r; r.dir = zero3<float>(); r.div = 0.f;
+        if (n >= kMaxReq) return r;
+        WarpReq q;
+        q.o[0] = o.x; q.o[1] = o.y; q.o[2] = o.z; q.gdiv = 0.f; q.d[0] = d.x; q.d[1] = d.y; q.d[2] = d.z; q.em_inv_dist = em_inv_dist;
+        q.gdir[0] = q.gdir[1] = q.gdir[2] = 0.f; q.fb1 = fb1; q.ftri = ftri; q.fb2 = fb2; q.pad0 = q.pad1 = 0.f;
+        req[(int64_t) n * N + i] = q;
+        n += 1;
+        return r;
+    }
+};
+struct ReadSink {
+    static constexpr bool kEval = true;
+    const WarpReq *req; int64_t N, i; int n;
+    EPSM_HD WarpTan warp(F3, F3, uint32_t, float, float, float) {
+        WarpTan r; r.dir = zero3<float>(); r.div = 0.f;
+        if (n >= kMaxReq) return r;
+        const WarpReq &q = req[(int64_t) n * N + i];
+        r.dir = f3(q.gdir[0], q.gdir[1], q.gdir[2]); r.div = q.gdiv;
+        n += 1;
+        return r;
+    }
+};
+
+// Forward form of `differential`: the vertex's warps first (the ray into it, its emitter ray; for the first vertex the camera
+// ray, in the order the backward pass asks for them), then one DualN<1> evaluation of eval_lo per colour channel with every
+// input seeded by its tangent.  Adds d(Le + Lr_dir + Lr_ind + extra) and the divergence terms to dLo; the camera ray's warp
+// goes back to the caller (`cam`).
+template <class Sink>
+EPSM_HD void differential_forward(const ReparamFwdArgs &R, Sink &sink, const Vertex *prev, const Vertex &cur, const Vertex *next,
+                                  const PrimaryRay &pr, F3 &dLo, WarpTan *cam) {
+    const EpsmScene &S = R.A.S;
+    const SurfHit &c = cur.si;
+    const bool first = prev == nullptr;
+    const bool has_normals = (c.mesh_flags & EPSM_MESH_VERTEX_NORMALS) != 0;
+    const EpsmMesh m = S.meshes[c.mesh];
+    TanSeeds sd;
+    for (int k = 0; k < kInputs; ++k) { sd.on[k] = false; sd.t[k] = zero3<float>(); }
+    WarpTan tin; tin.dir = zero3<float>(); tin.div = 0.f;
+    WarpTan tem = tin;
+    if (!first && cur.depth < R.cfg.max_depth) {
+        tin = sink.warp(cur.ray.o, cur.ray.d, prev->th.tri, prev->th.u, prev->th.v, 0.f);
+        sd.on[kInD] = true;
+    }
+    const bool em = cur.active_em && cur.depth + 1 < R.cfg.max_depth && (cur.Lr_dir.x != 0.f || cur.Lr_dir.y != 0.f || cur.Lr_dir.z != 0.f);
+    if (em) {
+        float dist;
+        const Ray er = spawn_ray_to(c, cur.es.p, dist);
+        tem = sink.warp(er.o, er.d, cur.th.tri, cur.th.u, cur.th.v, 1.f / dist);
+        sd.on[kInDem] = true;
+    }
+    if (first && R.cfg.max_depth > 0) {
+        tin = sink.warp(pr.ray.o, pr.ray.d, kNoIndex, 0.f, 0.f, 0.f);
+        sd.on[kInD] = true;
+        *cam = tin;
+    }
+    if (!Sink::kEval) return;
+    sd.t[kInD] = tin.dir; sd.t[kInDem] = tem.dir;
+    if ((m.flags & EPSM_MESH_POS_ATTACHED) && R.T.pos)
+        for (int j = 0; j < 3; ++j) { sd.on[kInP + j] = true; sd.t[kInP + j] = tan_vertex(R.T.pos, c.vi[j]); }
+    if (has_normals && (m.flags & EPSM_MESH_NRM_ATTACHED) && R.T.nrm)
+        for (int j = 0; j < 3; ++j) { sd.on[kInN + j] = true; sd.t[kInN + j] = tan_vertex(R.T.nrm, c.vi[j]); }
+    bool any = false;
+    for (int k = 0; k < kInputs; ++k) any = any || sd.on[k];
+    if (any) {
+        // eval_lo is linear in its weight dL: the unit weights give the three channels
+        const float e[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
+        float out[3];
+        for (int ch = 0; ch < 3; ++ch) out[ch] = eval_lo<DualN<1>, TanSeeds>(S, prev, cur, next, f3(e[ch][0], e[ch][1], e[ch][2]), sd).d[0];
+        dLo = dLo + f3(out[0], out[1], out[2]);
+    }
+    // the divergences: that of the ray into the vertex multiplies (Le + Lr_dir + Lr_ind), whose value is L_in; the emitter
+    // ray's multiplies Lr_dir.  (The camera ray's is the film's determinant: the caller's.)
+    if (!first) dLo = dLo + cur.L_in * tin.div;
+    if (em) dLo = dLo + cur.Lr_dir * tem.div;
+}
+
+// One path of the forward pass: d L and d (film x, film y, det) of path i for the tangents R.T.
+template <class Sink>
+EPSM_HD void reparam_forward_one_path(const ReparamFwdArgs &R, int64_t i, const BvhStack &st, Sink &sink) {
+    const TraceArgs &A = R.A;
+    const int64_t widx = A.path_offset + i;
+    PathState s = path_begin(A, i, false);
+    PrimaryRay pr;
+    { Pcg32 r2 = seed_sampler(A.seed, (uint32_t) widx); pr = sample_primary_ray(A.C, widx, A.spp, r2); }
+    F3 dLo = zero3<float>();
+    WarpTan cam; cam.dir = zero3<float>(); cam.div = 0.f;
+    InlineVis vis{st};
+    Vertex v[3];
+    for (int k = 0; k < 3; ++k) vertex_clear(v[k]);
+    F3 L_run = ld3(R.radiance + 3 * i);
+    const int max_depth = path_max_depth(A);
+    bool primary_done = false;
+    for (int j = 0; j <= max_depth; ++j) {
+        Vertex &nx = v[j % 3];
+        vertex_clear(nx);
+        if (j < max_depth) {
+            TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
+            const bool was_active = s.active;
+            if (s.active) th = intersect<false>(A.S, s.ray, st);
+            nx.ray = s.ray; nx.th = th; nx.beta = s.beta; nx.depth = s.depth;
+            Capture cap{&nx};
+            path_bounce(A, i, j, s, th, vis, cap);
+            nx.valid = nx.valid && was_active;
+            nx.escaped = was_active && !th.hit;
+            nx.L_in = L_run;
+            L_run = L_run - nx.Le - nx.Lr_dir;
+            nx.L_after = L_run;
+        }
+        if (j == 0) continue;
+        const Vertex &cur = v[(j - 1) % 3];
+        const Vertex *prev = j >= 2 ? &v[(j - 2) % 3] : nullptr;
+        if (!cur.valid) {
+            // an escaped ray towards an environment emitter: its warp's direction moves the lookup, its divergence multiplies L_in
+            if (cur.escaped && prev && has_environment(A.S) && cur.depth < R.cfg.max_depth && (cur.Le.x != 0.f || cur.Le.y != 0.f || cur.Le.z != 0.f)) {
+                const WarpTan t = sink.warp(cur.ray.o, cur.ray.d, prev->th.tri, prev->th.u, prev->th.v, 0.f);
+                if (Sink::kEval) {
+                    F3 g[3];
+                    const F3 L0 = env_eval_grad(A.S, cur.ray.d, g);
+                    dLo = dLo + f3(L0.x > 0.f ? dot(g[0], t.dir) * cur.Le.x / L0.x : 0.f, L0.y > 0.f ? dot(g[1], t.dir) * cur.Le.y / L0.y : 0.f,
+                                   L0.z > 0.f ? dot(g[2], t.dir) * cur.Le.z / L0.z : 0.f) + cur.L_in * t.div;
+                }
+            }
+            continue;
+        }
+        differential_forward(R, sink, prev, cur, &nx, pr, dLo, &cam);
+        if (j == 1 && R.cfg.max_depth > 0) primary_done = true;
+    }
+    if (!primary_done && R.cfg.max_depth > 0) {                            // the camera ray hit nothing: the film's term, and the
+        cam = sink.warp(pr.ray.o, pr.ray.d, kNoIndex, 0.f, 0.f, 0.f);      // environment's radiance along the reparameterised ray
+        if (Sink::kEval && has_environment(A.S)) {
+            F3 g[3];
+            env_eval_grad(A.S, pr.ray.d, g);
+            dLo = dLo + f3(dot(g[0], cam.dir), dot(g[1], cam.dir), dot(g[2], cam.dir));
+        }
+    }
+    if (!Sink::kEval) return;
+    float fx, fy;
+    direction_to_film(A.C, pr, cam.dir, fx, fy);
+    R.d_radiance[3 * i] = dLo.x; R.d_radiance[3 * i + 1] = dLo.y; R.d_radiance[3 * i + 2] = dLo.z;
+    R.d_film[3 * i] = fx; R.d_film[3 * i + 1] = fy; R.d_film[3 * i + 2] = cam.div;
 }
 
 }  // namespace rp

@@ -1,5 +1,5 @@
-// epsm_trace_reparam.hip -- kernel + C ABI of the reparameterised backward pass (include/epsm_trace.h,
-// epsm_trace_paths_reparam; per-path code: epsm_trace_reparam.h).
+// epsm_trace_reparam.hip -- kernels + C ABI of the reparameterised backward pass and of its transpose, the forward pass
+// (include/epsm_trace.h, epsm_trace_paths_reparam / epsm_trace_paths_reparam_forward; per-path code: epsm_trace_reparam.h).
 #include <stdio.h>
 #include <string.h>
 
@@ -144,6 +144,100 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
     }
 }
 
+// ---------------------------------------------------------------------------
+// the forward pass (epsm_trace_paths_reparam_forward): three launches on the backward's request layout
+// ---------------------------------------------------------------------------
+// Stages 1 and 3: one lane = one path, replayed.  Stage 1 (RecordSink) writes the warp requests and evaluates nothing; stage 3
+// (ReadSink) reads each request's tangents back, does the dual evaluations and writes the path's d_radiance / d_film.
+template <class Sink>
+__global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_fwd_path_kernel(rp::ReparamFwdArgs R, rp::WarpReq *req, int *count) {
+    constexpr int kLds = 32;
+    __shared__ uint32_t s_stack[kLds * EPSM_RP_THREADS];
+    uint32_t deep[kBvhStack - kLds];
+    const int64_t i = (int64_t) blockIdx.x * EPSM_RP_THREADS + threadIdx.x;
+    BvhStack st{s_stack + threadIdx.x, EPSM_RP_THREADS};
+    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
+    if (i >= R.A.N) return;
+    Sink sink{req, R.A.N, i, 0};
+    rp::reparam_forward_one_path(R, i, st, sink);
+    if (!Sink::kEval) count[i] = sink.n;
+}
+
+// Stage 2: one lane = one auxiliary ray, a group of G lanes = one request, listed and walked as in epsm_reparam_warp_kernel (the
+// same rays).  Each lane gathers the motion of its hit and of the request's glued origin; the group reduces Z, dZ and then
+// sum w_i v_i', sum (dw_i - w_i dZ / Z) . v_i' (warp_forward); lane 0 writes d' and div' into the request's gdir / gdiv.
+template <int G>
+__global__ __launch_bounds__(256) void epsm_reparam_fwd_warp_kernel(rp::ReparamFwdArgs R, rp::WarpReq *req, const int *count, int n_max) {
+    constexpr int kPaths = 256, kGroups = 256 / G;
+    __shared__ uint32_t s_pstack[kPacketStack * 4];
+    __shared__ uint16_t s_list[kPaths * rp::kMaxReq];
+    __shared__ int s_off[rp::kMaxReq * 4 + 1];
+    const int64_t N = R.A.N, p0 = (int64_t) blockIdx.x * kPaths;
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    int c = p0 + tid < N ? count[p0 + tid] : 0;
+    c = c < n_max ? c : n_max;
+    int rank[rp::kMaxReq];
+#pragma unroll
+    for (int n = 0; n < rp::kMaxReq; ++n) {
+        const unsigned long long m = __ballot(c > n);
+        rank[n] = __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u));
+        if (lane == 0) s_off[n * 4 + wv] = __popcll(m);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int e = 0; e < rp::kMaxReq * 4; ++e) { const int v = s_off[e]; s_off[e] = run; run += v; }
+        s_off[rp::kMaxReq * 4] = run;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < rp::kMaxReq; ++n)
+        if (c > n) s_list[s_off[n * 4 + wv] + rank[n]] = (uint16_t) ((n << 8) | tid);
+    __syncthreads();
+    const int total = s_off[rp::kMaxReq * 4];
+    const int r = tid % G;
+    for (int b0 = 0; b0 < total; b0 += kGroups) {
+        const int b = b0 + tid / G;
+        const bool live = b < total;
+        const int e = s_list[live ? b : 0], n = e >> 8;
+        const int64_t i = p0 + (e & 255);
+        const rp::WarpReq q = req[(int64_t) n * N + i];
+        const F3 o = f3(q.o[0], q.o[1], q.o[2]), d = f3(q.d[0], q.d[1], q.d[2]);
+        F3 fs, ft;
+        coordinate_system(d, fs, ft);
+        rp::Aux A;
+        A.w = 0.f; A.dw = zero3<float>(); A.v = d; A.tri = kNoIndex; A.b1 = A.b2 = A.inv_dist = 0.f;
+        const bool mine = live && r < R.cfg.rays;
+        rp::AuxDraw D; D.ray.o = o; D.ray.d = d; D.ray.maxt = 0.f; D.tangent = zero3<float>(); D.sy_ = 0.f;
+        if (mine) D = rp::aux_begin(R.cfg, rp::WarpId{0xffffffffu ^ R.A.seed, (uint32_t) (R.A.path_offset + i), n}, r, o, d, fs, ft);
+        const TriHit ath = packet_intersect(R.A.S, D.ray, mine, s_pstack + wv * kPacketStack);
+        if (mine) A = rp::aux_finish(R.A.S, R.cfg, D, ath, o, d);
+        float Z = A.w; F3 dZ = A.dw;
+#pragma unroll
+        for (int m = 1; m < G; m <<= 1) { Z += __shfl_xor(Z, m); dZ.x += __shfl_xor(dZ.x, m); dZ.y += __shfl_xor(dZ.y, m); dZ.z += __shfl_xor(dZ.z, m); }
+        Z = fmaxf(Z, 1e-8f);
+        const float iZ = 1.f / Z;
+        F3 wv3 = zero3<float>();
+        float dv = 0.f;
+        if (mine) {
+            const F3 t_o = q.ftri != kNoIndex ? rp::follow_tangent(R.A.S, R.T, q.ftri, q.fb1, q.fb2) : zero3<float>();
+            const F3 tv = rp::aux_tangent(R.A.S, R.T, A, d, t_o, q.em_inv_dist);
+            wv3 = tv * A.w;
+            dv = dot(A.dw - dZ * (iZ * A.w), tv);
+        }
+#pragma unroll
+        for (int m = 1; m < G; m <<= 1) {
+            wv3.x += __shfl_xor(wv3.x, m); wv3.y += __shfl_xor(wv3.y, m); wv3.z += __shfl_xor(wv3.z, m);
+            dv += __shfl_xor(dv, m);
+        }
+        if (live && r == 0) {
+            const F3 td = (wv3 - d * dot(d, wv3)) * iZ;
+            rp::WarpReq &w = req[(int64_t) n * N + i];
+            w.gdir[0] = td.x; w.gdir[1] = td.y; w.gdir[2] = td.z; w.gdiv = dv * iZ;
+        }
+    }
+}
+
 size_t req_bytes(int64_t N) { return ((size_t) N * rp::kMaxReq * sizeof(rp::WarpReq) + 255) & ~(size_t) 255; }
 
 }  // namespace
@@ -201,5 +295,63 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
         e = hipGetLastError();
         if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam", e);
     }
+    return EPSM_OK;
+}
+
+extern "C" size_t epsm_trace_reparam_forward_workspace_bytes(int64_t N) { return epsm_trace_reparam_workspace_bytes(N); }
+
+extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                                uint32_t seed, int spp, int max_depth, int rr_depth,
+                                                int64_t path_offset, int64_t N, const float *radiance,
+                                                const float *tan_pos, const float *tan_nrm,
+                                                int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
+                                                float *d_radiance, float *d_film, void *workspace, size_t workspace_bytes, void *stream) {
+    epsm_host::err_buf()[0] = 0;
+    auto bad = [&](const char *what) { char msg[200]; snprintf(msg, sizeof(msg), "epsm_trace_paths_reparam_forward: %s", what); return fail(EPSM_EINVAL, msg); };
+    if (!scene || !sensor) return bad("NULL scene / sensor");
+    if (N == 0) return EPSM_OK;
+    if (N < 0 || spp < 1 || max_depth < 1 || rr_depth < 1 || path_offset < 0) return bad("bad N / spp / max_depth / rr_depth / path_offset");
+    if (sensor->border < 0 || sensor->border > 8) return bad("bad sensor border");
+    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
+        path_offset + N > 0xFFFFFFFFLL)
+        return bad("path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32)");
+    if (!radiance || !tan_pos || !d_radiance || !d_film) return bad("NULL per-path input / output or tan_pos");
+    if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < epsm_trace_reparam_forward_workspace_bytes(N))
+        return bad("workspace: 16-byte aligned, >= epsm_trace_reparam_forward_workspace_bytes(N)");
+    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
+        return bad("need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0");
+    if (flags & ~EPSM_REPARAM_ANTITHETIC) return bad("unknown flag");
+    if (scene->n_triangles <= 0 || !scene->positions || !scene->normals || !scene->tri || !scene->tri_mesh || !scene->meshes ||
+        !scene->bsdfs || !scene->bvh || !scene->prim_index || !scene->tri_verts)
+        return bad("NULL scene array");
+    if (const char *why = epsm_host::scene_tables_invalid(scene)) return bad(why);
+    rp::ReparamFwdArgs R;
+    memset(&R, 0, sizeof(R));
+    R.A.S = *scene; R.A.C = *sensor;
+    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
+    R.A.path_offset = path_offset; R.A.N = N;
+    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
+    rp::WarpReq *req = (rp::WarpReq *) workspace;
+    int *count = (int *) ((char *) workspace + req_bytes(N));
+    const dim3 path_grid((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS));
+    hipError_t e;
+    if (reparam_max_depth > 0) {                                           // (no warp at depth 0: stage 3 alone)
+        hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::RecordSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
+        e = hipGetLastError();
+        if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
+        const int depth = max_depth < 6 ? max_depth : 6;
+        const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
+        const int G = reparam_rays <= 16 ? 16 : reparam_rays <= 32 ? 32 : 64;
+        const dim3 grid((unsigned) ((N + 255) / 256));
+        if (G == 16) hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<16>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+        else if (G == 32) hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<32>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+        else hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<64>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+        e = hipGetLastError();
+        if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
+    }
+    hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::ReadSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
+    e = hipGetLastError();
+    if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
     return EPSM_OK;
 }

@@ -185,6 +185,16 @@ class EPSMIntegrator:
                 _dist.allreduce_param_grads(target.flat)   # one RCCL all-reduce of the whole buffer
                 params.flat += target.flat
 
+    # -- forward ------------------------------------------------------------
+    def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
+        """common.py:118-197: d image / d theta . delta theta, (H,W,3), for the tangent ``params`` (laid out like the gradients
+        of ``render_backward``).  The transpose of the 3-channel branch of ``render_backward``: the ``prb`` forward pass at this
+        integrator's depths -- the attached colour parameters; geometry tangents contribute nothing, as that branch leaves the
+        geometry alone.  The 5-channel branch transports a requested pixel motion (epsm.py:236-272) and is no adjoint of a
+        rendered quantity: it has no forward form."""
+        prb = PRBIntegrator({"max_depth": self.max_depth, "rr_depth": self.rr_depth})
+        return prb.render_forward(scene, params, sensor=sensor, seed=seed, spp=spp)
+
     def tracer_depth(self) -> int:
         """``max_depth`` as the tracer takes it: the path loop stops after 6 bounces whatever the integrator says
         (epsm.py:549) and -1 means "no limit" (common.py:31-37)."""
@@ -333,6 +343,91 @@ def film_adjoint_reparam_torch(film_pos: torch.Tensor, radiance: torch.Tensor, g
     return dL.contiguous(), adj.contiguous()
 
 
+def film_splat_tangent(d_accum: torch.Tensor, film_pos: torch.Tensor, radiance: torch.Tensor, d_radiance: torch.Tensor,
+                       d_film: Optional[torch.Tensor], rfilter: int) -> None:
+    """Forward mode of splat + weight division, the transpose of ``film_adjoint_reparam`` (and, with ``d_film`` None, of
+    ``film_adjoint``): ACCUMULATES into ``d_accum (H,W,4)``, per pixel p,
+        dA_p += (grad f(p - pos_i) . d pos_i + f d det_i) L_i + f d L_i,    dW_p += grad f . d pos_i + f d det_i
+    for the samples' film positions (n,2), radiance (n,3) and tangents ``d_radiance (n,3)``, ``d_film (n,3)`` = [d pos.x, d pos.y,
+    d det] (None: the samples do not move).  ``develop_tangent`` turns the film and this into the image's tangent.
+    On the GPU: ONE kernel (``epsm_film_splat_tangent``, include/epsm_trace.h); the torch form is its checker and the CPU path."""
+    if film_pos.is_cuda:
+        import ctypes as C
+        from . import _lib
+        n = int(film_pos.shape[0])
+        fp, rad, drad = film_pos.detach().float().contiguous(), radiance.detach().float().contiguous(), d_radiance.detach().float().contiguous()
+        dfilm = None if d_film is None else d_film.detach().float().contiguous()
+        assert d_accum.is_contiguous() and d_accum.dtype == torch.float32
+        _lib.check(_lib.lib().epsm_film_splat_tangent(n, fp.data_ptr(), rad.data_ptr(), drad.data_ptr(),
+                                                       None if dfilm is None else dfilm.data_ptr(), int(d_accum.shape[1]),
+                                                       int(d_accum.shape[0]), int(rfilter), d_accum.data_ptr(),
+                                                       C.c_void_p(_lib.stream(film_pos.device))), "epsm_film_splat_tangent")
+        return
+    d_accum += film_splat_tangent_torch(film_pos, radiance, d_radiance, d_film, d_accum.shape[0], d_accum.shape[1], rfilter)
+
+
+def film_splat_tangent_torch(film_pos: torch.Tensor, radiance: torch.Tensor, d_radiance: torch.Tensor, d_film: Optional[torch.Tensor],
+                             H: int, W: int, rfilter: int) -> torch.Tensor:
+    """``film_splat_tangent`` as dense torch operations: returns the (H,W,4) tangent film of the samples."""
+    out = torch.zeros((H * W, 4), device=film_pos.device, dtype=torch.float32)
+    px, py = film_pos[:, 0], film_pos[:, 1]
+    X, Y = torch.floor(px).long(), torch.floor(py).long()
+    if rfilter == 0:                                      # EPSM_RFILTER_BOX: the weight does not move with the sample
+        if d_film is not None:
+            raise ValueError("film_splat_tangent: a box filter has no derivative in the film position")
+        ok = (X >= 0) & (Y >= 0) & (X < W) & (Y < H)
+        out[:, :3].index_add_(0, (Y * W + X)[ok], d_radiance[ok].float())
+        return out.view(H, W, 4)
+    radius, alpha = 2.0, -1.0 / (2.0 * 0.5 * 0.5)
+    bias = math.exp(alpha * radius * radius)
+    off = torch.arange(-2, 3, device=film_pos.device)
+    xs, ys = X[:, None] + off[None, :], Y[:, None] + off[None, :]
+    dx, dy = (xs.float() + 0.5) - px[:, None], (ys.float() + 0.5) - py[:, None]
+
+    def weights(d_, inside):
+        e = torch.exp(alpha * d_ * d_)
+        w = (e - bias).clamp_min(0)
+        live = (d_.abs() <= radius) & inside & (w > 0)
+        return torch.where(live, w, torch.zeros_like(w)), torch.where(live, -2.0 * alpha * d_ * e, torch.zeros_like(w))
+    wx, dwx = weights(dx, (xs >= 0) & (xs < W))
+    wy, dwy = weights(dy, (ys >= 0) & (ys < H))
+    w2 = wy[:, :, None] * wx[:, None, :]                                     # (n,5,5)
+    if d_film is None:
+        dw = torch.zeros_like(w2)
+    else:
+        fx, fy, fd = d_film[:, 0, None, None], d_film[:, 1, None, None], d_film[:, 2, None, None]
+        dw = wy[:, :, None] * dwx[:, None, :] * fx + dwy[:, :, None] * wx[:, None, :] * fy + w2 * fd
+    rgb = dw[..., None] * radiance[:, None, None, :] + w2[..., None] * d_radiance[:, None, None, :]
+    inside = ((ys >= 0) & (ys < H))[:, :, None] & ((xs >= 0) & (xs < W))[:, None, :]
+    idx = (ys.clamp(0, H - 1)[:, :, None] * W + xs.clamp(0, W - 1)[:, None, :])[inside]
+    out.index_add_(0, idx, torch.cat([rgb, dw[..., None]], dim=-1)[inside])
+    return out.view(H, W, 4)
+
+
+def develop_tangent(accum: torch.Tensor, d_accum: torch.Tensor) -> torch.Tensor:
+    """The tangent of the developed image A / W: (dA - image dW) / W, zero where the primal film has no weight."""
+    Wp = accum[..., 3:4]
+    inv = torch.where(Wp > 0, 1.0 / Wp.clamp_min(1e-30), torch.zeros_like(Wp))
+    return (d_accum[..., :3] - accum[..., :3] * inv * d_accum[..., 3:4]) * inv
+
+
+def _develop_forward(scene, sensor: int, films) -> torch.Tensor:
+    """Sums the image tangents of the (primal film, tangent film) pairs of a forward pass; with several ranks ONE all-reduce of
+    all of them first."""
+    s = scene.sensors[min(sensor, len(scene.sensors) - 1)]
+    out = torch.zeros((s.height, s.width, 3), device=scene.device, dtype=torch.float32)
+    if not films:
+        return out
+    _, world = _dist.world()
+    if world > 1:
+        flat = torch.stack([t for pair in films for t in pair])
+        _dist.allreduce_param_grads(flat)
+        films = [(flat[2 * k], flat[2 * k + 1]) for k in range(len(films))]
+    for accum, d_accum in films:
+        out += develop_tangent(accum, d_accum)
+    return out
+
+
 class PRBIntegrator:
     """Second phase of the reference's ``*_hybrid`` scheme (EPSM/optim.py:87-94, 113-119 switch to ``prb_reparam`` after
     ``thres`` iterations): a 3-channel image and the COLOUR adjoint -- ``render_backward`` takes ``grad_in (H,W,3)``
@@ -373,6 +468,43 @@ class PRBIntegrator:
     def render_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
         """Accumulates into ``params.color`` (one all-reduce of this call's contribution when there are several ranks)."""
         self._color_backward(scene, params, grad_in, sensor, seed, spp)
+
+    def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
+        """common.py:118-197: the image's tangent d image / d theta . delta theta (H,W,3) for the tangent ``params`` (its
+        ``color`` rows: the attached colour parameters), under the estimator and the random numbers of ``render`` /
+        ``render_backward`` with the same seed and spp -- the exact transpose of ``render_backward``."""
+        films = []
+        c = self._color_forward(scene, params, sensor, seed, spp)
+        if c is not None:
+            films.append(c)
+        return _develop_forward(scene, sensor, films)
+
+    def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
+        """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
+        primal pass's film weights.  Returns this rank's (primal film, tangent film), or None when no colour is attached."""
+        if not getattr(scene, "color_slots", None):
+            if self.reparam:
+                return None
+            if getattr(scene, "has_attached_geometry", lambda: False)():
+                raise NotImplementedError(
+                    "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
+                    "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
+                    "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
+            return None
+        si = min(sensor, len(scene.sensors) - 1)
+        s = scene.sensors[si]
+        spp = spp or s.spp
+        rank, world = _dist.world()
+        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+        d_accum = torch.zeros_like(accum)
+        values = scene.color_values()                                   # (C,3)
+        t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
+        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
+            film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
+            scene.film_splat(accum, s, film_pos, radiance)
+            dL = (sums * t[None]).sum(dim=1)                            # (n,3)
+            film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
+        return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
         if not getattr(scene, "color_slots", None):
@@ -467,6 +599,69 @@ class PRBReparamIntegrator(PRBIntegrator):
             params.nrm += full.nrm
             return
         self._geometry_backward(scene, params, grad_in, sensor, seed, spp)
+
+    def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
+        """The transpose of ``render_backward``: the colour part of ``PRBIntegrator.render_forward`` plus the reparameterised
+        forward pass (``Scene.trace_reparam_forward``) for the tangents of the attached meshes' vertex positions / normals and,
+        with ``Scene.attach_sensor``, of the sensor's position (``params.cam_origin``)."""
+        films = []
+        c = self._color_forward(scene, params, sensor, seed, spp)
+        if c is not None:
+            films.append(c)
+        cam = bool(getattr(scene, "sensor_attached", False))
+        if not scene.has_attached_geometry() and not cam:
+            return _develop_forward(scene, sensor, films)
+        dev = scene.device
+        tan_nrm = params.nrm.to(dev, torch.float32).contiguous()
+        if cam:
+            # the sensor moving by t = every shape moving by -t: the attached meshes' own rows on top, every mesh attached for the call
+            if any(e["type"] == 1 for e in scene.emitter_desc):
+                raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
+                                          "sensor's gradient; scenes with point emitters keep the sensor fixed")
+            tan_pos = (-params.cam_origin.to(dev, torch.float32))[None, :].repeat(params.V, 1)
+            was = [(m, bool(getattr(m, "pos_attached", False))) for m in scene.meshes]
+            for m, a in was:
+                if a:
+                    lo, hi = params.mesh_slices[m.name]
+                    tan_pos[lo:hi] += params.pos[lo:hi].to(dev, torch.float32)
+            for m, _ in was:
+                m.pos_attached = True
+            scene._refresh_attach_flags(sync_host=False)
+            try:
+                films.append(self._geometry_forward(scene, tan_pos.contiguous(), tan_nrm, sensor, seed, spp))
+            finally:
+                for m, a in was:
+                    m.pos_attached = a
+                scene._refresh_attach_flags(sync_host=False)
+        else:
+            films.append(self._geometry_forward(scene, params.pos.to(dev, torch.float32).contiguous(), tan_nrm, sensor, seed, spp))
+        return _develop_forward(scene, sensor, films)
+
+    def _geometry_forward(self, scene, tan_pos: torch.Tensor, tan_nrm: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0):
+        """The transpose of ``_geometry_backward``: this rank's (primal film, tangent film) of the reparameterised pass."""
+        si = min(sensor, len(scene.sensors) - 1)
+        s = scene.sensors[si]
+        if s.rfilter == 0:
+            raise Exception("ADIntegrator detected the potential for image-space motion due to differentiable shape or camera "
+                            "pose parameters. This is, however, incompatible with the box reconstruction filter that is "
+                            "currently used. Please specify a smooth reconstruction filter in your scene description (e.g. "
+                            "'gaussian', which is actually the default)")          # common.py:379-388
+        spp = spp or s.spp
+        rank, world = _dist.world()
+        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+        d_accum = torch.zeros_like(accum)
+        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "reparam", rank, world):
+            with _prof.phase("epsm.prb_reparam.primal_pass"):
+                tr = scene._trace(si, seed, spp, self._depth(), 0, lo, hi)
+                scene.film_splat(accum, s, tr.film_pos, tr.radiance)
+            radiance = tr.radiance.contiguous()
+            with _prof.phase("epsm.prb_reparam.reparam_forward"):
+                d_rad, d_film = scene.trace_reparam_forward(si, seed, spp, self._depth(), lo, hi, radiance, tan_pos, tan_nrm,
+                                                            int(self.reparam_max_depth), self.reparam_rays, self.reparam_kappa,
+                                                            self.reparam_exp, antithetic=self.reparam_antithetic)
+            with _prof.phase("epsm.prb_reparam.film_tangent"):
+                film_splat_tangent(d_accum, tr.film_pos, radiance, d_rad, d_film, s.rfilter)
+        return accum, d_accum
 
     def _geometry_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
         si = min(sensor, len(scene.sensors) - 1)

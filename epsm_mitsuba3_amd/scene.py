@@ -1285,6 +1285,34 @@ class Scene:
             C.c_size_t(ws.numel()), C.c_void_p(stream))
         self._check(rc, "epsm_trace_paths_reparam")
 
+    def trace_reparam_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tan_pos,
+                              tan_nrm, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float, antithetic: bool = False):
+        """``epsm_trace_paths_reparam_forward``: the forward mode of ``trace_reparam`` (its exact transpose) on paths [lo, hi).  For the
+        tangents ``tan_pos`` / ``tan_nrm`` (V,3) of the vertex positions / normals -- read on the attached meshes only -- returns, per
+        path, ``d_radiance (n,3)`` and ``d_film (n,3)`` = d (film position x, y; det), which integrators.film_splat_tangent turns
+        into the image's tangent.  Same workspace as ``trace_reparam``."""
+        lib, stream = self._runtime()
+        dev = self.device
+        n = hi - lo
+        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3) and radiance.device.type == dev.type
+        for t_ in (tan_pos, tan_nrm):
+            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (self.V, 3) and t_.device.type == dev.type
+        d_radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        d_film = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        cs = self.sensors[sensor_index].c_struct()
+        need = int(lib.epsm_trace_reparam_forward_workspace_bytes(C.c_int64(n)))
+        ws = getattr(self, "_reparam_ws", None)
+        if ws is None or ws.numel() < max(need, 16) or ws.device != radiance.device:
+            ws = self._reparam_ws = torch.empty(max(need, 16), device=radiance.device, dtype=torch.uint8)
+        rc = lib.epsm_trace_paths_reparam_forward(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(tan_pos.data_ptr()),
+            C.c_void_p(tan_nrm.data_ptr()), int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
+            C.c_uint32(1 if antithetic else 0), C.c_void_p(d_radiance.data_ptr()), C.c_void_p(d_film.data_ptr()),
+            C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_reparam_forward")
+        return d_radiance, d_film
+
     def film_splat(self, accum: torch.Tensor, sensor: Sensor, film_pos: torch.Tensor, radiance: torch.Tensor) -> None:
         """``epsm_film_splat``: adds the samples of a tile -- film positions (n,2), radiance (n,3) -- into the film accumulator
         ``accum`` (H,W,4) [r,g,b,w] of ``sensor`` with its reconstruction filter."""

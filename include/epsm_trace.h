@@ -322,6 +322,30 @@ int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor *sensor,
                              int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                              float *grad_pos, float *grad_nrm, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_reparam_forward -- forward mode of the same pass: what `prb_reparam`'s render_forward
+ *   (src/python/python/ad/integrators/common.py:118-197, prb_reparam.py:243-589 under ADMode.Forward) computes for the
+ *   geometry, as the exact TRANSPOSE of epsm_trace_paths_reparam: the same paths, the same auxiliary rays and the same
+ *   detached quantities.  For tangents of the vertex positions (and vertex normals) of the meshes flagged
+ *   EPSM_MESH_POS_ATTACHED (EPSM_MESH_NRM_ATTACHED) -- the rows of other meshes are not read -- it WRITES, per path:
+ *     d_radiance    (N,3) d L
+ *     d_film        (N,3) d film position (x, y in pixels) and d det of the primary ray's reparameterisation
+ *   so that sum(adj_radiance * d_radiance + adj_film * d_film) = sum(grad_pos * tan_pos + grad_nrm * tan_nrm) for any
+ *   adjoints the backward pass is given.  radiance, reparam_max_depth .. flags: as for epsm_trace_paths_reparam;
+ *   tan_pos, tan_nrm (V,3) f32 device buffers, tan_nrm may be NULL; workspace >= epsm_trace_reparam_forward_workspace_bytes(N).
+ *   Three launches: (1) a lane replays its path and writes its warp requests (ray, glued origin, emitter distance);
+ *   (2) one lane per auxiliary ray, as in the backward pass, gathers the motion of its hit and of the origin, and each
+ *   request's group reduces them to the tangent of its direction and of its divergence; (3) a lane replays its path again,
+ *   reads those back and evaluates each vertex once per colour channel in dual numbers.  No atomics.
+ * ------------------------------------------------------------------------- */
+size_t epsm_trace_reparam_forward_workspace_bytes(int64_t N);
+int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                     uint32_t seed, int spp, int max_depth, int rr_depth,
+                                     int64_t path_offset, int64_t N,
+                                     const float *radiance, const float *tan_pos, const float *tan_nrm,
+                                     int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
+                                     float *d_radiance, float *d_film, void *workspace, size_t workspace_bytes, void *stream);
+
 /* epsm_film_splat -- ImageBlock::put + weight division (film.develop): accumulates
  * radiance with the reconstruction filter into accum (height,width,4) [r,g,b,w] (atomics);
  * epsm_film_develop divides into image (height,width,3). */
@@ -338,6 +362,15 @@ int epsm_film_develop(int width, int height, const float *accum, float *image, v
  * which epsm_trace_paths_reparam takes as adj_radiance / adj_film.  One kernel, no allocation. */
 int epsm_film_adjoint_reparam(int64_t N, const float *film_pos, const float *radiance, const float *grad_img, int grad_channels,
                               const float *accum, int width, int height, float *dL, float *adj, void *stream);
+
+/* epsm_film_splat_tangent -- forward mode of splat + weight division, the transpose of epsm_film_adjoint_reparam (common.py:880-920):
+ * per sample i (film position (N,2), radiance (N,3)) and its tangents d_radiance (N,3) and d_film (N,3) = [d pos.x, d pos.y,
+ * d det], ACCUMULATES into d_accum (height,width,4), with the filter and footprint of epsm_film_splat,
+ *   d_accum[p].rgb += (grad f(p - pos_i) . d pos_i + f d det_i) L_i + f d L_i,   d_accum[p].w += grad f . d pos_i + f d det_i
+ * The tangent of the developed image is (d_accum.rgb - image * d_accum.w) / accum.w with the primal film.  d_film may be
+ * NULL (colour tangents: the samples stay where they are); with the box filter it must be. */
+int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radiance, const float *d_radiance, const float *d_film,
+                            int width, int height, int rfilter, float *d_accum, void *stream);
 
 /* epsm_probe -- evaluates ONE of the tracer's per-path functions on n rows of plain numbers, on the device, with the very
  * code the tracer runs (csrc/epsm_probe_core.h).  It exists so that the known answers the reference's own unit tests hold

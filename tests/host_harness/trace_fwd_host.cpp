@@ -1,0 +1,32 @@
+// TEST HARNESS ONLY: the host build of the tracer (trace_host.cpp) plus the forward mode of the reparameterised pass,
+// epsm_trace_paths_reparam_forward (include/epsm_trace.h) on host pointers.  Like the host backward pass, a path traces its
+// warps on the spot (rp::InlineFwdSink): same auxiliary rays, same numbers as the device's three stages.  Built into its own
+// library by tests/_forward_host.py.  Not shipped, not a fallback.
+#include "trace_host.cpp"
+
+extern "C" size_t epsm_trace_reparam_forward_workspace_bytes(int64_t) { return 0; }
+
+extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
+                                                int rr_depth, int64_t path_offset, int64_t N, const float *radiance,
+                                                const float *tan_pos, const float *tan_nrm, int reparam_max_depth, int reparam_rays,
+                                                float kappa, float exponent, uint32_t flags, float *d_radiance, float *d_film, void *,
+                                                size_t, void *) {
+    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux) return -22;
+    if (!radiance || !tan_pos || !d_radiance || !d_film) return -22;
+    rp::ReparamFwdArgs R;
+    memset(&R, 0, sizeof(R));
+    R.A.S = *scene; R.A.C = *sensor;
+    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
+    R.A.path_offset = path_offset; R.A.N = N;
+    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < N; ++i) {
+        uint32_t stack[kBvhStack];
+        rp::Warp W;
+        const BvhStack st{stack, 1};
+        rp::InlineFwdSink sink{R.A.S, R.cfg, R.T, st, W, rp::WarpId{0xffffffffu ^ seed, (uint32_t) (path_offset + i), 0}};
+        rp::reparam_forward_one_path(R, i, st, sink);
+    }
+    return 0;
+}
