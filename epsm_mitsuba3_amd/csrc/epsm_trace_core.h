@@ -1009,6 +1009,12 @@ EPSM_HD int path_max_depth(const TraceArgs &A) { return A.max_depth < 6 ? A.max_
 struct NoObserver {
     EPSM_HD void vertex(const SurfHit &, const EpsmBsdf &, uint32_t, F3, F3, const EmitterSample &, bool, float, const BsdfSample &, bool) {}
 };
+// An observer that declares `state(const PathState &)` is also shown the loop state right before `vertex`: the ray just traced
+// (at a miss surface_interaction has zeroed the SurfHit, so the escaped direction is s.ray.d), L collected so far, beta and the MIS
+// state of the previous bounce (the texel adjoint, epsm_trace_texture.h).  The others -- NoObserver, the reparameterised pass's --
+// are not, and compile to what they did.
+template <class Obs> EPSM_HD auto observe_state(Obs &obs, const PathState &s, int) -> decltype(obs.state(s), void()) { obs.state(s); }
+template <class Obs> EPSM_HD void observe_state(Obs &, const PathState &, long) {}
 // EPSM_TRACE_FUSE_FIRST_HIT: does the rule retire a path at its FIRST vertex, hit `th`?  Follows from the mesh's and the BSDF's flag
 // bits alone; `lite` then holds what first_hit_rows reads -- validity, mesh flags, triangle id and, for a diffuse mesh hit, the
 // triangle's positions and the barycentrics -- and `w` the vertex's five flag bits.
@@ -1169,6 +1175,7 @@ EPSM_HD void path_bounce(const TraceArgs &A, int64_t i, int iteration, PathState
         }
         if (here >= 0 && bs.valid) s.cnt += 1u << (8 * here);              // the sampled direction carries one more factor rho_j
     }
+    observe_state(obs, s, 0);
     obs.vertex(si, bsdf, flags, Le, Lr_dir, es, active_em, mis_em, bs, s.active);
     // ---- update (epsm.py:658-683)
     if (s.active) vis.direct(s.L, Le, Lr_dir);

@@ -428,6 +428,32 @@ def _develop_forward(scene, sensor: int, films) -> torch.Tensor:
     return out
 
 
+class _TexelBuffers:
+    """One flat buffer of the texel gradients of a backward call, (H, W, 3) views per texture slot."""
+
+    def __init__(self, shapes, device):
+        self.flat = torch.zeros(sum(3 * h * w for h, w in shapes), device=device, dtype=torch.float32)
+        self.views, o = [], 0
+        for h, w in shapes:
+            self.views.append(self.flat[o: o + 3 * h * w].view(h, w, 3))
+            o += 3 * h * w
+
+
+def _texture_scratch(scene, params: ParamGrads) -> _TexelBuffers:
+    shapes = scene.texture_shapes()
+    if list(getattr(params, "tex_shapes", [])) != list(shapes):
+        raise ValueError("texture slots are attached: the gradient buffer must come from Scene.param_grads() after attach_texture")
+    return _TexelBuffers(shapes, scene.device)
+
+
+def _texture_tangents(scene, params: ParamGrads):
+    """The texel tangents the forward replay reads, per slot: the bitmap's tangent (``ParamGrads.texture``) times its scale."""
+    shapes = scene.texture_shapes()
+    if list(getattr(params, "tex_shapes", [])) != list(shapes):
+        raise ValueError("texture slots are attached: the tangent must come from Scene.param_grads() after attach_texture")
+    return [(params.texture(k).to(scene.device, torch.float32) * scene.texture_scale(k)).contiguous() for k in range(len(shapes))]
+
+
 class PRBIntegrator:
     """Second phase of the reference's ``*_hybrid`` scheme (EPSM/optim.py:87-94, 113-119 switch to ``prb_reparam`` after
     ``thres`` iterations): a 3-channel image and the COLOUR adjoint -- ``render_backward`` takes ``grad_in (H,W,3)``
@@ -481,8 +507,10 @@ class PRBIntegrator:
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
-        primal pass's film weights.  Returns this rank's (primal film, tangent film), or None when no colour is attached."""
-        if not getattr(scene, "color_slots", None):
+        primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``).  Returns this
+        rank's (primal film, tangent film), or None when neither a colour nor a texture is attached."""
+        texs = bool(getattr(scene, "texture_slots", None))
+        if not getattr(scene, "color_slots", None) and not texs:
             if self.reparam:
                 return None
             if getattr(scene, "has_attached_geometry", lambda: False)():
@@ -499,15 +527,19 @@ class PRBIntegrator:
         d_accum = torch.zeros_like(accum)
         values = scene.color_values()                                   # (C,3)
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
+        tex_t = _texture_tangents(scene, params) if texs else None
         for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
             dL = (sums * t[None]).sum(dim=1)                            # (n,3)
+            if texs:
+                dL = dL + scene.trace_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
             film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        if not getattr(scene, "color_slots", None):
+        texs = bool(getattr(scene, "texture_slots", None))
+        if not getattr(scene, "color_slots", None) and not texs:
             if self.reparam:
                 return
             if getattr(scene, "has_attached_geometry", lambda: False)():
@@ -522,22 +554,31 @@ class PRBIntegrator:
         rank, world = _dist.world()
         accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
         kept = []
-        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
+        tiles = scene.tile_plan(s.wavefront_size(spp), "color", rank, world)
+        for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
-            kept.append((film_pos, sums))
+            kept.append((film_pos, sums, radiance.contiguous() if texs else None))
         if world > 1:
             _dist.allreduce_param_grads(accum)
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
-        for film_pos, sums in kept:
+        tex = _texture_scratch(scene, params) if texs else None
+        for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, accum[..., 3], s.rfilter)    # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
+            if texs:                                                    # the texel adjoint: a replay of the same paths
+                scene.trace_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
         contrib = contrib / values.clamp_min(1e-12)
         if world > 1:
             _dist.allreduce_param_grads(contrib)
         params.color += contrib
+        if texs:
+            if world > 1:
+                _dist.allreduce_param_grads(tex.flat)                   # this call's texel contribution, once
+            for k, v in enumerate(tex.views):
+                params.texture(k).add_(v, alpha=scene.texture_scale(k))   # (an envmap's: w.r.t. the bitmap before its scale)
 
 
 class PRBReparamIntegrator(PRBIntegrator):
@@ -585,7 +626,8 @@ class PRBReparamIntegrator(PRBIntegrator):
                 m.pos_attached = True
             scene._refresh_attach_flags(sync_host=False)
             try:
-                full = ParamGrads(params.V, params.B, device=params.flat.device, mesh_slices=params.mesh_slices, n_colors=params.C)
+                full = ParamGrads(params.V, params.B, device=params.flat.device, mesh_slices=params.mesh_slices, n_colors=params.C,
+                                  tex_shapes=getattr(params, "tex_shapes", None))
                 self._geometry_backward(scene, full, grad_in, sensor, seed, spp)
             finally:
                 for m, a in was:

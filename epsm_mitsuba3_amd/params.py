@@ -6,7 +6,7 @@ pass needs a single RCCL all-reduce, with no packing copies.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -14,19 +14,28 @@ import torch
 class ParamGrads:
     """``pos (V,3)``: d/d vertex_positions; ``nrm (V,3)``: d/d vertex_normals;
     ``alpha (B)``: d/d per-BSDF roughness; ``cam_origin (3)``: d/d ray origin
-    (epsm.py:260-261); ``color (C,3)``: d/d the attached colour parameters (PRBIntegrator).  Vertex indices are global: meshes are concatenated and a
-    mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
+    (epsm.py:260-261); ``color (C,3)``: d/d the attached colour parameters (PRBIntegrator); ``texture(slot) (H,W,3)``: d/d the
+    texels of an attached bitmap (``Scene.attach_texture``), one section per entry of ``tex_shapes`` at the END of ``flat`` -- every
+    other offset, and the buffer of a scene without textures, are what they are without them.  Vertex indices are global: meshes
+    are concatenated and a mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
 
-    def __init__(self, n_vertices: int, n_bsdfs: int = 0, device="cuda", mesh_slices: Optional[dict] = None, n_colors: int = 0):
+    def __init__(self, n_vertices: int, n_bsdfs: int = 0, device="cuda", mesh_slices: Optional[dict] = None, n_colors: int = 0,
+                 tex_shapes: Optional[Sequence[Tuple[int, int]]] = None):
         self.V, self.B, self.C = int(n_vertices), int(n_bsdfs), int(n_colors)
-        n = 6 * self.V + self.B + 3 + 3 * self.C
+        self.tex_shapes = [(int(h), int(w)) for h, w in (tex_shapes or [])]
+        n0 = 6 * self.V + self.B + 3 + 3 * self.C
+        n = n0 + sum(3 * h * w for h, w in self.tex_shapes)
         self.flat = torch.zeros(n, device=device, dtype=torch.float32)
         self.pos = self.flat[: 3 * self.V].view(self.V, 3)
         self.nrm = self.flat[3 * self.V: 6 * self.V].view(self.V, 3)
         self.alpha = self.flat[6 * self.V: 6 * self.V + self.B]
         self.cam_origin = self.flat[6 * self.V + self.B: 6 * self.V + self.B + 3]
         # colour parameters of the hybrid scheme's second phase (diffuse reflectances, emitter radiances): (C,3)
-        self.color = self.flat[6 * self.V + self.B + 3:].view(self.C, 3)
+        self.color = self.flat[6 * self.V + self.B + 3: n0].view(self.C, 3)
+        self._tex, o = [], n0
+        for h, w in self.tex_shapes:
+            self._tex.append(self.flat[o: o + 3 * h * w].view(h, w, 3))
+            o += 3 * h * w
         self.mesh_slices = dict(mesh_slices or {})
 
     def zero_(self):
@@ -38,8 +47,13 @@ class ParamGrads:
         contributes before it is summed over the ranks and added to the accumulated gradients."""
         s = getattr(self, "_scratch", None)
         if s is None:
-            s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C)
+            s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C,
+                                           tex_shapes=self.tex_shapes)
         return s.zero_()
+
+    def texture(self, slot: int) -> torch.Tensor:
+        """(H, W, 3) view of texture slot ``slot`` (``Scene.attach_texture``): d/d the bitmap the user gave."""
+        return self._tex[slot]
 
     def mesh_pos(self, name: str) -> torch.Tensor:
         lo, hi = self.mesh_slices[name]

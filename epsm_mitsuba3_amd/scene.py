@@ -724,6 +724,8 @@ class Scene:
         self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it bounds prb_reparam's tiles (tile_plan)
         self.alpha_slots: Dict[int, int] = {}
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
+        self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoint: ("bsdf" | "envmap", index)
+        self.emitter_names = [f"emitter{i}" for i in range(len(self.emitter_desc))]     # (from_dict: the scene dict's keys)
         self.rr_depth = 5
         # test hook: tests/host_harness compiles the tracer's per-path code for the CPU and plugs
         # its entry points in here; the product path (None) is the HIP library and needs a GPU (_runtime)
@@ -798,7 +800,7 @@ class Scene:
                 named[val.get("id", key)] = add_bsdf(key, val)
                 named[key] = named[val.get("id", key)]
         default_bsdf = None
-        meshes, emitters, sensors = [], [], []
+        meshes, emitters, sensors, emitter_names = [], [], [], []
         for key, val in d.items():
             if not isinstance(val, dict):
                 continue
@@ -808,6 +810,7 @@ class Scene:
             elif t == "point":
                 emitters.append(dict(type=1, mesh=-1, radiance=_rgb(val.get("intensity"), [1, 1, 1]),
                                      position=np.asarray(val.get("position", [0, 0, 0]), np.float32)))
+                emitter_names.append(key)
             elif t in ("constant", "envmap"):
                 if any(e["type"] in (2, 3) for e in emitters):
                     raise ValueError("a scene has at most one environment emitter")
@@ -815,8 +818,10 @@ class Scene:
                          position=np.zeros(3, np.float32))
                 if t == "envmap":
                     e["bitmap"] = _envmap_bitmap(val, base_dir)
+                    e["scale"] = float(val.get("scale", 1.0))            # (the texel adjoint's gradient is w.r.t. the bitmap before it)
                     e["to_world"] = np.asarray(val.get("to_world", np.eye(4)), dtype=np.float64)
                 emitters.append(e)
+                emitter_names.append(key)
             elif t in ("obj", "ply", "mesh", "rectangle"):
                 tw = np.asarray(val.get("to_world", np.eye(4)), dtype=np.float64)
                 uv = None
@@ -849,6 +854,7 @@ class Scene:
                     elif v2.get("type") == "area":
                         emitters.append(dict(type=0, mesh=len(meshes), radiance=_rgb(v2.get("radiance"), [1, 1, 1]),
                                              position=np.zeros(3, np.float32)))
+                        emitter_names.append(key)
                         emitter_id = len(emitters) - 1
                 if bsdf_id is None:
                     if default_bsdf is None:
@@ -858,8 +864,10 @@ class Scene:
                 meshes.append(Mesh(key, v, f, n, bsdf=bsdf_id, emitter=emitter_id,
                                    flip_normals=bool(val.get("flip_normals", False)), is_mesh=(t != "rectangle"),
                                    face_normals=face_normals, uv=uv))
-        return Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder,
-                     scene_tables=scene_tables)
+        sc = Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder,
+                   scene_tables=scene_tables)
+        sc.emitter_names = emitter_names
+        return sc
 
     # -- parameters ----------------------------------------------------------------------------
     def mesh(self, name: str) -> Mesh:
@@ -943,6 +951,93 @@ class Scene:
         kind, i = self.color_slots[slot]
         (self.bsdf_desc[i] if kind == "bsdf" else self.emitter_desc[i])["reflectance" if kind == "bsdf" else "radiance"] = [float(x) for x in rgb]
         self._upload()
+
+    def attach_texture(self, name) -> int:
+        """``dr.enable_grad(params['<bsdf>.reflectance.data'])`` -- the ``bitmap`` reflectance of a diffuse BSDF, by BSDF name -- or
+        ``dr.enable_grad(params['<emitter>.data'])`` -- the envmap's bitmap, by emitter name or index -- for the texel adjoint
+        (``epsm_trace_paths_texture_backward``; PRBIntegrator).  Returns the slot: ``ParamGrads.texture(slot)``."""
+        key = None
+        if isinstance(name, str):
+            for suffix in (".reflectance.data", ".data"):
+                if name.endswith(suffix) and name[: -len(suffix)] in self.bsdf_names + self.emitter_names:
+                    name = name[: -len(suffix)]
+                    break
+        if isinstance(name, str) and name in self.bsdf_names:
+            i = self.bsdf_names.index(name)
+            if self.bsdf_desc[i]["type"] != 0:
+                raise ValueError(f"attach_texture: {name!r} is not a diffuse BSDF (only a diffuse reflectance may be a bitmap here)")
+            if "texture" not in self.bsdf_desc[i]:
+                raise ValueError(f"attach_texture: the reflectance of {name!r} is not a bitmap (attach_color takes a constant one)")
+            key = ("bsdf", i)
+        else:
+            i = name if isinstance(name, int) else (self.emitter_names.index(name) if name in self.emitter_names else -1)
+            if not (0 <= i < len(self.emitter_desc)):
+                raise ValueError(f"attach_texture: {name!r} is neither a BSDF nor an emitter of this scene")
+            if self.emitter_desc[i]["type"] == 2:
+                raise ValueError("attach_texture: a `constant` environment has no bitmap (attach_radiance takes its radiance)")
+            if self.emitter_desc[i]["type"] != 3:
+                raise ValueError("attach_texture: the emitter is not an envmap (the scene has no envmap of that name)")
+            if not float(self.emitter_desc[i].get("scale", 1.0)):
+                raise ValueError("attach_texture: an envmap with scale 0")
+            key = ("envmap", i)
+        if key not in self.texture_slots:
+            if len(self.texture_slots) >= 8:                        # EPSM_MAX_TEXTURE_GRADS
+                raise ValueError("at most 8 texture parameters")
+            self.texture_slots.append(key)
+        return self.texture_slots.index(key)
+
+    def texture_shapes(self):
+        """(H, W) of every attached texture slot, slot order (ParamGrads' ``tex_shapes``)."""
+        return [self._texture_shape(k)[:2] for k in range(len(self.texture_slots))]
+
+    def _texture_shape(self, slot: int):
+        kind, i = self.texture_slots[slot]
+        a = self.bsdf_desc[i]["texture"]["bitmap"] if kind == "bsdf" else self.emitter_desc[i]["bitmap"]
+        return tuple(int(x) for x in a.shape)
+
+    def texture_values(self, slot: int) -> torch.Tensor:
+        """(H, W, 3) current bitmap of texture slot ``slot`` -- an envmap's as the user gave it, before its ``scale``."""
+        kind, i = self.texture_slots[slot]
+        if kind == "bsdf":
+            a = self.bsdf_desc[i]["texture"]["bitmap"]
+        else:
+            e = self.emitter_desc[i]
+            a = e["bitmap"] / np.float32(e.get("scale", 1.0))
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+
+    def texture_scale(self, slot: int) -> float:
+        """d texel / d bitmap of a slot: an envmap's ``scale``, 1 for a BSDF's bitmap."""
+        kind, i = self.texture_slots[slot]
+        return float(self.emitter_desc[i].get("scale", 1.0)) if kind == "envmap" else 1.0
+
+    def set_texture(self, slot: int, array):
+        """``params['<...>.data'] = array; params.update()`` for texture slot ``slot``: the texels are rewritten in place on the
+        device (same shape only); for the envmap its sampling tables are rebuilt too -- ``environment_tables`` (host tables) or
+        ``epsm_environment_tables`` (``scene_tables="device"``)."""
+        kind, i = self.texture_slots[slot]
+        a = np.asarray(array.detach().cpu().numpy() if torch.is_tensor(array) else array, dtype=np.float32)
+        if a.ndim == 2:
+            a = np.repeat(a[:, :, None], 3, axis=2)
+        old = self._texture_shape(slot)
+        if a.shape != old:
+            raise ValueError(f"set_texture: shape {a.shape} is not the slot's {old}")
+        f32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+        if kind == "bsdf":
+            b = self.bsdf_desc[i]
+            b["texture"]["bitmap"] = np.ascontiguousarray(a)
+            b["reflectance"] = b["texture"]["bitmap"].reshape(-1, 3).mean(0).astype(np.float32)         # (the stand-in of from_dict)
+            self._tex_buf[b["texture_index"]][0].copy_(f32(a))
+            self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
+            return
+        e = self.emitter_desc[i]
+        e["bitmap"] = np.ascontiguousarray(a * float(e.get("scale", 1.0)))        # (as _envmap_bitmap applies it)
+        if self.scene_tables == "device":
+            from . import scene_tables as st
+            new = list(st.environment_tables(f32(e["bitmap"])))
+        else:
+            new = [f32(x) for x in environment_tables(e["bitmap"])]
+        for dst, src in zip(self._env_buf, new):
+            dst.copy_(src)
 
     def set_alpha(self, bsdf_name: str, alpha: float):
         """``params['<bsdf>.alpha.value'] = alpha; params.update()``: only the BSDF table is rewritten (in place)."""
@@ -1042,7 +1137,7 @@ class Scene:
 
     def param_grads(self) -> ParamGrads:
         return ParamGrads(self.V, len(self.alpha_slots), device=self.device, mesh_slices=self.mesh_slices,
-                          n_colors=len(self.color_slots))
+                          n_colors=len(self.color_slots), tex_shapes=self.texture_shapes())
 
     # -- upload ----------------------------------------------------------------------------------
     def _upload(self):
@@ -1244,19 +1339,67 @@ class Scene:
         lib, stream = self._runtime()
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
-        if Cn == 0:
+        if Cn == 0 and not self.texture_slots:
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
         film_pos = torch.empty((n, 2), device=dev, dtype=torch.float32)
         radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
         valid = torch.empty((n,), device=dev, dtype=torch.uint8)
-        sums = torch.empty((n, Cn, 3), device=dev, dtype=torch.float32)
+        # (textures alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the texel adjoint's replay
+        # must see the radiance of this very estimator)
+        sums = torch.empty((n, max(Cn, 1), 3), device=dev, dtype=torch.float32)
         cs = self.sensors[sensor_index].c_struct()
         rc = lib.epsm_trace_paths_color(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
                                         int(self.rr_depth), C.c_int64(lo), C.c_int64(n), C.c_void_p(film_pos.data_ptr()),
                                         C.c_void_p(radiance.data_ptr()), C.c_void_p(valid.data_ptr()), C.c_void_p(sums.data_ptr()),
-                                        int(Cn), C.c_void_p(stream))
+                                        int(max(Cn, 1)), C.c_void_p(stream))
         self._check(rc, "epsm_trace_paths_color")
-        return film_pos, radiance, sums
+        return film_pos, radiance, sums[:, :Cn]
+
+    def _texture_pointers(self, bufs):
+        """The (n_textures) pointer array and the envmap pointer of the texture entry points for per-slot (H, W, 3) buffers."""
+        n_tex = len(getattr(self, "_tex_buf", []))
+        arr, env = (C.c_void_p * max(1, n_tex))(), None
+        for (kind, i), t_ in zip(self.texture_slots, bufs):
+            assert t_.is_contiguous() and t_.dtype == torch.float32 and t_.device.type == self.device.type
+            assert tuple(t_.shape) == self._texture_shape(self.texture_slots.index((kind, i)))
+            if kind == "bsdf":
+                arr[self.bsdf_desc[i]["texture_index"]] = t_.data_ptr()
+            else:
+                env = C.c_void_p(t_.data_ptr())
+        return C.cast(arr, C.c_void_p), env
+
+    def trace_texture_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
+                               grads):
+        """``epsm_trace_paths_texture_backward``: ACCUMULATES d loss / d texel of paths [lo, hi) into ``grads`` -- one (H, W, 3) buffer
+        per texture slot, w.r.t. the texels the tracer reads (an envmap's: its bitmap times ``scale``) -- given the radiance of the
+        primal pass (``trace_color`` with the same seed) and its adjoint."""
+        lib, stream = self._runtime()
+        n = hi - lo
+        for t_ in (radiance, adj_radiance):
+            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, 3) and t_.device.type == self.device.type
+        arr, env = self._texture_pointers(grads)
+        cs = self.sensors[sensor_index].c_struct()
+        rc = lib.epsm_trace_paths_texture_backward(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()), arr, env,
+            C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_texture_backward")
+
+    def trace_texture_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangents):
+        """``epsm_trace_paths_texture_forward``: the transpose of ``trace_texture_backward`` -- for one (H, W, 3) texel tangent per
+        texture slot returns d radiance (n, 3) of paths [lo, hi)."""
+        lib, stream = self._runtime()
+        n = hi - lo
+        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3)
+        arr, env = self._texture_pointers(tangents)
+        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
+        cs = self.sensors[sensor_index].c_struct()
+        rc = lib.epsm_trace_paths_texture_forward(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), arr, env, C.c_void_p(d_radiance.data_ptr()),
+            C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_texture_forward")
+        return d_radiance
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                       adj_film, grad_pos, grad_nrm, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float,

@@ -346,6 +346,39 @@ int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const EpsmSensor *s
                                      int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                                      float *d_radiance, float *d_film, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_texture_backward -- the TEXEL adjoint of `prb` (prb.py, sampling, Russian roulette and MIS detached):
+ *   paths [path_offset, path_offset + N) are replayed under the primal seed as epsm_trace_paths_color traced them, and
+ *   d loss / d texel is ACCUMULATED (float atomics, after a merge over the lanes of a wave that share a footprint) for
+ *     - the `bitmap` reflectance of a diffuse BSDF (EpsmBsdf.texture = t): grad_tex[t], (height_t, width_t, 3) f32 shaped like
+ *       EpsmScene.textures[t].  A diffuse vertex k looked up at uv_k adds adj . L_after_k / rho_k x w to each texel of its
+ *       footprint (4 bilinear, 1 nearest; wrap as the lookup), L_after_k = radiance - L collected up to and including the
+ *       emission at k; a channel with rho_k = 0 adds nothing (prb.py's inv_bsdf_val_det);
+ *     - the envmap (EpsmScene.env.kind == EPSM_ENV_ENVMAP): grad_env, (height, width, 3) f32 -- the bitmap's shape: column
+ *       `width` of EpsmEnvironment.texels folds into column 0.  A ray that leaves the scene adds adj . beta mis x w, an emitter
+ *       sample on the map adj . beta bsdf mis / pdf x w when it is not occluded; the sampling tables are detached.
+ *     radiance      (N,3) L of every path from the primal pass (epsm_trace_paths_color with the same seed / spp / depths)
+ *     adj_radiance  (N,3) d loss / d L (the adjoint of splat + weight division, which the caller owns)
+ *     grad_tex      NULL or an array of n_textures HOST pointers; entry t NULL = texture t not attached.  At most
+ *                   EPSM_MAX_TEXTURE_GRADS entries non-NULL (EPSM_EINVAL): they go into the kernel's arguments, no allocation
+ *     grad_env      NULL or the envmap's buffer
+ *   One launch.  No host synchronisation.
+ * epsm_trace_paths_texture_forward -- its exact transpose: the same replay GATHERS the tangents tan_tex / tan_env (same
+ *   layouts, read only where attached) and WRITES d_radiance (N,3), so that sum(adj_radiance * d_radiance) =
+ *   sum(grad_tex . tan_tex) + sum(grad_env . tan_env) for any adjoint.  No atomics.
+ * ------------------------------------------------------------------------- */
+#define EPSM_MAX_TEXTURE_GRADS 8
+int epsm_trace_paths_texture_backward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                      uint32_t seed, int spp, int max_depth, int rr_depth,
+                                      int64_t path_offset, int64_t N,
+                                      const float *radiance, const float *adj_radiance,
+                                      float *const *grad_tex, float *grad_env, void *stream);
+int epsm_trace_paths_texture_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                     uint32_t seed, int spp, int max_depth, int rr_depth,
+                                     int64_t path_offset, int64_t N,
+                                     const float *radiance, const float *const *tan_tex, const float *tan_env,
+                                     float *d_radiance, void *stream);
+
 /* epsm_film_splat -- ImageBlock::put + weight division (film.develop): accumulates
  * radiance with the reconstruction filter into accum (height,width,4) [r,g,b,w] (atomics);
  * epsm_film_develop divides into image (height,width,3). */
