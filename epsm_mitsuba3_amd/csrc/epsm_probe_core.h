@@ -60,12 +60,25 @@ EPSM_HD void probe_row(int what, const float *in, float *out, const EpsmBsdf *bs
             bsdf_eval_pdf(*bsdf, f3(in[0], in[1], in[2]), f3(in[3], in[4], in[5]), v, pdf);
             out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = pdf;
         } break;
+        case EPSM_PROBE_MICROFACET_DALPHA: {           // in: m (3), v (3) -> d ln D(m) / d alpha, d ln G1(v, m) / d alpha, D(m), G1(v, m)
+            const F3 m = f3(in[0], in[1], in[2]), v = f3(in[3], in[4], in[5]);
+            out[0] = mf_eval_dlog_dalpha(*bsdf, m); out[1] = mf_smith_g1_dlog_dalpha(*bsdf, v, m);
+            out[2] = mf_eval(*bsdf, m); out[3] = mf_smith_g1(*bsdf, v, m);
+        } break;
+        case EPSM_PROBE_BSDF_DALPHA: {                 // in: wi (3), wo (3) -> d value / d alpha (3), d ln value / d alpha
+            F3 v; float pdf;
+            const F3 wi = f3(in[0], in[1], in[2]), wo = f3(in[3], in[4], in[5]);
+            bsdf_eval_pdf(*bsdf, wi, wo, v, pdf);
+            const float dl = bsdf->type == EPSM_BSDF_ROUGHCONDUCTOR_T ? rough_dlog_dalpha(*bsdf, wi, wo) : 0.f;
+            out[0] = v.x * dl; out[1] = v.y * dl; out[2] = v.z * dl; out[3] = dl;
+        } break;
         default: break;
     }
 }
 
 EPSM_HD bool probe_needs_bsdf(int what) {
-    return what == EPSM_PROBE_MICROFACET || what == EPSM_PROBE_MICROFACET_SAMPLE || what == EPSM_PROBE_BSDF_SAMPLE || what == EPSM_PROBE_BSDF_EVAL;
+    return what == EPSM_PROBE_MICROFACET || what == EPSM_PROBE_MICROFACET_SAMPLE || what == EPSM_PROBE_BSDF_SAMPLE || what == EPSM_PROBE_BSDF_EVAL ||
+           what == EPSM_PROBE_MICROFACET_DALPHA || what == EPSM_PROBE_BSDF_DALPHA;
 }
 EPSM_HD bool probe_needs_sensor(int what) { return what == EPSM_PROBE_PRIMARY_RAY; }
 

@@ -383,6 +383,40 @@ EPSM_HD float mf_smith_g1(const EpsmBsdf &b, F3 v, F3 m) {
     if (dot(v, m) * v.z <= 0.f) result = 0.f;
     return result;
 }
+// d ln D(m) / d alpha and d ln G1(v, m) / d alpha in closed form (the roughness adjoint, epsm_trace_bsdf.h); 0 wherever the value
+// is cut to a constant: mf_eval's 1e-20 cut-off, G1 = 1 (the Beckmann fit's a >= 1.6 side, xy_alpha_2 == 0) and G1 = 0.
+//   with s = (m_x^2 + m_y^2) / alpha^2:  Beckmann  ln D = -s / m_z^2 - 2 ln alpha + c     GGX  ln D = -2 ln alpha - 2 ln(s + m_z^2) + c
+EPSM_HD float mf_eval_dlog_dalpha(const EpsmBsdf &b, F3 m) {
+    if (mf_eval(b, m) == 0.f) return 0.f;
+    const float a = b.alpha, s = (sqr(m.x) + sqr(m.y)) / (a * a);
+    if (b.distr == EPSM_DISTR_BECKMANN) return (2.f / a) * ((s - sqr(m.z)) / sqr(m.z));
+    return (2.f / a) * ((s - sqr(m.z)) / (s + sqr(m.z)));
+}
+//   both are functions of tan^2 = alpha^2 (v_x^2 + v_y^2) / v_z^2:  Beckmann's fit R(a), a = 1 / sqrt(tan^2), d a / d alpha = -a / alpha;
+//   GGX  G1 = 2 / (1 + r), r = sqrt(1 + tan^2), d r / d alpha = tan^2 / (alpha r)
+EPSM_HD float mf_smith_g1_dlog_dalpha(const EpsmBsdf &b, F3 v, F3 m) {
+    const float xy_alpha_2 = sqr(b.alpha * v.x) + sqr(b.alpha * v.y), tan2 = xy_alpha_2 / sqr(v.z);
+    if (xy_alpha_2 == 0.f || dot(v, m) * v.z <= 0.f) return 0.f;
+    if (b.distr == EPSM_DISTR_BECKMANN) {
+        const float a = 1.f / sqrtf(tan2), a2 = a * a;
+        if (a >= 1.6f) return 0.f;
+        const float num = 3.535f * a + 2.181f * a2, den = 1.f + 2.276f * a + 2.577f * a2;
+        const float dnum = 3.535f + 2.f * 2.181f * a, dden = 2.276f + 2.f * 2.577f * a;
+        return -(dnum / num - dden / den) * a / b.alpha;
+    }
+    const float r = sqrtf(1.f + tan2);
+    return -tan2 / (b.alpha * r * (1.f + r));
+}
+// d ln f / d alpha of the roughconductor's value f = F D G / (4 cos_i) for (wi, wo) as bsdf_eval_pdf sees them -- the Fresnel
+// factor and the reflectance do not depend on alpha, so this one scalar serves every channel; 0 where f = 0.
+EPSM_HD float rough_dlog_dalpha(const EpsmBsdf &b, F3 wi, F3 wo) {
+    if (b.twosided && wi.z < 0.f) { wi.z = -wi.z; wo.z = -wo.z; }
+    if (!(wi.z > 0.f && wo.z > 0.f)) return 0.f;
+    const F3 H = normalize3(wi + wo);
+    if (mf_eval(b, H) == 0.f) return 0.f;
+    if (mf_smith_g1(b, wi, H) * mf_smith_g1(b, wo, H) == 0.f) return 0.f;
+    return mf_eval_dlog_dalpha(b, H) + mf_smith_g1_dlog_dalpha(b, wi, H) + mf_smith_g1_dlog_dalpha(b, wo, H);
+}
 EPSM_HD float mf_pdf(const EpsmBsdf &b, F3 wi, F3 m) {
     float result = mf_eval(b, m);
     if (b.sample_visible) result *= mf_smith_g1(b, wi, m) * fabsf(dot(wi, m)) / wi.z;

@@ -259,19 +259,19 @@ class ManifoldCausticIntegrator(EPSMIntegrator):
     variant = "manifold_caustic"
 
 
-def film_adjoint(film_pos: torch.Tensor, grad_img: torch.Tensor, weight_img: torch.Tensor, rfilter: int) -> torch.Tensor:
-    """Adjoint of ImageBlock::put + film.develop (``epsm_film_splat`` / ``epsm_film_develop``) w.r.t. the radiance of
-    every sample: image[p] = sum_i w_ip L_i / W_p, so dL_i = sum_p grad[p] w_ip / W_p -- the box filter touches the
-    pixel under the sample, the gaussian (stddev 0.5, radius 2, src/rfilters/gaussian.cpp) its 5x5 window.
-    ``film_pos (n,2)``, ``grad_img (H,W,3)``, ``weight_img (H,W)`` = W_p of the primal pass; returns ``(n,3)``."""
-    H, W = weight_img.shape
-    g = grad_img[..., :3] / weight_img.clamp_min(1e-30)[..., None]
-    g = torch.where((weight_img > 0)[..., None], g, torch.zeros_like(g))
+def _box_window(film_pos: torch.Tensor, H: int, W: int):
+    """The pixel under every sample, (X, Y) (n) each, and whether it is on the film."""
+    X, Y = torch.floor(film_pos[:, 0]).long(), torch.floor(film_pos[:, 1]).long()
+    return X, Y, (X >= 0) & (Y >= 0) & (X < W) & (Y < H)
+
+
+def _gaussian_window(film_pos: torch.Tensor, H: int, W: int):
+    """The 5 x 5 window of the gaussian reconstruction filter (stddev 0.5, radius 2, src/rfilters/gaussian.cpp) around every
+    sample: pixel columns ``xs`` and rows ``ys`` (n,5) each, not clamped, and the separable weights ``wx``, ``wy`` (n,5), zero
+    off the film.  The weight of pixel (ys[i,a], xs[i,b]) is wy[i,a] wx[i,b]: what ``film_adjoint`` gathers with and what
+    ``film_weight_counts`` sums."""
     px, py = film_pos[:, 0], film_pos[:, 1]
     X, Y = torch.floor(px).long(), torch.floor(py).long()
-    if rfilter == 0:                                      # EPSM_RFILTER_BOX
-        ok = (X >= 0) & (Y >= 0) & (X < W) & (Y < H)
-        return g[Y.clamp(0, H - 1), X.clamp(0, W - 1)] * ok[:, None]
     radius, alpha = 2.0, -1.0 / (2.0 * 0.5 * 0.5)
     bias = math.exp(alpha * radius * radius)
     off = torch.arange(-2, 3, device=film_pos.device)
@@ -280,8 +280,44 @@ def film_adjoint(film_pos: torch.Tensor, grad_img: torch.Tensor, weight_img: tor
     wx = torch.where(dx.abs() <= radius, (torch.exp(alpha * dx * dx) - bias).clamp_min(0), torch.zeros_like(dx))
     wy = torch.where(dy.abs() <= radius, (torch.exp(alpha * dy * dy) - bias).clamp_min(0), torch.zeros_like(dy))
     wx = wx * ((xs >= 0) & (xs < W)); wy = wy * ((ys >= 0) & (ys < H))
+    return xs, ys, wx, wy
+
+
+def film_adjoint(film_pos: torch.Tensor, grad_img: torch.Tensor, weight_img: torch.Tensor, rfilter: int) -> torch.Tensor:
+    """Adjoint of ImageBlock::put + film.develop (``epsm_film_splat`` / ``epsm_film_develop``) w.r.t. the radiance of
+    every sample: image[p] = sum_i w_ip L_i / W_p, so dL_i = sum_p grad[p] w_ip / W_p -- the box filter touches the
+    pixel under the sample, the gaussian (stddev 0.5, radius 2, src/rfilters/gaussian.cpp) its 5x5 window.
+    ``film_pos (n,2)``, ``grad_img (H,W,3)``, ``weight_img (H,W)`` = W_p of the primal pass; returns ``(n,3)``."""
+    H, W = weight_img.shape
+    g = grad_img[..., :3] / weight_img.clamp_min(1e-30)[..., None]
+    g = torch.where((weight_img > 0)[..., None], g, torch.zeros_like(g))
+    if rfilter == 0:                                      # EPSM_RFILTER_BOX
+        X, Y, ok = _box_window(film_pos, H, W)
+        return g[Y.clamp(0, H - 1), X.clamp(0, W - 1)] * ok[:, None]
+    xs, ys, wx, wy = _gaussian_window(film_pos, H, W)
     gw = g[ys.clamp(0, H - 1)[:, :, None], xs.clamp(0, W - 1)[:, None, :]]      # (n,5,5,3)
     return (gw * (wy[:, :, None] * wx[:, None, :])[..., None]).sum(dim=(1, 2))
+
+
+_WEIGHT_ONE = float(1 << 40)
+
+
+def film_weight_counts(counts: torch.Tensor, film_pos: torch.Tensor, rfilter: int) -> None:
+    """The film's weight channel W_p = sum_i w_ip of a tile's samples in FIXED POINT: adds round(w_ip 2^40) to ``counts`` (H,W)
+    int64.  Integer addition is associative, so the sums are the same bits in whatever order the adds land -- unlike the float
+    atomics of ``epsm_film_splat``, whose weight channel differs in its last bits from call to call.  The roughness adjoint is
+    summed without atomics so that a call repeats bit for bit; the adjoint radiance it is fed divides by W_p, so W_p must repeat
+    too.  (2^-40 per sample is far below float32's resolution; 2^23 samples of weight 1 fit a pixel.)"""
+    H, W = counts.shape
+    flat = counts.view(-1)
+    if rfilter == 0:                                      # EPSM_RFILTER_BOX
+        X, Y, ok = _box_window(film_pos, H, W)
+        flat.index_add_(0, Y.clamp(0, H - 1) * W + X.clamp(0, W - 1), ok.long() << 40)
+        return
+    xs, ys, wx, wy = _gaussian_window(film_pos, H, W)
+    w = torch.round((wy[:, :, None] * wx[:, None, :]).double() * _WEIGHT_ONE).long()              # (n,5,5)
+    idx = ys.clamp(0, H - 1)[:, :, None] * W + xs.clamp(0, W - 1)[:, None, :]
+    flat.index_add_(0, idx.reshape(-1), w.reshape(-1))
 
 
 def film_adjoint_reparam(film_pos: torch.Tensor, radiance: torch.Tensor, grad_img: torch.Tensor, accum: torch.Tensor):
@@ -454,6 +490,19 @@ def _texture_tangents(scene, params: ParamGrads):
     return [(params.texture(k).to(scene.device, torch.float32) * scene.texture_scale(k)).contiguous() for k in range(len(shapes))]
 
 
+def _alpha_slots(scene, params: ParamGrads) -> int:
+    """The number of roughness slots the colour adjoint serves (``Scene.attach_alpha``); ``params.alpha`` must hold them."""
+    n = len(getattr(scene, "alpha_slots", None) or {})
+    if n and not hasattr(scene, "trace_alpha_backward"):
+        raise NotImplementedError("roughness slots are attached to a scene object without Scene.trace_alpha_backward: the colour "
+                                  "adjoint cannot differentiate them (and does not drop them)")
+    if n:
+        scene._alpha_slot_count()                   # (refuses more than EPSM_MAX_ALPHA_GRADS)
+        if params.B < n:
+            raise ValueError("roughness slots are attached: the gradient buffer must come from Scene.param_grads() after attach_alpha")
+    return n
+
+
 class PRBIntegrator:
     """Second phase of the reference's ``*_hybrid`` scheme (EPSM/optim.py:87-94, 113-119 switch to ``prb_reparam`` after
     ``thres`` iterations): a 3-channel image and the COLOUR adjoint -- ``render_backward`` takes ``grad_in (H,W,3)``
@@ -507,10 +556,14 @@ class PRBIntegrator:
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
-        primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``).  Returns this
-        rank's (primal film, tangent film), or None when neither a colour nor a texture is attached."""
+        primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``) and the
+        roughness tangents ``params.alpha`` of the attached roughconductors (``Scene.trace_alpha_forward``).  Returns this rank's
+        (primal film, tangent film), or None when neither a colour, a texture nor a roughness is attached.  (The tangent film is
+        developed with the film's own float-atomic weights, while the backward pass of a call with a roughness divides by their
+        fixed-point sums: ~1e-7 apart, far inside the transpose identity's bound.)"""
         texs = bool(getattr(scene, "texture_slots", None))
-        if not getattr(scene, "color_slots", None) and not texs:
+        n_alpha = _alpha_slots(scene, params)
+        if not getattr(scene, "color_slots", None) and not texs and not n_alpha:
             if self.reparam:
                 return None
             if getattr(scene, "has_attached_geometry", lambda: False)():
@@ -528,18 +581,22 @@ class PRBIntegrator:
         values = scene.color_values()                                   # (C,3)
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
         tex_t = _texture_tangents(scene, params) if texs else None
+        alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
         for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
             dL = (sums * t[None]).sum(dim=1)                            # (n,3)
             if texs:
                 dL = dL + scene.trace_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
+            if n_alpha:
+                dL = dL + scene.trace_alpha_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), alpha_t)
             film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
         texs = bool(getattr(scene, "texture_slots", None))
-        if not getattr(scene, "color_slots", None) and not texs:
+        n_alpha = _alpha_slots(scene, params)
+        if not getattr(scene, "color_slots", None) and not texs and not n_alpha:
             if self.reparam:
                 return
             if getattr(scene, "has_attached_geometry", lambda: False)():
@@ -553,23 +610,34 @@ class PRBIntegrator:
         spp = spp or s.spp
         rank, world = _dist.world()
         accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
-        kept = []
+        kept, counts = [], None
         tiles = scene.tile_plan(s.wavefront_size(spp), "color", rank, world)
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
-            kept.append((film_pos, sums, radiance.contiguous() if texs else None))
+            kept.append((film_pos, sums, radiance.contiguous() if texs or n_alpha else None))
+            if n_alpha:
+                if counts is None:
+                    counts = torch.zeros((s.height, s.width), device=scene.device, dtype=torch.int64)
+                film_weight_counts(counts, film_pos, s.rfilter)
         if world > 1:
             _dist.allreduce_param_grads(accum)
+            if n_alpha:
+                _dist.allreduce_param_grads(counts)
+        # (with a roughness attached the call repeats bit for bit: the weights the film adjoint divides by are the exact sums)
+        weight_img = accum[..., 3] if not n_alpha else (counts.double() / _WEIGHT_ONE).float()
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
         tex = _texture_scratch(scene, params) if texs else None
+        d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
-            dL = film_adjoint(film_pos, g, accum[..., 3], s.rfilter)    # (n,3)
+            dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
             if texs:                                                    # the texel adjoint: a replay of the same paths
                 scene.trace_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
+            if n_alpha:                                                 # the roughness adjoint: another replay of them
+                scene.trace_alpha_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_alpha)
         contrib = contrib / values.clamp_min(1e-12)
         if world > 1:
             _dist.allreduce_param_grads(contrib)
@@ -579,6 +647,10 @@ class PRBIntegrator:
                 _dist.allreduce_param_grads(tex.flat)                   # this call's texel contribution, once
             for k, v in enumerate(tex.views):
                 params.texture(k).add_(v, alpha=scene.texture_scale(k))   # (an envmap's: w.r.t. the bitmap before its scale)
+        if n_alpha:
+            if world > 1:
+                _dist.allreduce_param_grads(d_alpha)                    # this call's roughness contribution, once
+            params.alpha[:n_alpha] += d_alpha.to(params.alpha.device)
 
 
 class PRBReparamIntegrator(PRBIntegrator):

@@ -28,6 +28,7 @@ from . import dist as _dist
 from .params import ParamGrads
 
 MESH_VERTEX_NORMALS, MESH_FLIP_NORMALS, MESH_POS_ATTACHED, MESH_NRM_ATTACHED, MESH_IS_MESH, MESH_HAS_UV = 1, 2, 4, 8, 16, 32
+MAX_ALPHA_GRADS = 8          # EPSM_MAX_ALPHA_GRADS (include/epsm_trace.h; tests/test_alpha_abi.py holds the two together)
 BSDF_TYPES = {"diffuse": 0, "conductor": 1, "roughconductor": 2, "dielectric": 3}
 
 # complex IORs at R,G,B for the `material` names the experiments use (approximate: Mitsuba
@@ -1339,13 +1340,13 @@ class Scene:
         lib, stream = self._runtime()
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
-        if Cn == 0 and not self.texture_slots:
+        if Cn == 0 and not self.texture_slots and not self.alpha_slots:
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
         film_pos = torch.empty((n, 2), device=dev, dtype=torch.float32)
         radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
         valid = torch.empty((n,), device=dev, dtype=torch.uint8)
-        # (textures alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the texel adjoint's replay
-        # must see the radiance of this very estimator)
+        # (textures or roughnesses alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the replays
+        # of the texel and roughness adjoints must see the radiance of this very estimator)
         sums = torch.empty((n, max(Cn, 1), 3), device=dev, dtype=torch.float32)
         cs = self.sensors[sensor_index].c_struct()
         rc = lib.epsm_trace_paths_color(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
@@ -1399,6 +1400,51 @@ class Scene:
             C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), arr, env, C.c_void_p(d_radiance.data_ptr()),
             C.c_void_p(stream))
         self._check(rc, "epsm_trace_paths_texture_forward")
+        return d_radiance
+
+    def _alpha_slot_count(self) -> int:
+        """The alpha slots the colour adjoint's replay serves: all of them, at most EPSM_MAX_ALPHA_GRADS."""
+        B = len(self.alpha_slots)
+        if B > MAX_ALPHA_GRADS:
+            raise ValueError(f"{B} roughness parameters are attached: the colour adjoint (prb, prb_reparam, a 3-channel gradient image) "
+                             f"differentiates at most {MAX_ALPHA_GRADS} (EPSM_MAX_ALPHA_GRADS) per scene")
+        return B
+
+    def trace_alpha_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
+                             grad_alpha):
+        """``epsm_trace_paths_bsdf_backward``: ADDS d loss / d alpha of paths [lo, hi) to ``grad_alpha`` (one float per alpha slot,
+        ``attach_alpha``) given the radiance of the primal pass (``trace_color`` with the same seed) and its adjoint.  No atomics:
+        the same call gives the same bits."""
+        lib, stream = self._runtime()
+        n, B = hi - lo, self._alpha_slot_count()
+        for t_ in (radiance, adj_radiance):
+            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, 3) and t_.device.type == self.device.type
+        assert grad_alpha.is_contiguous() and grad_alpha.dtype == torch.float32 and grad_alpha.numel() == B
+        assert grad_alpha.device.type == self.device.type
+        nbytes = int(lib.epsm_trace_bsdf_workspace_bytes(C.c_int64(n)))
+        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
+        cs = self.sensors[sensor_index].c_struct()
+        rc = lib.epsm_trace_paths_bsdf_backward(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()),
+            C.c_void_p(grad_alpha.data_ptr()), int(B), C.c_void_p(work.data_ptr()), C.c_size_t(work.numel() * 4), C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_bsdf_backward")
+
+    def trace_alpha_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangent_alpha):
+        """``epsm_trace_paths_bsdf_forward``: the transpose of ``trace_alpha_backward`` -- for one tangent per alpha slot returns
+        d radiance (n, 3) of paths [lo, hi)."""
+        lib, stream = self._runtime()
+        n, B = hi - lo, self._alpha_slot_count()
+        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3)
+        assert tangent_alpha.is_contiguous() and tangent_alpha.dtype == torch.float32 and tangent_alpha.numel() == B
+        assert tangent_alpha.device.type == self.device.type
+        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
+        cs = self.sensors[sensor_index].c_struct()
+        rc = lib.epsm_trace_paths_bsdf_forward(
+            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
+            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(tangent_alpha.data_ptr()), int(B),
+            C.c_void_p(d_radiance.data_ptr()), C.c_void_p(stream))
+        self._check(rc, "epsm_trace_paths_bsdf_forward")
         return d_radiance
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,

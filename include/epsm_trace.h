@@ -379,6 +379,38 @@ int epsm_trace_paths_texture_forward(const EpsmScene *scene, const EpsmSensor *s
                                      const float *radiance, const float *const *tan_tex, const float *tan_env,
                                      float *d_radiance, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_bsdf_backward -- the ROUGHNESS adjoint of `prb` (prb.py:145-158, 209-226; sampling, Russian roulette and the
+ *   MIS weights detached): paths [path_offset, path_offset + N) are replayed under the primal seed as epsm_trace_paths_color
+ *   traced them, and d loss / d alpha is ADDED to grad_alpha[EpsmBsdf.alpha_slot] for every `roughconductor` BSDF with
+ *   0 <= alpha_slot < B.  At an active bounce on such a BSDF
+ *     - the sampled direction adds adj . L_ind  d f / d alpha / (weight pdf) per channel, L_ind = what the path collects behind
+ *       the bounce, f the value of eval_pdf for the sampled direction, weight and pdf those of the sample (a channel with
+ *       weight pdf = 0 adds nothing);
+ *     - the emitter sample adds adj . Lr_dir  d ln f / d alpha (nothing when occluded); its MIS weight is detached like the
+ *       weight of the next vertex's emission, so that the two move together.
+ *     radiance      (N,3) L of every path from the primal pass (epsm_trace_paths_color with the same seed / spp / depths)
+ *     adj_radiance  (N,3) d loss / d L
+ *     grad_alpha    (B) f32, added to; B <= EPSM_MAX_ALPHA_GRADS (EPSM_EINVAL otherwise: nothing is dropped silently)
+ *     workspace     device memory, 16-byte aligned, >= epsm_trace_bsdf_workspace_bytes(N); scratch
+ *   No float atomics: each workgroup of 128 paths reduces its sums to one row of the workspace, a second launch adds the rows
+ *   in float64 in a fixed order -- two calls with the same arguments give the same bits.  No host synchronisation.
+ * epsm_trace_paths_bsdf_forward -- its exact transpose: the same replay WRITES d_radiance (N,3) = sum over the path's terms of
+ *   their coefficient x tangent_alpha[slot], so that sum(adj_radiance * d_radiance) = sum(grad_alpha * tangent_alpha).  One launch.
+ * ------------------------------------------------------------------------- */
+#define EPSM_MAX_ALPHA_GRADS 8
+size_t epsm_trace_bsdf_workspace_bytes(int64_t N);
+int epsm_trace_paths_bsdf_backward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                   uint32_t seed, int spp, int max_depth, int rr_depth,
+                                   int64_t path_offset, int64_t N,
+                                   const float *radiance, const float *adj_radiance, float *grad_alpha, int B,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                  uint32_t seed, int spp, int max_depth, int rr_depth,
+                                  int64_t path_offset, int64_t N,
+                                  const float *radiance, const float *tangent_alpha, int B,
+                                  float *d_radiance, void *stream);
+
 /* epsm_film_splat -- ImageBlock::put + weight division (film.develop): accumulates
  * radiance with the reconstruction filter into accum (height,width,4) [r,g,b,w] (atomics);
  * epsm_film_develop divides into image (height,width,3). */
@@ -419,11 +451,13 @@ int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radia
  *   EPSM_PROBE_PRIMARY_RAY        in film position (pixels); cfg = EpsmSensor   out o, d, d_x, d_y (3 each)                  src/sensors/perspective.cpp:238-279 (src/sensors/tests/test_perspective.py:89-135)
  *   EPSM_PROBE_BSDF_SAMPLE        in wi (3), sample1, sample2 (2); cfg = EpsmBsdf out wo (3), weight (3), pdf, eta, sampled_type (bits), valid   src/bsdfs/{diffuse,conductor,roughconductor,dielectric,twosided}.cpp sample() (src/bsdfs/tests/test_dielectric.py:31-158)
  *   EPSM_PROBE_BSDF_EVAL          in wi (3), wo (3); cfg = EpsmBsdf             out value incl. cosine (3), pdf              eval_pdf() (src/bsdfs/tests/test_diffuse.py:13-35, test_twosided.py:29-45)
+ *   EPSM_PROBE_MICROFACET_DALPHA  in m (3), v (3); cfg = EpsmBsdf                out d ln D(m) / d alpha, d ln smith_g1(v, m) / d alpha, D(m), smith_g1(v, m)   the closed forms of the roughness adjoint (epsm_trace_paths_bsdf_backward)
+ *   EPSM_PROBE_BSDF_DALPHA        in wi (3), wo (3); cfg = EpsmBsdf             out d value / d alpha (3), d ln value / d alpha   roughconductor; 0 for the others
  * in: (n, EPSM_PROBE_IN) floats, out: (n, EPSM_PROBE_OUT) floats, device pointers; cfg: HOST pointer to the struct named
  * above (NULL otherwise).  Not on any hot path. */
 enum { EPSM_PROBE_TEA = 0, EPSM_PROBE_PCG32 = 1, EPSM_PROBE_SAMPLER = 2, EPSM_PROBE_MICROFACET = 3, EPSM_PROBE_MICROFACET_SAMPLE = 4,
        EPSM_PROBE_FRESNEL = 5, EPSM_PROBE_FRESNEL_CONDUCTOR = 6, EPSM_PROBE_RFILTER = 7, EPSM_PROBE_PRIMARY_RAY = 8, EPSM_PROBE_BSDF_SAMPLE = 9,
-       EPSM_PROBE_BSDF_EVAL = 10, EPSM_PROBE_COUNT = 11 };
+       EPSM_PROBE_BSDF_EVAL = 10, EPSM_PROBE_MICROFACET_DALPHA = 11, EPSM_PROBE_BSDF_DALPHA = 12, EPSM_PROBE_COUNT = 13 };
 #define EPSM_PROBE_IN 8
 #define EPSM_PROBE_OUT 16
 int epsm_probe(int what, int64_t n, const float *in, float *out, const void *cfg, void *stream);
