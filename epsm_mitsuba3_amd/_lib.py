@@ -130,6 +130,20 @@ def _declare(lib):
     declare_tracer(lib)
     declare_bvh(lib)
     declare_scene_tables(lib)
+    declare_rigid(lib)
+    return lib
+
+
+def declare_rigid(lib):
+    """Prototypes of the rigid-motion reduction and its transpose of include/epsm_trace.h (device library only)."""
+    lib.epsm_rigid_workspace_bytes.restype = C.c_size_t
+    lib.epsm_rigid_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.epsm_rigid_reduce.restype = C.c_int
+    lib.epsm_rigid_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_rigid_expand.restype = C.c_int
+    lib.epsm_rigid_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
     return lib
 
 

@@ -152,11 +152,17 @@ class EPSMIntegrator:
             # parameters attached to the scene.
             prb = PRBIntegrator({"max_depth": self.max_depth, "rr_depth": self.rr_depth})
             return prb.render_backward(scene, params, grad_in, sensor=sensor, seed=seed, spp=spp)
+        if getattr(scene, "sensor_rotation", False):
+            # this branch transports d / d ray.o alone (epsm.py:260-261): the sensor's rotation has no term in it
+            raise NotImplementedError("the 5-channel manifold branch differentiates the sensor's position only (epsm.py:260-261); the "
+                                      "gradient of its rotation is `prb_reparam`'s (attach_sensor(rotation=True))")
         rank, world = _dist.world()
         # dr.backward ACCUMULATES into the gradients that are already there.  With more than one rank only THIS
         # call's contribution may be summed over the ranks: what `params` held on entry is already a sum over the
-        # ranks (or the caller's own data) and must not be multiplied by the world size.
-        target = params.scratch() if world > 1 else params
+        # ranks (or the caller's own data) and must not be multiplied by the world size.  The rigid slots reduce this call's
+        # contribution too: then it is kept apart on one rank as well.
+        rigid = _rigid_slot_count(scene, params)
+        target = params.scratch() if world > 1 or rigid else params
         tracer = getattr(scene, "iter_traces", None) or scene.trace_paths      # a generator: one tile resident at a time
         kw = {}
         if self.fused and self.fuse_tangent and self.packed_log and getattr(scene, "supports_packed_log", False):
@@ -183,7 +189,9 @@ class EPSMIntegrator:
         if world > 1:
             with _prof.phase("epsm.render_backward.allreduce"):
                 _dist.allreduce_param_grads(target.flat)   # one RCCL all-reduce of the whole buffer
-                params.flat += target.flat
+        if target is not params:
+            params.flat += target.flat
+            _rigid_backward(scene, params, target)
 
     # -- forward ------------------------------------------------------------
     def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
@@ -503,6 +511,58 @@ def _alpha_slots(scene, params: ParamGrads) -> int:
     return n
 
 
+def _rigid_slot_count(scene, params: ParamGrads) -> int:
+    """The number of rigid slots (``Scene.attach_rigid``); ``params.rigid`` must hold them."""
+    n = len(getattr(scene, "rigid_slots", None) or [])
+    if n and getattr(params, "R", 0) < n:
+        raise ValueError("rigid slots are attached: the gradient buffer must come from Scene.param_grads() after attach_rigid")
+    return n
+
+
+def _rigid_backward(scene, params: ParamGrads, contrib: ParamGrads) -> None:
+    """``params.rigid`` += [force, torque] of every rigid slot over ONE call's contribution to the vertex rows, after its sum
+    over the ranks (``epsm_rigid_reduce``: float64, a fixed order -- every rank adds the same bits)."""
+    n = _rigid_slot_count(scene, params)
+    if n:
+        with _prof.phase("epsm.render_backward.rigid_reduce"):
+            scene.rigid_reduce(contrib.pos, contrib.nrm, params.rigid[:n], *scene.rigid_tables())
+
+
+def _sensor_pose_refusals(scene) -> bool:
+    """Whether the sensor's rotation is attached; refuses what the every-shape-moves argument cannot carry."""
+    if any(e["type"] == 1 for e in scene.emitter_desc):
+        raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
+                                  "sensor's gradient; scenes with point emitters keep the sensor fixed")
+    rot = bool(getattr(scene, "sensor_rotation", False))
+    if rot and any(e["type"] == 3 for e in scene.emitter_desc):
+        raise NotImplementedError("prb_reparam: an `envmap` would have to turn with the shapes for the gradient of the sensor's "
+                                  "rotation; scenes with an envmap take attach_sensor(rotation=False)")
+    return rot
+
+
+class _EveryMeshAttached:
+    """For the duration of the sensor's pass: the positions of every mesh attached and, for the rotation, the normals of the
+    meshes that have vertex normals (a rotation turns them too).  ``was``: (mesh, positions attached, normals attached) before."""
+
+    def __init__(self, scene, normals: bool):
+        self.scene, self.normals = scene, normals
+        self.was = [(m, bool(getattr(m, "pos_attached", False)), bool(getattr(m, "nrm_attached", False))) for m in scene.meshes]
+
+    def __enter__(self):
+        for m, _, n in self.was:
+            m.pos_attached = True
+            if self.normals:
+                m.nrm_attached = bool(n or m.has_normals)
+        self.scene._refresh_attach_flags(sync_host=False)
+        return self
+
+    def __exit__(self, *exc):
+        for m, p, n in self.was:
+            m.pos_attached, m.nrm_attached = p, n
+        self.scene._refresh_attach_flags(sync_host=False)
+        return False
+
+
 class PRBIntegrator:
     """Second phase of the reference's ``*_hybrid`` scheme (EPSM/optim.py:87-94, 113-119 switch to ``prb_reparam`` after
     ``thres`` iterations): a 3-channel image and the COLOUR adjoint -- ``render_backward`` takes ``grad_in (H,W,3)``
@@ -682,35 +742,47 @@ class PRBReparamIntegrator(PRBIntegrator):
     __repr__ = to_string
 
     def render_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        self._color_backward(scene, params, grad_in, sensor, seed, spp)
         cam = bool(getattr(scene, "sensor_attached", False))
+        rot = _sensor_pose_refusals(scene) if cam else False          # (before the colour pass: a refused call leaves nothing behind)
+        if rot and getattr(params, "cam_rotation", None) is None:
+            raise ValueError("the sensor's rotation is attached: the gradient buffer must come from Scene.param_grads() after "
+                             "attach_sensor(rotation=True)")
+        _rigid_slot_count(scene, params)
+        self._color_backward(scene, params, grad_in, sensor, seed, spp)
         if not scene.has_attached_geometry() and not cam:
             return
         if cam:
             # Moving the sensor by t moves every shape (and every emitter that is one) by -t as the sensor sees it; environment
             # emitters do not care.  So d loss / d sensor position = - sum over ALL vertices of d loss / d vertex position: the
             # same reparameterised pass with every mesh attached, summed (the primary rays' warp field carries the silhouettes).
-            if any(e["type"] == 1 for e in scene.emitter_desc):
-                raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
-                                          "sensor's gradient; scenes with point emitters keep the sensor fixed")
-            was = [(m, bool(getattr(m, "pos_attached", False))) for m in scene.meshes]
-            for m, _ in was:
-                m.pos_attached = True
-            scene._refresh_attach_flags(sync_host=False)
-            try:
+            # Its rotation likewise: the sensor turning by omega about its position o is every shape turning by -omega about o, so
+            # d loss / d omega = - the torque about o of all vertex rows, normals included; a `constant` environment does not care.
+            # Both are ONE slot of epsm_rigid_reduce over every vertex with pivot o.
+            with _EveryMeshAttached(scene, normals=rot) as every:
                 full = ParamGrads(params.V, params.B, device=params.flat.device, mesh_slices=params.mesh_slices, n_colors=params.C,
                                   tex_shapes=getattr(params, "tex_shapes", None))
                 self._geometry_backward(scene, full, grad_in, sensor, seed, spp)
-            finally:
-                for m, a in was:
-                    m.pos_attached = a
-                scene._refresh_attach_flags(sync_host=False)
-            params.cam_origin -= full.pos.sum(dim=0)
-            for m, a in was:                                   # the meshes the caller attached keep their own rows
-                if a:
-                    lo, hi = params.mesh_slices[m.name]
+            o = scene.sensors[min(sensor, len(scene.sensors) - 1)].to_world[:3, 3]
+            twist = torch.zeros((1, 6), device=full.flat.device, dtype=torch.float32)
+            ranges, pivots = scene.rigid_tables(extra=[(0, params.V, o)])
+            k = len(getattr(scene, "rigid_slots", None) or [])
+            scene.rigid_reduce(full.pos, full.nrm if rot else None, twist, ranges[k:], pivots[k:])
+            params.cam_origin -= twist[0, :3]
+            if rot:
+                params.cam_rotation -= twist[0, 3:]
+            for m, p, n in every.was:                          # the meshes the caller attached keep their own rows
+                lo, hi = params.mesh_slices[m.name]
+                if p:
                     params.pos[lo:hi] += full.pos[lo:hi]
-            params.nrm += full.nrm
+                if n:
+                    params.nrm[lo:hi] += full.nrm[lo:hi]
+            _rigid_backward(scene, params, full)
+            return
+        if _rigid_slot_count(scene, params):
+            contrib = params.scratch()                         # this call's contribution alone: what the rigid slots reduce
+            self._geometry_backward(scene, contrib, grad_in, sensor, seed, spp)
+            params.flat += contrib.flat
+            _rigid_backward(scene, params, contrib)
             return
         self._geometry_backward(scene, params, grad_in, sensor, seed, spp)
 
@@ -719,36 +791,44 @@ class PRBReparamIntegrator(PRBIntegrator):
         forward pass (``Scene.trace_reparam_forward``) for the tangents of the attached meshes' vertex positions / normals and,
         with ``Scene.attach_sensor``, of the sensor's position (``params.cam_origin``)."""
         films = []
+        cam = bool(getattr(scene, "sensor_attached", False))
+        rot = _sensor_pose_refusals(scene) if cam else False          # (before the colour pass, as the backward pass refuses)
+        if rot and getattr(params, "cam_rotation", None) is None:
+            raise ValueError("the sensor's rotation is attached: the tangent must come from Scene.param_grads() after "
+                             "attach_sensor(rotation=True)")
+        n_rigid = _rigid_slot_count(scene, params)
         c = self._color_forward(scene, params, sensor, seed, spp)
         if c is not None:
             films.append(c)
-        cam = bool(getattr(scene, "sensor_attached", False))
         if not scene.has_attached_geometry() and not cam:
             return _develop_forward(scene, sensor, films)
         dev = scene.device
-        tan_nrm = params.nrm.to(dev, torch.float32).contiguous()
+        twists = [params.rigid[:n_rigid].to(dev, torch.float32)] if n_rigid else []
+        extra = []
         if cam:
-            # the sensor moving by t = every shape moving by -t: the attached meshes' own rows on top, every mesh attached for the call
-            if any(e["type"] == 1 for e in scene.emitter_desc):
-                raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
-                                          "sensor's gradient; scenes with point emitters keep the sensor fixed")
-            tan_pos = (-params.cam_origin.to(dev, torch.float32))[None, :].repeat(params.V, 1)
-            was = [(m, bool(getattr(m, "pos_attached", False))) for m in scene.meshes]
-            for m, a in was:
-                if a:
-                    lo, hi = params.mesh_slices[m.name]
-                    tan_pos[lo:hi] += params.pos[lo:hi].to(dev, torch.float32)
-            for m, _ in was:
-                m.pos_attached = True
-            scene._refresh_attach_flags(sync_host=False)
-            try:
-                films.append(self._geometry_forward(scene, tan_pos.contiguous(), tan_nrm, sensor, seed, spp))
-            finally:
-                for m, a in was:
-                    m.pos_attached = a
-                scene._refresh_attach_flags(sync_host=False)
+            # the sensor moving by t and turning by omega about its position o = every shape moving by -t and turning by -omega
+            # about o: one more slot over every vertex, the attached meshes' own rows on top, every mesh attached for the call
+            w = params.cam_rotation.to(dev, torch.float32) if rot else torch.zeros(3, device=dev, dtype=torch.float32)
+            twists.append(-torch.cat([params.cam_origin.to(dev, torch.float32), w])[None, :])
+            extra.append((0, params.V, scene.sensors[min(sensor, len(scene.sensors) - 1)].to_world[:3, 3]))
+        # the tangents of the rows the caller attached (the others are not read -- unless the sensor's pass attaches them: zero there)
+        own = (lambda t: t.to(dev, torch.float32).clone()) if twists else (lambda t: t.to(dev, torch.float32).contiguous())
+        tan_pos = torch.zeros((params.V, 3), device=dev, dtype=torch.float32) if cam else own(params.pos)
+        tan_nrm = torch.zeros((params.V, 3), device=dev, dtype=torch.float32) if rot else own(params.nrm)
+        for m in scene.meshes:
+            lo, hi = params.mesh_slices[m.name]
+            if cam and getattr(m, "pos_attached", False):
+                tan_pos[lo:hi] += params.pos[lo:hi].to(dev, torch.float32)
+            if rot and getattr(m, "nrm_attached", False):
+                tan_nrm[lo:hi] += params.nrm[lo:hi].to(dev, torch.float32)
+        if twists:
+            ranges, pivots = scene.rigid_tables(extra=extra)
+            scene.rigid_expand(torch.cat(twists).contiguous(), tan_pos, tan_nrm, ranges, pivots)
+        if cam:
+            with _EveryMeshAttached(scene, normals=rot):
+                films.append(self._geometry_forward(scene, tan_pos, tan_nrm, sensor, seed, spp))
         else:
-            films.append(self._geometry_forward(scene, params.pos.to(dev, torch.float32).contiguous(), tan_nrm, sensor, seed, spp))
+            films.append(self._geometry_forward(scene, tan_pos, tan_nrm, sensor, seed, spp))
         return _develop_forward(scene, sensor, films)
 
     def _geometry_forward(self, scene, tan_pos: torch.Tensor, tan_nrm: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0):

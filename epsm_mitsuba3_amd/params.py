@@ -16,15 +16,21 @@ class ParamGrads:
     ``alpha (B)``: d/d per-BSDF roughness; ``cam_origin (3)``: d/d ray origin
     (epsm.py:260-261); ``color (C,3)``: d/d the attached colour parameters (PRBIntegrator); ``texture(slot) (H,W,3)``: d/d the
     texels of an attached bitmap (``Scene.attach_texture``), one section per entry of ``tex_shapes`` at the END of ``flat`` -- every
-    other offset, and the buffer of a scene without textures, are what they are without them.  Vertex indices are global: meshes
-    are concatenated and a mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
+    other offset, and the buffer of a scene without textures, are what they are without them.  ``rigid (R,6)``: d/d the twist
+    [translation, rotation about the slot's pivot] of the rigid slots (``Scene.attach_rigid``) as [force, torque];
+    ``cam_rotation (3)``: d/d omega of ``to_world <- Rot(omega) to_world`` about the sensor's own position, world axes, at omega = 0
+    (``Scene.attach_sensor(rotation=True)``).  These two sections exist only when asked for (``n_rigid``, ``cam_rotation``; None
+    otherwise) and follow the textures: a buffer constructed without them has the size and the offsets it always had.  Vertex
+    indices are global: meshes are concatenated and a mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
 
     def __init__(self, n_vertices: int, n_bsdfs: int = 0, device="cuda", mesh_slices: Optional[dict] = None, n_colors: int = 0,
-                 tex_shapes: Optional[Sequence[Tuple[int, int]]] = None):
+                 tex_shapes: Optional[Sequence[Tuple[int, int]]] = None, n_rigid: int = 0, cam_rotation: bool = False):
         self.V, self.B, self.C = int(n_vertices), int(n_bsdfs), int(n_colors)
         self.tex_shapes = [(int(h), int(w)) for h, w in (tex_shapes or [])]
         n0 = 6 * self.V + self.B + 3 + 3 * self.C
-        n = n0 + sum(3 * h * w for h, w in self.tex_shapes)
+        self.R, self.has_cam_rotation = int(n_rigid), bool(cam_rotation)
+        n1 = n0 + sum(3 * h * w for h, w in self.tex_shapes)
+        n = n1 + 6 * self.R + (3 if self.has_cam_rotation else 0)
         self.flat = torch.zeros(n, device=device, dtype=torch.float32)
         self.pos = self.flat[: 3 * self.V].view(self.V, 3)
         self.nrm = self.flat[3 * self.V: 6 * self.V].view(self.V, 3)
@@ -36,6 +42,8 @@ class ParamGrads:
         for h, w in self.tex_shapes:
             self._tex.append(self.flat[o: o + 3 * h * w].view(h, w, 3))
             o += 3 * h * w
+        self.rigid = self.flat[n1: n1 + 6 * self.R].view(self.R, 6) if self.R else None
+        self.cam_rotation = self.flat[n1 + 6 * self.R: n] if self.has_cam_rotation else None
         self.mesh_slices = dict(mesh_slices or {})
 
     def zero_(self):
@@ -48,7 +56,7 @@ class ParamGrads:
         s = getattr(self, "_scratch", None)
         if s is None:
             s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C,
-                                           tex_shapes=self.tex_shapes)
+                                           tex_shapes=self.tex_shapes, n_rigid=self.R, cam_rotation=self.has_cam_rotation)
         return s.zero_()
 
     def texture(self, slot: int) -> torch.Tensor:

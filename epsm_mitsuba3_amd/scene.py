@@ -726,6 +726,8 @@ class Scene:
         self.alpha_slots: Dict[int, int] = {}
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
         self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoint: ("bsdf" | "envmap", index)
+        self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
+        self._rigid_tables = {}                    # (ranges, pivots) -> their device tensors
         self.emitter_names = [f"emitter{i}" for i in range(len(self.emitter_desc))]     # (from_dict: the scene dict's keys)
         self.rr_depth = 5
         # test hook: tests/host_harness compiles the tracer's per-path code for the CPU and plugs
@@ -900,11 +902,65 @@ class Scene:
                                 dtype=torch.int32, device=self.device)
             self.tri_table[:, 3] = mode[self.tri_mesh.long()]
 
-    def attach_sensor(self, attached: bool = True):
+    def attach_sensor(self, attached: bool = True, rotation: bool = False):
         """``dr.enable_grad(params['sensor.to_world'])`` for its translation: ``prb_reparam``'s render_backward then leaves
         d loss / d (world-space position of the sensor) in ``ParamGrads.cam_origin`` (test_ad_integrators.py:639-674,
-        TranslateCameraConfig; EPSM/exp/bedroom.py:18-36 optimises the camera in the hybrid scheme)."""
+        TranslateCameraConfig; EPSM/exp/bedroom.py:18-36 optimises the camera in the hybrid scheme).  ``rotation``: its rotation too --
+        d loss / d omega of ``to_world <- Rot(omega) to_world`` about the sensor's own position (world axes, omega = 0) in
+        ``ParamGrads.cam_rotation``, what bedroom's angle chains through (exp/camera_pose.py)."""
         self.sensor_attached = bool(attached)
+        self.sensor_rotation = bool(attached and rotation)
+
+    def attach_rigid(self, mesh_name: str, pivot=None) -> int:
+        """The mesh as a rigid body (the reference's ``trafo @ initial_positions``): render_backward leaves d loss / d its twist --
+        a translation and a rotation about ``pivot``, world axes -- as [force, torque] in ``ParamGrads.rigid[slot]``
+        (``epsm_rigid_reduce`` over the mesh's rows of ``pos`` / ``nrm``, which it keeps).  Attaches the mesh's positions, and its
+        normals when it has vertex normals.  ``pivot``: default the mesh's current centroid; it stays where it is until
+        ``set_rigid_pivot``."""
+        if mesh_name not in self.mesh_slices:
+            raise ValueError(f"attach_rigid: no mesh named {mesh_name!r} in this scene")
+        slot = next((k for k, r in enumerate(self.rigid_slots) if r["mesh"] == mesh_name), None)
+        if slot is None:
+            self.rigid_slots.append({"mesh": mesh_name, "pivot": None})
+            slot = len(self.rigid_slots) - 1
+        if pivot is None and self.rigid_slots[slot]["pivot"] is None:
+            lo, hi = self.mesh_slices[mesh_name]
+            pivot = self.positions[lo:hi].double().mean(dim=0).cpu().tolist()
+        if pivot is not None:                                  # (attached before and no pivot given: the stored one stays)
+            self.set_rigid_pivot(slot, pivot)
+        m = self.mesh(mesh_name)
+        m.pos_attached, m.nrm_attached = True, bool(m.nrm_attached or m.has_normals)
+        self._refresh_attach_flags()
+        return slot
+
+    def set_rigid_pivot(self, slot: int, c) -> None:
+        c = [float(x) for x in (c.detach().cpu().tolist() if torch.is_tensor(c) else np.asarray(c, float).reshape(-1))]
+        if len(c) != 3:
+            raise ValueError("set_rigid_pivot: a pivot is three numbers")
+        self.rigid_slots[slot]["pivot"] = c
+
+    def rigid_tables(self, extra=()):
+        """(ranges (n,2) int64, pivots (n,3) float32) on the device for the rigid slots followed by ``extra`` = ((lo, hi, pivot), ...)
+        -- the sensor's slot over every vertex.  Uploaded once per distinct table."""
+        rows = [(*self.mesh_slices[r["mesh"]], tuple(r["pivot"])) for r in self.rigid_slots] + [(int(lo), int(hi), tuple(float(x) for x in c)) for lo, hi, c in extra]
+        key = tuple(rows)
+        t = self._rigid_tables.get(key)
+        if t is None:
+            if len(self._rigid_tables) >= 8:
+                self._rigid_tables.pop(next(iter(self._rigid_tables)))
+            t = self._rigid_tables[key] = (torch.tensor([[lo, hi] for lo, hi, _ in rows], dtype=torch.int64).reshape(-1, 2).to(self.device),
+                                           torch.tensor([list(c) for _, _, c in rows], dtype=torch.float32).reshape(-1, 3).to(self.device))
+        return t
+
+    def rigid_reduce(self, g_pos, g_nrm, out, ranges, pivots) -> None:
+        """``out (n,6) += [F, T]`` of the slots over the gradient rows (``epsm_rigid_reduce``; rigid.reduce)."""
+        from . import rigid
+        rigid.reduce(self.positions, self.normals, g_pos, g_nrm, ranges, pivots, out, host=self._backend is not None)
+
+    def rigid_expand(self, twists, d_pos, d_nrm, ranges, pivots) -> None:
+        """``d_pos`` / ``d_nrm`` += the vertex motion under the slots' twists (``epsm_rigid_expand``; rigid.expand)."""
+        from . import rigid
+        rigid.expand(self.positions, self.normals, ranges, pivots, twists, d_pos, d_nrm, host=self._backend is not None)
 
     def has_attached_geometry(self) -> bool:
         """Any mesh whose vertex positions / normals receive gradients?"""
@@ -1138,7 +1194,8 @@ class Scene:
 
     def param_grads(self) -> ParamGrads:
         return ParamGrads(self.V, len(self.alpha_slots), device=self.device, mesh_slices=self.mesh_slices,
-                          n_colors=len(self.color_slots), tex_shapes=self.texture_shapes())
+                          n_colors=len(self.color_slots), tex_shapes=self.texture_shapes(), n_rigid=len(self.rigid_slots),
+                          cam_rotation=bool(getattr(self, "sensor_rotation", False)))
 
     # -- upload ----------------------------------------------------------------------------------
     def _upload(self):

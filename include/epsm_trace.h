@@ -547,6 +547,31 @@ size_t epsm_environment_tables_bytes(int32_t width, int32_t height);
 int epsm_environment_tables(const float *bitmap, int32_t width, int32_t height, float *texels, float *row_cdf, float *col_cdf,
                             float *cell_pdf, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Rigid motions of vertex ranges (csrc/epsm_trace_rigid.hip): what the reference's experiments optimise -- `trafo @
+ * initial_positions` of an object, the sensor's pose -- as a reduction of the per-vertex gradient rows the passes produce, and its
+ * transpose.  A slot s is a vertex range [ranges[2 s], ranges[2 s + 1]) (clipped to 0 .. V by the kernels; ranges may overlap or be
+ * empty) and a pivot pivots[3 s ..]; its twist is a translation dt and a rotation dw about the pivot, world axes.  Both entries
+ * run on `stream` with no host synchronisation and no allocation.  ranges (n_slots, 2) i64, pivots (n_slots, 3) f32, positions /
+ * normals / g_* / d_* (V, 3) f32: device.  EPSM_EINVAL (with epsm_last_error()) for a NULL pointer, V outside 0 .. 2^31 - 1,
+ * n_slots outside 0 .. 65535, n_slots ceil(V / 1024) above 2^23 (the reduce's first launch is a grid of that many workgroups) or a
+ * workspace that is too small or misaligned -- checked before anything touches the device.
+ *
+ * epsm_rigid_reduce -- out (n_slots, 6) += [F, T] per slot: force F = sum_v g_pos[v], torque T = sum_v (x_v - c) x g_pos[v] +
+ *   n_v x g_nrm[v] (a rotation turns the stored vertex normals too; g_nrm NULL: no normal term, normals is not read).  float64
+ *   sums, no atomics, a fixed order: a first launch writes one row of six doubles per (slot, chunk of 1024 vertices), a second adds
+ *   a slot's rows and ADDS the result to out in float32.  Two calls on the same input add the same bits.
+ *   workspace: device, 16-byte aligned, >= epsm_rigid_workspace_bytes(V, n_slots) = 48 n_slots ceil(V / 1024) bytes.
+ * epsm_rigid_expand -- the transpose: d_pos[v] += dt + dw x (x_v - c), d_nrm[v] += dw x n_v for every slot that contains v, in
+ *   slot order; twists (n_slots, 6) f32 = [dt, dw].  d_nrm NULL: positions only.  Vertices in no slot are not written.
+ * ------------------------------------------------------------------------- */
+size_t epsm_rigid_workspace_bytes(int64_t V, int32_t n_slots);
+int epsm_rigid_reduce(const float *positions, const float *normals, const float *g_pos, const float *g_nrm, int64_t V,
+                      const int64_t *ranges, const float *pivots, int32_t n_slots, float *out, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int epsm_rigid_expand(const float *positions, const float *normals, int64_t V, const int64_t *ranges, const float *pivots,
+                      const float *twists, int32_t n_slots, float *d_pos, float *d_nrm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
