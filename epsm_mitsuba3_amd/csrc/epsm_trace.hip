@@ -3,7 +3,7 @@
 #include <string.h>
 
 #include "epsm_common.h"
-#include "epsm_trace_core.h"
+#include "epsm_trace_replay.h"
 #include "epsm_trace_wavefront.h"
 #include "epsm_trace_packet.h"
 #include "epsm_wave_scatter.h"           // wave_total_lane63 (DPP sums): the first-hit stage
@@ -18,24 +18,22 @@ namespace {
 __global__ __launch_bounds__(128, 4) void epsm_trace_kernel(TraceArgs A) {
     // traversal stacks: one LDS column of 32 entries per path (16 KB: four waves per SIMD); the four-wide tree may push
     // 3 x 16 references: the rare entries beyond 32 go to a private array (scratch)
-    constexpr int kLds = 32;
-    __shared__ uint32_t s_stack[kLds * 128];
-    uint32_t deep[kBvhStack - kLds];
+    __shared__ uint32_t s_stack[kLaneStackLds * 128];
+    uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * 128 + threadIdx.x;
-    BvhStack st{s_stack + threadIdx.x, 128};
-    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
+    const BvhStack st = lane_stack(s_stack, deep, 128);
     // trace_one_path with the PRIMARY rays walked by the wave (epsm_trace_packet.h: the lanes of a wave are the samples of one
     // pixel or of a few neighbours); the packet's LDS column is entry 0 of the wave's own per-lane stacks, not yet in use
     const bool has = i < A.N;
     if (__ballot(has) == 0ull) return;
-    PathState s = path_begin(A, has ? i : A.N - 1, has);
-    const TriHit th0 = packet_intersect(A.S, s.ray, has, s_stack + (threadIdx.x & ~63));
+    PrimaryHit p = primary_hit(A, i, has, true, s_stack);
     if (!has) return;
+    PathState &s = p.s;
     InlineVis vis{st};
     const int max_depth = path_max_depth(A);
     for (int iteration = 0; iteration < max_depth; ++iteration) {
         TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
-        if (iteration == 0) th = th0;
+        if (iteration == 0) th = p.th0;
         else if (s.active) th = intersect<false>(A.S, s.ray, st);
         path_bounce(A, i, iteration, s, th, vis);
     }
@@ -566,22 +564,15 @@ __global__ __launch_bounds__(256) void epsm_film_develop_kernel(int64_t n, const
 
 }  // namespace
 
-// Validates the arguments of the two tracer entry points and fills the kernel argument block.
+// Validates the arguments of the tracer entry points and fills the kernel argument block (the common prefix: replay_args_fill).
 static int fill_trace_args(TraceArgs &A, const char *who, const EpsmScene *scene, const EpsmSensor *sensor,
                            uint32_t seed, int spp, int max_depth, int rr_depth, int64_t path_offset, int64_t N, int K_log,
                            float *ray_o, float *ray_d, float *ray_dx, float *ray_dy, float *film_pos, float *radiance,
                            uint8_t *valid, const EpsmRecordOut *recs, uint32_t flags) {
-    char msg[200];
-    auto bad = [&](const char *what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fail(EPSM_EINVAL, msg); };
-    if (!scene || !sensor) return bad("NULL scene / sensor");
-    if (N < 0 || spp < 1 || max_depth < 1 || rr_depth < 1 || path_offset < 0)
-        return bad("bad N / spp / max_depth / rr_depth / path_offset");
+    auto bad = [&](const char *what) { return fail(EPSM_EINVAL, who, what); };
+    if (const char *why = replay_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return bad(why);
     if (K_log < 0 || K_log > EPSM_MAX_VERTICES || K_log > (max_depth < 6 ? max_depth : 6))
         return bad("K_log must be <= min(max_depth, 5)");
-    if (sensor->border < 0 || sensor->border > 8) return bad("bad sensor border");
-    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
-        path_offset + N > 0xFFFFFFFFLL)
-        return bad("path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32, common.py:468-475)");
     const bool packed = (flags & EPSM_TRACE_PACKED_LOG) != 0;
     if (!ray_o || (!packed && (!ray_d || !ray_dx || !ray_dy)) || (K_log > 0 && !recs)) return bad("NULL output");
     if (packed && ((((uintptr_t) ray_o) & 15) || (K_log > 0 && (!recs[0].packed || !recs[0].pflags || (((uintptr_t) recs[0].packed) & 15)))))
@@ -591,10 +582,6 @@ static int fill_trace_args(TraceArgs &A, const char *who, const EpsmScene *scene
         if (rs < 0 || ps < 0 || (rs & 3) || (ps & 3) || (rs && rs < 12) || (ps && ps < (int64_t) K_log * 32))
             return bad("EpsmRecordOut.ray_stride / packed_stride must be 0 or multiples of 4 words >= 12 / 32 K_log");
     }
-    if (scene->n_triangles > 0 && (!scene->positions || !scene->normals || !scene->tri || !scene->tri_mesh ||
-                                   !scene->meshes || !scene->bsdfs || !scene->bvh || !scene->prim_index || !scene->tri_verts))
-        return bad("NULL scene array");
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return bad(why);
     if (flags & ~(uint32_t) (EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | EPSM_TRACE_GRADIENT_ONLY | EPSM_TRACE_GRADIENT_CAUSTIC | EPSM_TRACE_NO_TAIL |
                              EPSM_TRACE_FUSE_FIRST_HIT))
         return bad("unknown flag");
@@ -610,11 +597,7 @@ static int fill_trace_args(TraceArgs &A, const char *who, const EpsmScene *scene
     }
     if ((flags & EPSM_TRACE_GRADIENT_CAUSTIC) && !(flags & EPSM_TRACE_GRADIENT_ONLY)) return bad("EPSM_TRACE_GRADIENT_CAUSTIC modifies EPSM_TRACE_GRADIENT_ONLY");
     if ((flags & EPSM_TRACE_GRADIENT_ONLY) && K_log < 1) return bad("EPSM_TRACE_GRADIENT_ONLY needs a vertex log (K_log >= 1)");
-    memset(&A, 0, sizeof(A));
-    A.flags = flags;
-    A.S = *scene; A.C = *sensor;
-    A.seed = seed; A.spp = spp; A.max_depth = max_depth; A.rr_depth = rr_depth; A.K_log = K_log;
-    A.path_offset = path_offset; A.N = N;
+    A.flags = flags; A.K_log = K_log;
     A.ray_o = ray_o; A.ray_d = ray_d; A.ray_dx = ray_dx; A.ray_dy = ray_dy;
     A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
     for (int k = 0; k < K_log; ++k) {

@@ -16,7 +16,7 @@
 // Plain C++, compiled by hipcc for gfx950 and by g++ for the host harness (tests/host_harness/trace_bsdf_host.cpp).
 #pragma once
 
-#include "epsm_trace_core.h"
+#include "epsm_trace_replay.h"
 
 namespace epsm {
 namespace ba {
@@ -35,8 +35,6 @@ struct BsdfArgs {
 };
 
 struct Item { int slot; F3 coef; };               // slot < 0: nothing
-EPSM_HD float finite_or_zero(float x) { return fabsf(x) < __builtin_inff() ? x : 0.f; }
-EPSM_HD F3 finite_or_zero3(F3 v) { return f3(finite_or_zero(v.x), finite_or_zero(v.y), finite_or_zero(v.z)); }
 
 // What one bounce of a path contributes: `a` the indirect term, `b` the emitter sample.  Shown the loop state before the bounce's
 // update (epsm_trace_core.h, observe_state).
@@ -72,24 +70,12 @@ struct AlphaObserver {
     }
 };
 
-// The replay of path i after its primary ray's closest hit th0 (the device walks those as a packet, the host one by one);
-// sink.item(it) after every bounce for both items, sink.finish() at the end.
+// The replay of path i (epsm_trace_replay.h) under an AlphaObserver.
 template <class Sink>
 EPSM_HD void bsdf_replay(const BsdfArgs &T, int64_t i, bool has, PathState &s, const TriHit &th0, const BvhStack &st, Sink &sink) {
-    InlineVis vis{st};
     AlphaObserver obs{T, has, has ? ld3(T.radiance + 3 * i) : zero3<float>()};
     obs.a.slot = obs.b.slot = -1; obs.a.coef = obs.b.coef = obs.L = zero3<float>();
-    if (!has) s.active = false;
-    const int max_depth = path_max_depth(T.A);
-    for (int iteration = 0; iteration < max_depth; ++iteration) {
-        TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
-        if (iteration == 0) th = th0;
-        else if (s.active) th = intersect<false>(T.A.S, s.ray, st);
-        path_bounce(T.A, i, iteration, s, th, vis, obs);
-        sink.item(obs.a);
-        sink.item(obs.b);
-    }
-    sink.finish();
+    replay_path(T.A, i, has, s, th0, st, obs, sink);
 }
 
 // Backward, per path: sum over its items of adj . coef, per slot (registers: the slot is matched, never used as an index).
@@ -116,21 +102,17 @@ struct TangentSink {
 inline int64_t partial_rows(int64_t N) { return (N + kBlock - 1) / kBlock; }
 inline size_t workspace_bytes(int64_t N) { return N > 0 ? (size_t) partial_rows(N) * kMaxSlots * sizeof(float) : 0; }
 
-// The arguments of both entry points (host side; device and host builds alike): NULL = fine, otherwise what is wrong.
+// The arguments of both entry points (host side; device and host builds alike): the common eight through replay_args_fill, then
+// this pass's own.  NULL = fine, otherwise what is wrong; at N == 0 fine with nothing else looked at (T.A.N = 0: the caller has
+// nothing to do).
 inline const char *bsdf_args_fill(BsdfArgs &T, const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
                                   int rr_depth, int64_t path_offset, int64_t N, const float *radiance, int B) {
     memset(&T, 0, sizeof(T));
-    if (!scene || !sensor || N < 0 || path_offset < 0 || spp < 1 || max_depth < 0) return "bad scene / sensor / N / spp / max_depth";
-    if (N > 0 && !radiance) return "NULL radiance";
-    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
-        path_offset + N > 0xFFFFFFFFLL)
-        return "path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32)";
-    if (scene->n_textures < 0 || (scene->n_textures > 0 && !scene->textures)) return "NULL textures";
+    if (const char *why = replay_args_fill(T.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 0)) return why;
+    if (N == 0) return nullptr;
+    if (!radiance) return "NULL radiance";
     if (B < 0) return "negative number of alpha slots";
     if (B > kMaxSlots) return "more than EPSM_MAX_ALPHA_GRADS alpha slots";
-    T.A.S = *scene; T.A.C = *sensor;
-    T.A.seed = seed; T.A.spp = spp; T.A.max_depth = max_depth; T.A.rr_depth = rr_depth; T.A.K_log = 0;
-    T.A.path_offset = path_offset; T.A.N = N;
     T.radiance = radiance;
     T.n_slots = B;
     return nullptr;

@@ -31,22 +31,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 // workgroup; epsm_bsdf_sum_kernel adds the rows up.
 template <bool BACKWARD>
 __global__ __launch_bounds__(128, 2) void epsm_bsdf_kernel(ba::BsdfArgs T) {
-    constexpr int kLds = 32;
-    __shared__ uint32_t s_stack[kLds * 128];
+    __shared__ uint32_t s_stack[kLaneStackLds * 128];
     __shared__ float s_part[2][ba::kMaxSlots];
-    uint32_t deep[kBvhStack - kLds];
+    uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * 128 + threadIdx.x;
-    BvhStack st{s_stack + threadIdx.x, 128};
-    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
-    const bool has = i < T.A.N;
-    const int64_t ii = has ? i : T.A.N - 1;
-    PathState s = path_begin(T.A, ii, false);
-    const TriHit th0 = packet_intersect(T.A.S, s.ray, has, s_stack + (threadIdx.x & ~63));
+    const BvhStack st = lane_stack(s_stack, deep, 128);
+    PrimaryHit p = primary_hit(T.A, i, false, s_stack);           // (no early exit: an idle wave still owes the reduction its zeros)
     if (BACKWARD) {
         BackwardSink sink;
-        sink.sums.adj = has ? ld3(T.adj + 3 * i) : zero3<float>();
+        sink.sums.adj = p.has ? ld3(T.adj + 3 * i) : zero3<float>();
         sink.sums.clear();
-        ba::bsdf_replay(T, ii, has, s, th0, st, sink);
+        ba::bsdf_replay(T, p.i, p.has, p.s, p.th0, st, sink);
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
         for (int k = 0; k < ba::kMaxSlots; ++k) {
@@ -57,8 +52,8 @@ __global__ __launch_bounds__(128, 2) void epsm_bsdf_kernel(ba::BsdfArgs T) {
         if (threadIdx.x < ba::kMaxSlots)
             T.partial[(int64_t) blockIdx.x * ba::kMaxSlots + threadIdx.x] = s_part[0][threadIdx.x] + s_part[1][threadIdx.x];
     } else {
-        ba::TangentSink sink{T, ii, has, zero3<float>()};
-        ba::bsdf_replay(T, ii, has, s, th0, st, sink);
+        ba::TangentSink sink{T, p.i, p.has, zero3<float>()};
+        ba::bsdf_replay(T, p.i, p.has, p.s, p.th0, st, sink);
     }
 }
 
@@ -91,10 +86,10 @@ extern "C" int epsm_trace_paths_bsdf_backward(const EpsmScene *scene, const Epsm
     ba::BsdfArgs T;
     if (const char *why = ba::bsdf_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, B))
         return fail(EPSM_EINVAL, what, why);
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return fail(EPSM_EINVAL, what, why);
-    if (N > 0 && !adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
+    if (N == 0) return EPSM_OK;
+    if (!adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
     if (B > 0 && !grad_alpha) return fail(EPSM_EINVAL, what, "NULL grad_alpha");
-    if (N == 0 || B == 0) return EPSM_OK;
+    if (B == 0) return EPSM_OK;
     if (!workspace || workspace_bytes < ba::workspace_bytes(N) || ((uintptr_t) workspace & 15u))
         return fail(EPSM_EINVAL, what, "workspace NULL, misaligned or smaller than epsm_trace_bsdf_workspace_bytes(N)");
     T.adj = adj_radiance; T.partial = (float *) workspace;
@@ -117,10 +112,9 @@ extern "C" int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmS
     ba::BsdfArgs T;
     if (const char *why = ba::bsdf_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, B))
         return fail(EPSM_EINVAL, what, why);
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return fail(EPSM_EINVAL, what, why);
-    if (N > 0 && !d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
-    if (B > 0 && !tangent_alpha) return fail(EPSM_EINVAL, what, "NULL tangent_alpha");
     if (N == 0) return EPSM_OK;
+    if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
+    if (B > 0 && !tangent_alpha) return fail(EPSM_EINVAL, what, "NULL tangent_alpha");
     T.tangent = tangent_alpha; T.d_radiance = d_radiance;
     hipLaunchKernelGGL(epsm_bsdf_kernel<false>, dim3((unsigned) ba::partial_rows(N)), dim3(128), 0, (hipStream_t) stream, T);
     const hipError_t e = hipGetLastError();

@@ -102,4 +102,32 @@ __device__ __forceinline__ TriHit packet_intersect(const EpsmScene &S, const Ray
     return best;
 }
 
+// ---- the prologue of the kernels that carry one path per lane (the tracer, the replays of its derivative passes) ----
+// The lane's traversal stack: column threadIdx.x of the workgroup's LDS block `s_stack` (kLaneStackLds entries per lane, `threads`
+// columns); the four-wide tree may push 3 x 16 references, the rare entries beyond go to the private array `deep`
+// (kBvhStack - kLaneStackLds words: scratch).
+constexpr int kLaneStackLds = 32;
+__device__ __forceinline__ BvhStack lane_stack(uint32_t *s_stack, uint32_t *deep, int threads) {
+    BvhStack st{s_stack + threadIdx.x, threads};
+    st.cap = kLaneStackLds; st.ovf = deep; st.ovf_stride = 1;
+    return st;
+}
+// The primary ray of lane i, walked by the wave: all 64 lanes call it.  `has` = i < A.N: the lane carries a path (the kernel's to
+// compute: its early-exit rule is a ballot of it); a lane past N rides along on path N - 1 (`i` is that clamped index) and logs nothing.  The packet's LDS column is entry 0 of the wave's own per-lane
+// stacks in `s_stack` (lane_stack), not yet in use.
+struct PrimaryHit { bool has; int64_t i; PathState s; TriHit th0; };
+__device__ __forceinline__ PrimaryHit primary_hit(const TraceArgs &A, int64_t i, bool has, bool log, uint32_t *s_stack) {
+    PrimaryHit p;
+    p.has = has;
+    p.i = p.has ? i : A.N - 1;
+    p.s = path_begin(A, p.i, log && p.has);
+    p.th0 = packet_intersect(A.S, p.s.ray, p.has, s_stack + (threadIdx.x & ~63));
+    return p;
+}
+// (for a kernel without an early exit; register allocation follows where `has` is formed: 208 -> 210 registers in
+// epsm_bsdf_kernel<false> with it formed in the kernel, 220 -> 218 in epsm_texture_kernel<false> with it formed here)
+__device__ __forceinline__ PrimaryHit primary_hit(const TraceArgs &A, int64_t i, bool log, uint32_t *s_stack) {
+    return primary_hit(A, i, i < A.N, log, s_stack);
+}
+
 }  // namespace epsm

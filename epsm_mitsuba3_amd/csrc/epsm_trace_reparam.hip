@@ -2,9 +2,11 @@
 // (include/epsm_trace.h, epsm_trace_paths_reparam / epsm_trace_paths_reparam_forward; per-path code: epsm_trace_reparam.h).
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "epsm_common.h"
 #include "epsm_trace_reparam.h"
+#include "epsm_trace_replay.h"
 #include "epsm_trace_packet.h"
 
 using namespace epsm;
@@ -22,12 +24,10 @@ namespace {
 // its warps are left as requests.  (First version, auxiliary rays traced by the same lane: 182 ms per render_backward
 // at 4.26 M paths / 128 k triangles / 16 rays with one wave per SIMD, 99 ms with four.)
 __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_path_kernel(rp::ReparamArgs R, rp::WarpReq *req, int *count) {
-    constexpr int kLds = 32;
-    __shared__ uint32_t s_stack[kLds * EPSM_RP_THREADS];
-    uint32_t deep[kBvhStack - kLds];
+    __shared__ uint32_t s_stack[kLaneStackLds * EPSM_RP_THREADS];
+    uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * EPSM_RP_THREADS + threadIdx.x;
-    BvhStack st{s_stack + threadIdx.x, EPSM_RP_THREADS};
-    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
+    const BvhStack st = lane_stack(s_stack, deep, EPSM_RP_THREADS);
     if (i >= R.A.N) return;
     rp::QueueSink sink{req, R.A.N, i, 0};
     // (the camera rays of a wave walked together first, as the tracers do: 41.6 -> 42.3 ms per call; not kept)
@@ -43,13 +43,29 @@ __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_pat
 // through the list 256 / G requests at a time.  (Round 3 launched one group per (n, path) slot and let the empty ones leave:
 // 29 % of the slots exist -- 2.06 requests per path of 7 at max_depth 3 -- and the waves that held any were 75 % full.)
 // Z, dZ and the origin's adjoint are reduced over the group with xor shuffles.
-template <int G>
-__global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs R, const rp::WarpReq *req, const int *count, int n_max) {
-    constexpr int kPaths = 256, kGroups = 256 / G;
-    __shared__ uint32_t s_pstack[kPacketStack * 4];                        // one column per wave (epsm_trace_packet.h)
-    __shared__ uint16_t s_list[kPaths * rp::kMaxReq];                      // (n << 8) | path of the block
-    __shared__ int s_off[rp::kMaxReq * 4 + 1];
-    const int64_t N = R.A.N, p0 = (int64_t) blockIdx.x * kPaths;
+struct WarpLds {
+    uint32_t pstack[kPacketStack * 4];                                     // one column per wave (epsm_trace_packet.h)
+    uint16_t list[256 * rp::kMaxReq];                                      // (n << 8) | path of the block
+    int off[rp::kMaxReq * 4 + 1];
+};
+// One request as its group of G lanes holds it once the auxiliary rays are walked: lane r's ray `A` (mine: the lane has one),
+// Z and dZ summed over the group.
+struct WarpGroup {
+    bool live, mine;                   // the group has a request; this lane one of its rays
+    int r, n;                          // lane of the group; the request is call n ...
+    int64_t i;                         // ... of path i
+    rp::WarpReq q;
+    F3 d;
+    rp::Aux A;
+    float iZ; F3 dZ;
+};
+// What both stage-2 kernels do with a workgroup's requests before they part ways: list them, then, 256 / G at a time, draw each
+// lane's auxiliary ray, walk the wave's rays together and reduce Z, dZ; body(g) is the backward or the forward tail.
+template <int G, class Args, class Body>
+__device__ __forceinline__ void for_each_warp_group(const Args &R, const rp::WarpReq *req, const int *count, int n_max, WarpLds &lds,
+                                                    Body body) {
+    constexpr int kGroups = 256 / G;
+    const int64_t N = R.A.N, p0 = (int64_t) blockIdx.x * 256;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     int c = p0 + tid < N ? count[p0 + tid] : 0;
     c = c < n_max ? c : n_max;
@@ -58,45 +74,61 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
     for (int n = 0; n < rp::kMaxReq; ++n) {
         const unsigned long long m = __ballot(c > n);
         rank[n] = __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u));
-        if (lane == 0) s_off[n * 4 + wv] = __popcll(m);
+        if (lane == 0) lds.off[n * 4 + wv] = __popcll(m);
     }
     __syncthreads();
     if (tid == 0) {
         int run = 0;
-        for (int e = 0; e < rp::kMaxReq * 4; ++e) { const int v = s_off[e]; s_off[e] = run; run += v; }
-        s_off[rp::kMaxReq * 4] = run;
+        for (int e = 0; e < rp::kMaxReq * 4; ++e) { const int v = lds.off[e]; lds.off[e] = run; run += v; }
+        lds.off[rp::kMaxReq * 4] = run;
     }
     __syncthreads();
 #pragma unroll
     for (int n = 0; n < rp::kMaxReq; ++n)
-        if (c > n) s_list[s_off[n * 4 + wv] + rank[n]] = (uint16_t) ((n << 8) | tid);
+        if (c > n) lds.list[lds.off[n * 4 + wv] + rank[n]] = (uint16_t) ((n << 8) | tid);
     __syncthreads();
-    const int total = s_off[rp::kMaxReq * 4];
-    const int r = tid % G;
+    const int total = lds.off[rp::kMaxReq * 4];
+    WarpGroup g;
+    g.r = tid % G;
     for (int b0 = 0; b0 < total; b0 += kGroups) {                          // (uniform over the workgroup: the wave walks its rays together)
         const int b = b0 + tid / G;
-        const bool live = b < total;
-        const int e = s_list[live ? b : 0], n = e >> 8;
-        const int64_t i = p0 + (e & 255);
-        const rp::WarpReq q = req[(int64_t) n * N + i];
-        const F3 o = f3(q.o[0], q.o[1], q.o[2]), d = f3(q.d[0], q.d[1], q.d[2]), g_dir = f3(q.gdir[0], q.gdir[1], q.gdir[2]);
+        g.live = b < total;
+        const int e = lds.list[g.live ? b : 0];
+        g.n = e >> 8;
+        g.i = p0 + (e & 255);
+        g.q = req[(int64_t) g.n * N + g.i];
+        const F3 o = f3(g.q.o[0], g.q.o[1], g.q.o[2]);
+        g.d = f3(g.q.d[0], g.q.d[1], g.q.d[2]);
         F3 fs, ft;
-        coordinate_system(d, fs, ft);
-        rp::Aux A;
-        A.w = 0.f; A.dw = zero3<float>(); A.v = d; A.tri = kNoIndex; A.b1 = A.b2 = A.inv_dist = 0.f;
-        const bool mine = live && r < R.cfg.rays;
+        coordinate_system(g.d, fs, ft);
+        g.A.w = 0.f; g.A.dw = zero3<float>(); g.A.v = g.d; g.A.tri = kNoIndex; g.A.b1 = g.A.b2 = g.A.inv_dist = 0.f;
+        g.mine = g.live && g.r < R.cfg.rays;
         // the rays of a request leave one point within a fraction of a degree, the requests of a wave are the same call of
         // neighbouring paths: the wave walks the tree once for all of them
-        rp::AuxDraw D; D.ray.o = o; D.ray.d = d; D.ray.maxt = 0.f; D.tangent = zero3<float>(); D.sy_ = 0.f;
-        if (mine) D = rp::aux_begin(R.cfg, rp::WarpId{0xffffffffu ^ R.A.seed, (uint32_t) (R.A.path_offset + i), n}, r, o, d, fs, ft);
-        const TriHit ath = packet_intersect(R.A.S, D.ray, mine, s_pstack + wv * kPacketStack);
-        if (mine) A = rp::aux_finish(R.A.S, R.cfg, D, ath, o, d);
-        float Z = A.w; F3 dZ = A.dw;
+        rp::AuxDraw D; D.ray.o = o; D.ray.d = g.d; D.ray.maxt = 0.f; D.tangent = zero3<float>(); D.sy_ = 0.f;
+        if (g.mine) D = rp::aux_begin(R.cfg, rp::WarpId{0xffffffffu ^ R.A.seed, (uint32_t) (R.A.path_offset + g.i), g.n}, g.r, o, g.d, fs, ft);
+        const TriHit ath = packet_intersect(R.A.S, D.ray, g.mine, lds.pstack + wv * kPacketStack);
+        if (g.mine) g.A = rp::aux_finish(R.A.S, R.cfg, D, ath, o, g.d);
+        float Z = g.A.w;
+        g.dZ = g.A.dw;
 #pragma unroll
-        for (int m = 1; m < G; m <<= 1) { Z += __shfl_xor(Z, m); dZ.x += __shfl_xor(dZ.x, m); dZ.y += __shfl_xor(dZ.y, m); dZ.z += __shfl_xor(dZ.z, m); }
+        for (int m = 1; m < G; m <<= 1) { Z += __shfl_xor(Z, m); g.dZ.x += __shfl_xor(g.dZ.x, m); g.dZ.y += __shfl_xor(g.dZ.y, m); g.dZ.z += __shfl_xor(g.dZ.z, m); }
+        g.iZ = 1.f / fmaxf(Z, 1e-8f);
+        body(g);
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs R, const rp::WarpReq *req, const int *count, int n_max) {
+    __shared__ WarpLds lds;
+    for_each_warp_group<G>(R, req, count, n_max, lds, [&](const WarpGroup &g) {
+        const rp::WarpReq &q = g.q;
+        const rp::Aux &A = g.A;
+        const F3 d = g.d, dZ = g.dZ, g_dir = f3(q.gdir[0], q.gdir[1], q.gdir[2]);
+        const float iZ = g.iZ;
+        const bool live = g.live, mine = g.mine;
+        const int r = g.r;
         // the adjoint of reparam.py:269-327 at V = 0 (warp_backward, one auxiliary ray per lane)
-        Z = fmaxf(Z, 1e-8f);
-        const float iZ = 1.f / Z;
         const F3 g_V = (g_dir - d * dot(d, g_dir)) * iZ - dZ * (q.gdiv * iZ * iZ);
         const F3 g_v = mine ? g_V * A.w + A.dw * (q.gdiv * iZ) : zero3<float>();
         F3 g_o = zero3<float>(), g_d = zero3<float>(), g_p = zero3<float>();
@@ -141,7 +173,7 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
             if (q.em_inv_dist != 0.f) g_o = g_o - (g_d - d * dot(d, g_d)) * q.em_inv_dist;
             rp::add_follow_point(R.A.S, R.G, q.ftri, q.fb1, q.fb2, g_o);
         }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -151,12 +183,10 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
 // (ReadSink) reads each request's tangents back, does the dual evaluations and writes the path's d_radiance / d_film.
 template <class Sink>
 __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_fwd_path_kernel(rp::ReparamFwdArgs R, rp::WarpReq *req, int *count) {
-    constexpr int kLds = 32;
-    __shared__ uint32_t s_stack[kLds * EPSM_RP_THREADS];
-    uint32_t deep[kBvhStack - kLds];
+    __shared__ uint32_t s_stack[kLaneStackLds * EPSM_RP_THREADS];
+    uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * EPSM_RP_THREADS + threadIdx.x;
-    BvhStack st{s_stack + threadIdx.x, EPSM_RP_THREADS};
-    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
+    const BvhStack st = lane_stack(s_stack, deep, EPSM_RP_THREADS);
     if (i >= R.A.N) return;
     Sink sink{req, R.A.N, i, 0};
     rp::reparam_forward_one_path(R, i, st, sink);
@@ -168,77 +198,60 @@ __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_fwd
 // sum w_i v_i', sum (dw_i - w_i dZ / Z) . v_i' (warp_forward); lane 0 writes d' and div' into the request's gdir / gdiv.
 template <int G>
 __global__ __launch_bounds__(256) void epsm_reparam_fwd_warp_kernel(rp::ReparamFwdArgs R, rp::WarpReq *req, const int *count, int n_max) {
-    constexpr int kPaths = 256, kGroups = 256 / G;
-    __shared__ uint32_t s_pstack[kPacketStack * 4];
-    __shared__ uint16_t s_list[kPaths * rp::kMaxReq];
-    __shared__ int s_off[rp::kMaxReq * 4 + 1];
-    const int64_t N = R.A.N, p0 = (int64_t) blockIdx.x * kPaths;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    int c = p0 + tid < N ? count[p0 + tid] : 0;
-    c = c < n_max ? c : n_max;
-    int rank[rp::kMaxReq];
-#pragma unroll
-    for (int n = 0; n < rp::kMaxReq; ++n) {
-        const unsigned long long m = __ballot(c > n);
-        rank[n] = __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u));
-        if (lane == 0) s_off[n * 4 + wv] = __popcll(m);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int e = 0; e < rp::kMaxReq * 4; ++e) { const int v = s_off[e]; s_off[e] = run; run += v; }
-        s_off[rp::kMaxReq * 4] = run;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < rp::kMaxReq; ++n)
-        if (c > n) s_list[s_off[n * 4 + wv] + rank[n]] = (uint16_t) ((n << 8) | tid);
-    __syncthreads();
-    const int total = s_off[rp::kMaxReq * 4];
-    const int r = tid % G;
-    for (int b0 = 0; b0 < total; b0 += kGroups) {
-        const int b = b0 + tid / G;
-        const bool live = b < total;
-        const int e = s_list[live ? b : 0], n = e >> 8;
-        const int64_t i = p0 + (e & 255);
-        const rp::WarpReq q = req[(int64_t) n * N + i];
-        const F3 o = f3(q.o[0], q.o[1], q.o[2]), d = f3(q.d[0], q.d[1], q.d[2]);
-        F3 fs, ft;
-        coordinate_system(d, fs, ft);
-        rp::Aux A;
-        A.w = 0.f; A.dw = zero3<float>(); A.v = d; A.tri = kNoIndex; A.b1 = A.b2 = A.inv_dist = 0.f;
-        const bool mine = live && r < R.cfg.rays;
-        rp::AuxDraw D; D.ray.o = o; D.ray.d = d; D.ray.maxt = 0.f; D.tangent = zero3<float>(); D.sy_ = 0.f;
-        if (mine) D = rp::aux_begin(R.cfg, rp::WarpId{0xffffffffu ^ R.A.seed, (uint32_t) (R.A.path_offset + i), n}, r, o, d, fs, ft);
-        const TriHit ath = packet_intersect(R.A.S, D.ray, mine, s_pstack + wv * kPacketStack);
-        if (mine) A = rp::aux_finish(R.A.S, R.cfg, D, ath, o, d);
-        float Z = A.w; F3 dZ = A.dw;
-#pragma unroll
-        for (int m = 1; m < G; m <<= 1) { Z += __shfl_xor(Z, m); dZ.x += __shfl_xor(dZ.x, m); dZ.y += __shfl_xor(dZ.y, m); dZ.z += __shfl_xor(dZ.z, m); }
-        Z = fmaxf(Z, 1e-8f);
-        const float iZ = 1.f / Z;
+    __shared__ WarpLds lds;
+    for_each_warp_group<G>(R, req, count, n_max, lds, [&](const WarpGroup &g) {
+        const rp::WarpReq &q = g.q;
+        const F3 d = g.d;
         F3 wv3 = zero3<float>();
         float dv = 0.f;
-        if (mine) {
+        if (g.mine) {
             const F3 t_o = q.ftri != kNoIndex ? rp::follow_tangent(R.A.S, R.T, q.ftri, q.fb1, q.fb2) : zero3<float>();
-            const F3 tv = rp::aux_tangent(R.A.S, R.T, A, d, t_o, q.em_inv_dist);
-            wv3 = tv * A.w;
-            dv = dot(A.dw - dZ * (iZ * A.w), tv);
+            const F3 tv = rp::aux_tangent(R.A.S, R.T, g.A, d, t_o, q.em_inv_dist);
+            wv3 = tv * g.A.w;
+            dv = dot(g.A.dw - g.dZ * (g.iZ * g.A.w), tv);
         }
 #pragma unroll
         for (int m = 1; m < G; m <<= 1) {
             wv3.x += __shfl_xor(wv3.x, m); wv3.y += __shfl_xor(wv3.y, m); wv3.z += __shfl_xor(wv3.z, m);
             dv += __shfl_xor(dv, m);
         }
-        if (live && r == 0) {
-            const F3 td = (wv3 - d * dot(d, wv3)) * iZ;
-            rp::WarpReq &w = req[(int64_t) n * N + i];
-            w.gdir[0] = td.x; w.gdir[1] = td.y; w.gdir[2] = td.z; w.gdiv = dv * iZ;
+        if (g.live && g.r == 0) {
+            const F3 td = (wv3 - d * dot(d, wv3)) * g.iZ;
+            rp::WarpReq &w = req[(int64_t) g.n * R.A.N + g.i];
+            w.gdir[0] = td.x; w.gdir[1] = td.y; w.gdir[2] = td.z; w.gdiv = dv * g.iZ;
         }
-    }
+    });
 }
 
 size_t req_bytes(int64_t N) { return ((size_t) N * rp::kMaxReq * sizeof(rp::WarpReq) + 255) & ~(size_t) 255; }
+
+// What both entry points check behind replay_args_fill: NULL = fine and cfg filled, otherwise what is wrong.
+const char *reparam_args_invalid(rp::ReparamCfg &cfg, const EpsmScene *scene, int64_t N, int reparam_max_depth, int reparam_rays,
+                                 float kappa, float exponent, uint32_t flags, const void *workspace, size_t workspace_bytes) {
+    if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < epsm_trace_reparam_workspace_bytes(N))
+        return "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
+    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
+        return "need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0";
+    if (flags & ~EPSM_REPARAM_ANTITHETIC) return "unknown flag";
+    // (this pass's own rule: there is nothing to move, and its kernels have not been tried on a scene without geometry)
+    if (scene->n_triangles <= 0) return "the scene has no triangles";
+    cfg.max_depth = reparam_max_depth; cfg.rays = reparam_rays; cfg.kappa = kappa; cfg.exponent = exponent; cfg.flags = flags;
+    return nullptr;
+}
+
+// Stage 2 of either pass: launch(G, grid, n_max) starts its warp kernel for groups of G = 16, 32 or 64 >= reparam_rays lanes.
+template <class Launch>
+int launch_warp_stage(const char *what, const TraceArgs &A, int reparam_rays, Launch launch) {
+    // the n-th requests of all paths, n = 0 .. n_max - 1: the camera ray + two warps per vertex the depths allow
+    const int depth = path_max_depth(A);
+    const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
+    const dim3 grid((unsigned) ((A.N + 255) / 256));                       // one workgroup per 256 paths (N < 2^32: checked)
+    if (reparam_rays <= 16) launch(std::integral_constant<int, 16>(), grid, n_max);
+    else if (reparam_rays <= 32) launch(std::integral_constant<int, 32>(), grid, n_max);
+    else launch(std::integral_constant<int, 64>(), grid, n_max);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? EPSM_OK : epsm_host::hip_fail(what, e);
+}
 
 }  // namespace
 
@@ -251,51 +264,25 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
                                         int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                                         float *grad_pos, float *grad_nrm, void *workspace, size_t workspace_bytes, void *stream) {
     epsm_host::err_buf()[0] = 0;
-    auto bad = [&](const char *what) { char msg[200]; snprintf(msg, sizeof(msg), "epsm_trace_paths_reparam: %s", what); return fail(EPSM_EINVAL, msg); };
-    if (!scene || !sensor) return bad("NULL scene / sensor");
+    static const char *what = "epsm_trace_paths_reparam";
+    rp::ReparamArgs R = {};
+    if (const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return fail(EPSM_EINVAL, what, why);
     if (N == 0) return EPSM_OK;
-    if (N < 0 || spp < 1 || max_depth < 1 || rr_depth < 1 || path_offset < 0) return bad("bad N / spp / max_depth / rr_depth / path_offset");
-    if (sensor->border < 0 || sensor->border > 8) return bad("bad sensor border");
-    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
-        path_offset + N > 0xFFFFFFFFLL)
-        return bad("path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32)");
-    if (!radiance || !adj_radiance || !adj_film || !grad_pos) return bad("NULL per-path input or grad_pos");
-    if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < epsm_trace_reparam_workspace_bytes(N))
-        return bad("workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)");
-    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
-        return bad("need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0");
-    if (flags & ~EPSM_REPARAM_ANTITHETIC) return bad("unknown flag");
-    if (scene->n_triangles <= 0 || !scene->positions || !scene->normals || !scene->tri || !scene->tri_mesh || !scene->meshes ||
-        !scene->bsdfs || !scene->bvh || !scene->prim_index || !scene->tri_verts)
-        return bad("NULL scene array");
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return bad(why);
-    rp::ReparamArgs R;
-    memset(&R, 0, sizeof(R));
-    R.A.S = *scene; R.A.C = *sensor;
-    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
-    R.A.path_offset = path_offset; R.A.N = N;
-    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    if (!radiance || !adj_radiance || !adj_film || !grad_pos) return fail(EPSM_EINVAL, what, "NULL per-path input or grad_pos");
+    if (const char *why = reparam_args_invalid(R.cfg, scene, N, reparam_max_depth, reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
+        return fail(EPSM_EINVAL, what, why);
     R.radiance = radiance; R.adj_radiance = adj_radiance; R.adj_film = adj_film;
     R.G.pos = grad_pos; R.G.nrm = grad_nrm;
     rp::WarpReq *req = (rp::WarpReq *) workspace;
     int *count = (int *) ((char *) workspace + req_bytes(N));
     hipLaunchKernelGGL(epsm_reparam_path_kernel, dim3((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS)), dim3(EPSM_RP_THREADS), 0,
                        (hipStream_t) stream, R, req, count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam", e);
-    if (reparam_max_depth > 0) {
-        // the n-th requests of all paths, n = 0 .. n_max - 1: the camera ray + two warps per vertex the depths allow
-        const int depth = max_depth < 6 ? max_depth : 6;
-        const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
-        const int G = reparam_rays <= 16 ? 16 : reparam_rays <= 32 ? 32 : 64;
-        const dim3 grid((unsigned) ((N + 255) / 256));                     // one workgroup per 256 paths (N < 2^32: checked above)
-        if (G == 16) hipLaunchKernelGGL(epsm_reparam_warp_kernel<16>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        else if (G == 32) hipLaunchKernelGGL(epsm_reparam_warp_kernel<32>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        else hipLaunchKernelGGL(epsm_reparam_warp_kernel<64>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        e = hipGetLastError();
-        if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam", e);
-    }
-    return EPSM_OK;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
+    if (reparam_max_depth == 0) return EPSM_OK;
+    return launch_warp_stage(what, R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+        hipLaunchKernelGGL(epsm_reparam_warp_kernel<decltype(G)::value>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+    });
 }
 
 extern "C" size_t epsm_trace_reparam_forward_workspace_bytes(int64_t N) { return epsm_trace_reparam_workspace_bytes(N); }
@@ -307,51 +294,28 @@ extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const Ep
                                                 int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                                                 float *d_radiance, float *d_film, void *workspace, size_t workspace_bytes, void *stream) {
     epsm_host::err_buf()[0] = 0;
-    auto bad = [&](const char *what) { char msg[200]; snprintf(msg, sizeof(msg), "epsm_trace_paths_reparam_forward: %s", what); return fail(EPSM_EINVAL, msg); };
-    if (!scene || !sensor) return bad("NULL scene / sensor");
+    static const char *what = "epsm_trace_paths_reparam_forward";
+    rp::ReparamFwdArgs R = {};
+    if (const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return fail(EPSM_EINVAL, what, why);
     if (N == 0) return EPSM_OK;
-    if (N < 0 || spp < 1 || max_depth < 1 || rr_depth < 1 || path_offset < 0) return bad("bad N / spp / max_depth / rr_depth / path_offset");
-    if (sensor->border < 0 || sensor->border > 8) return bad("bad sensor border");
-    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
-        path_offset + N > 0xFFFFFFFFLL)
-        return bad("path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32)");
-    if (!radiance || !tan_pos || !d_radiance || !d_film) return bad("NULL per-path input / output or tan_pos");
-    if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < epsm_trace_reparam_forward_workspace_bytes(N))
-        return bad("workspace: 16-byte aligned, >= epsm_trace_reparam_forward_workspace_bytes(N)");
-    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
-        return bad("need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0");
-    if (flags & ~EPSM_REPARAM_ANTITHETIC) return bad("unknown flag");
-    if (scene->n_triangles <= 0 || !scene->positions || !scene->normals || !scene->tri || !scene->tri_mesh || !scene->meshes ||
-        !scene->bsdfs || !scene->bvh || !scene->prim_index || !scene->tri_verts)
-        return bad("NULL scene array");
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return bad(why);
-    rp::ReparamFwdArgs R;
-    memset(&R, 0, sizeof(R));
-    R.A.S = *scene; R.A.C = *sensor;
-    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
-    R.A.path_offset = path_offset; R.A.N = N;
-    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    if (!radiance || !tan_pos || !d_radiance || !d_film) return fail(EPSM_EINVAL, what, "NULL per-path input / output or tan_pos");
+    if (const char *why = reparam_args_invalid(R.cfg, scene, N, reparam_max_depth, reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
+        return fail(EPSM_EINVAL, what, why);
     R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
     rp::WarpReq *req = (rp::WarpReq *) workspace;
     int *count = (int *) ((char *) workspace + req_bytes(N));
     const dim3 path_grid((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS));
-    hipError_t e;
     if (reparam_max_depth > 0) {                                           // (no warp at depth 0: stage 3 alone)
         hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::RecordSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
-        e = hipGetLastError();
-        if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
-        const int depth = max_depth < 6 ? max_depth : 6;
-        const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
-        const int G = reparam_rays <= 16 ? 16 : reparam_rays <= 32 ? 32 : 64;
-        const dim3 grid((unsigned) ((N + 255) / 256));
-        if (G == 16) hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<16>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        else if (G == 32) hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<32>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        else hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<64>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
-        e = hipGetLastError();
-        if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return epsm_host::hip_fail(what, e);
+        const int rc = launch_warp_stage(what, R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+            hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<decltype(G)::value>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+        });
+        if (rc != EPSM_OK) return rc;
     }
     hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::ReadSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
-    e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_reparam_forward", e);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
     return EPSM_OK;
 }

@@ -16,7 +16,7 @@
 // Plain C++, compiled by hipcc for gfx950 and by g++ for the host harness (tests/host_harness/trace_tex_host.cpp).
 #pragma once
 
-#include "epsm_trace_core.h"
+#include "epsm_trace_replay.h"
 
 namespace epsm {
 namespace tx {
@@ -48,8 +48,6 @@ EPSM_HD void item_clear(Item &it) {
     for (int k = 0; k < 4; ++k) { it.off[k] = 0u; it.w[k] = 0.f; }
     it.coef = zero3<float>();
 }
-EPSM_HD float finite_or_zero(float x) { return fabsf(x) < __builtin_inff() ? x : 0.f; }   // (a non-finite coefficient adds nothing)
-EPSM_HD F3 finite_or_zero3(F3 v) { return f3(finite_or_zero(v.x), finite_or_zero(v.y), finite_or_zero(v.z)); }
 
 // the texels tex_eval interpolates at (u, v), same wrap
 EPSM_HD void texture_footprint(const EpsmTexture &T, float u, float v, Item &it) {
@@ -154,42 +152,25 @@ struct TexObserver {
     }
 };
 
-// The replay of path i after its primary ray's closest hit th0 (the device walks those as a packet, the host one by one);
-// sink.item(it) after every bounce for both items (on or not: the device sink works across the wave), sink.finish() at the end.
+// The replay of path i (epsm_trace_replay.h) under a TexObserver.
 template <class Sink>
 EPSM_HD void texture_replay(const TexArgs &T, int64_t i, bool has, PathState &s, const TriHit &th0, const BvhStack &st, Sink &sink) {
-    InlineVis vis{st};
     TexObserver obs{T, st, has, has ? ld3(T.radiance + 3 * i) : zero3<float>()};
     item_clear(obs.a); item_clear(obs.b);
     obs.L = obs.beta = obs.dir = zero3<float>(); obs.prev_bsdf_pdf = 1.f; obs.prev_bsdf_delta = true;
-    if (!has) s.active = false;
-    const int max_depth = path_max_depth(T.A);
-    for (int iteration = 0; iteration < max_depth; ++iteration) {
-        TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
-        if (iteration == 0) th = th0;
-        else if (s.active) th = intersect<false>(T.A.S, s.ray, st);
-        path_bounce(T.A, i, iteration, s, th, vis, obs);
-        sink.item(obs.a);
-        sink.item(obs.b);
-    }
-    sink.finish();
+    replay_path(T.A, i, has, s, th0, st, obs, sink);
 }
 
-// The arguments of both entry points (host side; device and host builds alike): NULL = fine, otherwise what is wrong.  `bufs`
-// holds n_textures pointers (or is NULL), `env` the envmap's; both entry points' buffers go into T.buf.
+// The arguments of both entry points (host side; device and host builds alike): the common eight through replay_args_fill, then
+// this pass's own.  NULL = fine, otherwise what is wrong; at N == 0 fine with nothing else looked at (T.A.N = 0: the caller has
+// nothing to do).  `bufs` holds n_textures pointers (or is NULL), `env` the envmap's; both entry points' buffers go into T.buf.
 inline const char *tex_args_fill(TexArgs &T, const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
                                  int rr_depth, int64_t path_offset, int64_t N, const float *radiance, float *const *bufs, float *env) {
     memset(&T, 0, sizeof(T));
-    if (!scene || !sensor || N < 0 || path_offset < 0 || spp < 1 || max_depth < 0) return "bad scene / sensor / N / spp / max_depth";
-    if (N > 0 && !radiance) return "NULL radiance";
-    if (path_offset + N > (int64_t) (sensor->width + 2 * sensor->border) * (sensor->height + 2 * sensor->border) * spp ||
-        path_offset + N > 0xFFFFFFFFLL)
-        return "path range exceeds (width + 2 border) * (height + 2 border) * spp (or 2^32)";
-    if (scene->n_textures < 0 || (scene->n_textures > 0 && !scene->textures)) return "NULL textures";
+    if (const char *why = replay_args_fill(T.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 0)) return why;
+    if (N == 0) return nullptr;
+    if (!radiance) return "NULL radiance";
     if (env && scene->env.kind != EPSM_ENV_ENVMAP) return "an envmap buffer for a scene without an envmap";
-    T.A.S = *scene; T.A.C = *sensor;
-    T.A.seed = seed; T.A.spp = spp; T.A.max_depth = max_depth; T.A.rr_depth = rr_depth; T.A.K_log = 0;
-    T.A.path_offset = path_offset; T.A.N = N;
     T.radiance = radiance;
     if (bufs)
         for (int t = 0; t < scene->n_textures; ++t) {

@@ -52,23 +52,19 @@ struct ScatterSink {
 // and the observer's state spill 376 B per lane to scratch, at two 220-228 registers and 36 B.
 template <bool BACKWARD>
 __global__ __launch_bounds__(128, 2) void epsm_texture_kernel(tx::TexArgs T) {
-    constexpr int kLds = 32;
-    __shared__ uint32_t s_stack[kLds * 128];
-    uint32_t deep[kBvhStack - kLds];
+    __shared__ uint32_t s_stack[kLaneStackLds * 128];
+    uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * 128 + threadIdx.x;
-    BvhStack st{s_stack + threadIdx.x, 128};
-    st.cap = kLds; st.ovf = deep; st.ovf_stride = 1;
+    const BvhStack st = lane_stack(s_stack, deep, 128);
     const bool has = i < T.A.N;
     if (__ballot(has) == 0ull) return;
-    const int64_t ii = has ? i : T.A.N - 1;
-    PathState s = path_begin(T.A, ii, false);
-    const TriHit th0 = packet_intersect(T.A.S, s.ray, has, s_stack + (threadIdx.x & ~63));
+    PrimaryHit p = primary_hit(T.A, i, has, false, s_stack);
     if (BACKWARD) {
-        ScatterSink sink{T, has ? ld3(T.adj + 3 * i) : zero3<float>()};
-        tx::texture_replay(T, ii, has, s, th0, st, sink);
+        ScatterSink sink{T, p.has ? ld3(T.adj + 3 * i) : zero3<float>()};
+        tx::texture_replay(T, p.i, p.has, p.s, p.th0, st, sink);
     } else {
-        tx::GatherSink sink{T, ii, has, zero3<float>()};
-        tx::texture_replay(T, ii, has, s, th0, st, sink);
+        tx::GatherSink sink{T, p.i, p.has, zero3<float>()};
+        tx::texture_replay(T, p.i, p.has, p.s, p.th0, st, sink);
     }
 }
 
@@ -91,9 +87,9 @@ extern "C" int epsm_trace_paths_texture_backward(const EpsmScene *scene, const E
     tx::TexArgs T;
     if (const char *why = tx::tex_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, grad_tex, grad_env))
         return fail(EPSM_EINVAL, what, why);
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return fail(EPSM_EINVAL, what, why);
-    if (N > 0 && !adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
-    if (N == 0 || (T.n_buf == 0 && !grad_env)) return EPSM_OK;
+    if (N == 0) return EPSM_OK;
+    if (!adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
+    if (T.n_buf == 0 && !grad_env) return EPSM_OK;
     T.adj = adj_radiance;
     return launch(what, T, true, stream);
 }
@@ -108,9 +104,8 @@ extern "C" int epsm_trace_paths_texture_forward(const EpsmScene *scene, const Ep
     if (const char *why = tx::tex_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance,
                                             (float *const *) tan_tex, (float *) tan_env))
         return fail(EPSM_EINVAL, what, why);
-    if (const char *why = epsm_host::scene_tables_invalid(scene)) return fail(EPSM_EINVAL, what, why);
-    if (N > 0 && !d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     if (N == 0) return EPSM_OK;
+    if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     T.d_radiance = d_radiance;
     return launch(what, T, false, stream);
 }

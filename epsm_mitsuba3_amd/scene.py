@@ -1392,9 +1392,29 @@ class Scene:
             raise RuntimeError(f"host tracer rc={rc}")
         _lib.check(rc, what)
 
+    def _replay(self, entry: str, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, *tail) -> None:
+        """Calls tracer entry point ``entry`` on paths [lo, hi): the eight arguments they all start with, ``tail`` (tensors by
+        their pointer, None as NULL), the stream; raises unless it returns EPSM_OK."""
+        lib, stream = self._runtime()
+        cs = self.sensors[sensor_index].c_struct()
+        tail = [C.c_void_p(None if t is None else t.data_ptr()) if t is None or torch.is_tensor(t) else t for t in tail]
+        rc = getattr(lib, entry)(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
+                                 int(self.rr_depth), C.c_int64(lo), C.c_int64(hi - lo), *tail, C.c_void_p(stream))
+        self._check(rc, entry)
+
+    def _rows(self, t: torch.Tensor, n: int, w: int) -> None:
+        """``t`` is what an entry point reads or writes as n rows of w floats."""
+        assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (n, w) and t.device.type == self.device.type
+
+    def _reparam_workspace(self, need: int, device) -> torch.Tensor:
+        """The workspace of the reparameterised passes, kept between calls and grown on demand."""
+        ws = getattr(self, "_reparam_ws", None)
+        if ws is None or ws.numel() < max(need, 16) or ws.device != device:
+            ws = self._reparam_ws = torch.empty(max(need, 16), device=device, dtype=torch.uint8)
+        return ws
+
     def trace_color(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int):
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
-        lib, stream = self._runtime()
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
         if Cn == 0 and not self.texture_slots and not self.alpha_slots:
@@ -1405,12 +1425,7 @@ class Scene:
         # (textures or roughnesses alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the replays
         # of the texel and roughness adjoints must see the radiance of this very estimator)
         sums = torch.empty((n, max(Cn, 1), 3), device=dev, dtype=torch.float32)
-        cs = self.sensors[sensor_index].c_struct()
-        rc = lib.epsm_trace_paths_color(C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth),
-                                        int(self.rr_depth), C.c_int64(lo), C.c_int64(n), C.c_void_p(film_pos.data_ptr()),
-                                        C.c_void_p(radiance.data_ptr()), C.c_void_p(valid.data_ptr()), C.c_void_p(sums.data_ptr()),
-                                        int(max(Cn, 1)), C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_color")
+        self._replay("epsm_trace_paths_color", sensor_index, seed, spp, max_depth, lo, hi, film_pos, radiance, valid, sums, int(max(Cn, 1)))
         return film_pos, radiance, sums[:, :Cn]
 
     def _texture_pointers(self, bufs):
@@ -1431,32 +1446,18 @@ class Scene:
         """``epsm_trace_paths_texture_backward``: ACCUMULATES d loss / d texel of paths [lo, hi) into ``grads`` -- one (H, W, 3) buffer
         per texture slot, w.r.t. the texels the tracer reads (an envmap's: its bitmap times ``scale``) -- given the radiance of the
         primal pass (``trace_color`` with the same seed) and its adjoint."""
-        lib, stream = self._runtime()
-        n = hi - lo
         for t_ in (radiance, adj_radiance):
-            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, 3) and t_.device.type == self.device.type
+            self._rows(t_, hi - lo, 3)
         arr, env = self._texture_pointers(grads)
-        cs = self.sensors[sensor_index].c_struct()
-        rc = lib.epsm_trace_paths_texture_backward(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()), arr, env,
-            C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_texture_backward")
+        self._replay("epsm_trace_paths_texture_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, arr, env)
 
     def trace_texture_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangents):
         """``epsm_trace_paths_texture_forward``: the transpose of ``trace_texture_backward`` -- for one (H, W, 3) texel tangent per
         texture slot returns d radiance (n, 3) of paths [lo, hi)."""
-        lib, stream = self._runtime()
-        n = hi - lo
-        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3)
+        self._rows(radiance, hi - lo, 3)
         arr, env = self._texture_pointers(tangents)
-        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
-        cs = self.sensors[sensor_index].c_struct()
-        rc = lib.epsm_trace_paths_texture_forward(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), arr, env, C.c_void_p(d_radiance.data_ptr()),
-            C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_texture_forward")
+        d_radiance = torch.empty((hi - lo, 3), device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_texture_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, arr, env, d_radiance)
         return d_radiance
 
     def _alpha_slot_count(self) -> int:
@@ -1472,36 +1473,25 @@ class Scene:
         """``epsm_trace_paths_bsdf_backward``: ADDS d loss / d alpha of paths [lo, hi) to ``grad_alpha`` (one float per alpha slot,
         ``attach_alpha``) given the radiance of the primal pass (``trace_color`` with the same seed) and its adjoint.  No atomics:
         the same call gives the same bits."""
-        lib, stream = self._runtime()
         n, B = hi - lo, self._alpha_slot_count()
         for t_ in (radiance, adj_radiance):
-            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, 3) and t_.device.type == self.device.type
+            self._rows(t_, n, 3)
         assert grad_alpha.is_contiguous() and grad_alpha.dtype == torch.float32 and grad_alpha.numel() == B
         assert grad_alpha.device.type == self.device.type
-        nbytes = int(lib.epsm_trace_bsdf_workspace_bytes(C.c_int64(n)))
+        nbytes = int(self._runtime()[0].epsm_trace_bsdf_workspace_bytes(C.c_int64(n)))
         work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
-        cs = self.sensors[sensor_index].c_struct()
-        rc = lib.epsm_trace_paths_bsdf_backward(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()),
-            C.c_void_p(grad_alpha.data_ptr()), int(B), C.c_void_p(work.data_ptr()), C.c_size_t(work.numel() * 4), C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_bsdf_backward")
+        self._replay("epsm_trace_paths_bsdf_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_alpha,
+                     int(B), work, C.c_size_t(work.numel() * 4))
 
     def trace_alpha_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangent_alpha):
         """``epsm_trace_paths_bsdf_forward``: the transpose of ``trace_alpha_backward`` -- for one tangent per alpha slot returns
         d radiance (n, 3) of paths [lo, hi)."""
-        lib, stream = self._runtime()
         n, B = hi - lo, self._alpha_slot_count()
-        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3)
+        self._rows(radiance, n, 3)
         assert tangent_alpha.is_contiguous() and tangent_alpha.dtype == torch.float32 and tangent_alpha.numel() == B
         assert tangent_alpha.device.type == self.device.type
         d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
-        cs = self.sensors[sensor_index].c_struct()
-        rc = lib.epsm_trace_paths_bsdf_forward(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(tangent_alpha.data_ptr()), int(B),
-            C.c_void_p(d_radiance.data_ptr()), C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_bsdf_forward")
+        self._replay("epsm_trace_paths_bsdf_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_alpha, int(B), d_radiance)
         return d_radiance
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
@@ -1511,25 +1501,15 @@ class Scene:
         positions (and normals) into ``grad_pos`` / ``grad_nrm`` (V,3) given, per path, the radiance of the primal pass under
         the same seed, its adjoint and the adjoint of the film position + determinant (integrators.film_adjoint_reparam).
         ``antithetic``: EPSM_REPARAM_ANTITHETIC (auxiliary rays in mirrored pairs, reparam.py:82-84)."""
-        lib, stream = self._runtime()
-        dev = self.device
         n = hi - lo
-        for t_, w in ((radiance, 3), (adj_radiance, 3), (adj_film, 3)):
-            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (n, w) and t_.device.type == dev.type
+        for t_ in (radiance, adj_radiance, adj_film):
+            self._rows(t_, n, 3)
         for t_ in (grad_pos, grad_nrm):
-            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (self.V, 3) and t_.device.type == dev.type
-        cs = self.sensors[sensor_index].c_struct()
-        need = int(lib.epsm_trace_reparam_workspace_bytes(C.c_int64(n)))
-        ws = getattr(self, "_reparam_ws", None)
-        if ws is None or ws.numel() < max(need, 16) or ws.device != radiance.device:
-            ws = self._reparam_ws = torch.empty(max(need, 16), device=radiance.device, dtype=torch.uint8)
-        rc = lib.epsm_trace_paths_reparam(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(adj_radiance.data_ptr()),
-            C.c_void_p(adj_film.data_ptr()), int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
-            C.c_uint32(1 if antithetic else 0), C.c_void_p(grad_pos.data_ptr()), C.c_void_p(grad_nrm.data_ptr()), C.c_void_p(ws.data_ptr()),
-            C.c_size_t(ws.numel()), C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_reparam")
+            self._rows(t_, self.V, 3)
+        ws = self._reparam_workspace(int(self._runtime()[0].epsm_trace_reparam_workspace_bytes(C.c_int64(n))), radiance.device)
+        self._replay("epsm_trace_paths_reparam", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, adj_film,
+                     int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent), C.c_uint32(1 if antithetic else 0),
+                     grad_pos, grad_nrm, ws, C.c_size_t(ws.numel()))
 
     def trace_reparam_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tan_pos,
                               tan_nrm, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float, antithetic: bool = False):
@@ -1537,26 +1517,17 @@ class Scene:
         tangents ``tan_pos`` / ``tan_nrm`` (V,3) of the vertex positions / normals -- read on the attached meshes only -- returns, per
         path, ``d_radiance (n,3)`` and ``d_film (n,3)`` = d (film position x, y; det), which integrators.film_splat_tangent turns
         into the image's tangent.  Same workspace as ``trace_reparam``."""
-        lib, stream = self._runtime()
         dev = self.device
         n = hi - lo
-        assert radiance.is_contiguous() and radiance.dtype == torch.float32 and tuple(radiance.shape) == (n, 3) and radiance.device.type == dev.type
+        self._rows(radiance, n, 3)
         for t_ in (tan_pos, tan_nrm):
-            assert t_.is_contiguous() and t_.dtype == torch.float32 and tuple(t_.shape) == (self.V, 3) and t_.device.type == dev.type
+            self._rows(t_, self.V, 3)
         d_radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
         d_film = torch.empty((n, 3), device=dev, dtype=torch.float32)
-        cs = self.sensors[sensor_index].c_struct()
-        need = int(lib.epsm_trace_reparam_forward_workspace_bytes(C.c_int64(n)))
-        ws = getattr(self, "_reparam_ws", None)
-        if ws is None or ws.numel() < max(need, 16) or ws.device != radiance.device:
-            ws = self._reparam_ws = torch.empty(max(need, 16), device=radiance.device, dtype=torch.uint8)
-        rc = lib.epsm_trace_paths_reparam_forward(
-            C.byref(self.c_scene), C.byref(cs), C.c_uint32(seed & 0xFFFFFFFF), int(spp), int(max_depth), int(self.rr_depth),
-            C.c_int64(lo), C.c_int64(n), C.c_void_p(radiance.data_ptr()), C.c_void_p(tan_pos.data_ptr()),
-            C.c_void_p(tan_nrm.data_ptr()), int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
-            C.c_uint32(1 if antithetic else 0), C.c_void_p(d_radiance.data_ptr()), C.c_void_p(d_film.data_ptr()),
-            C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), C.c_void_p(stream))
-        self._check(rc, "epsm_trace_paths_reparam_forward")
+        ws = self._reparam_workspace(int(self._runtime()[0].epsm_trace_reparam_forward_workspace_bytes(C.c_int64(n))), radiance.device)
+        self._replay("epsm_trace_paths_reparam_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tan_pos, tan_nrm,
+                     int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent), C.c_uint32(1 if antithetic else 0),
+                     d_radiance, d_film, ws, C.c_size_t(ws.numel()))
         return d_radiance, d_film
 
     def film_splat(self, accum: torch.Tensor, sensor: Sensor, film_pos: torch.Tensor, radiance: torch.Tensor) -> None:

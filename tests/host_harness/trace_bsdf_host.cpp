@@ -21,26 +21,23 @@ extern "C" int epsm_trace_paths_bsdf_backward(const EpsmScene *scene, const Epsm
                                               size_t workspace_bytes, void *) {
     ba::BsdfArgs T;
     if (ba::bsdf_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, B)) return -22;
-    if ((N > 0 && !adj_radiance) || (B > 0 && !grad_alpha)) return -22;
-    if (N == 0 || B == 0) return 0;
+    if (N == 0) return 0;
+    if (!adj_radiance || (B > 0 && !grad_alpha)) return -22;
+    if (B == 0) return 0;
     if (!workspace || workspace_bytes < ba::workspace_bytes(N)) return -22;
     T.adj = adj_radiance; T.partial = (float *) workspace;
     const int64_t rows = ba::partial_rows(N);
 #pragma omp parallel for schedule(dynamic, 2)
     for (int64_t r = 0; r < rows; ++r) {
         float row[ba::kMaxSlots] = {};
-        const int64_t end = (r + 1) * ba::kBlock < N ? (r + 1) * ba::kBlock : N;
-        for (int64_t i = r * ba::kBlock; i < end; ++i) {
-            uint32_t stack[kBvhStack];
-            const BvhStack st{stack, 1};
-            PathState s = path_begin(T.A, i, false);
-            const TriHit th0 = intersect<false>(T.A.S, s.ray, st);
+        for_each_path(T.A, r * ba::kBlock, (r + 1) * ba::kBlock < N ? (r + 1) * ba::kBlock : N,
+                      [&](int64_t i, PathState &s, const TriHit &th0, const BvhStack &st) {
             HostSlotSink sink;
             sink.sums.adj = ld3(adj_radiance + 3 * i);
             sink.sums.clear();
             ba::bsdf_replay(T, i, true, s, th0, st, sink);
             for (int k = 0; k < B; ++k) row[k] += sink.sums.acc[k];
-        }
+        });
         for (int k = 0; k < ba::kMaxSlots; ++k) T.partial[r * ba::kMaxSlots + k] = row[k];
     }
     for (int k = 0; k < B; ++k) {
@@ -56,16 +53,12 @@ extern "C" int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmS
                                              const float *tangent_alpha, int B, float *d_radiance, void *) {
     ba::BsdfArgs T;
     if (ba::bsdf_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, B)) return -22;
-    if ((N > 0 && !d_radiance) || (B > 0 && !tangent_alpha)) return -22;
+    if (N == 0) return 0;
+    if (!d_radiance || (B > 0 && !tangent_alpha)) return -22;
     T.tangent = tangent_alpha; T.d_radiance = d_radiance;
-#pragma omp parallel for schedule(dynamic, 256)
-    for (int64_t i = 0; i < N; ++i) {
-        uint32_t stack[kBvhStack];
-        const BvhStack st{stack, 1};
-        PathState s = path_begin(T.A, i, false);
-        const TriHit th0 = intersect<false>(T.A.S, s.ray, st);
+    for_each_path(T.A, [&](int64_t i, PathState &s, const TriHit &th0, const BvhStack &st) {
         ba::TangentSink sink{T, i, true, zero3<float>()};
         ba::bsdf_replay(T, i, true, s, th0, st, sink);
-    }
+    });
     return 0;
 }

@@ -11,13 +11,11 @@ extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const Ep
                                                 const float *tan_pos, const float *tan_nrm, int reparam_max_depth, int reparam_rays,
                                                 float kappa, float exponent, uint32_t flags, float *d_radiance, float *d_film, void *,
                                                 size_t, void *) {
+    rp::ReparamFwdArgs R = {};
+    if (replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return -22;
+    if (N == 0) return 0;
     if (reparam_rays < 1 || reparam_rays > rp::kMaxAux) return -22;
     if (!radiance || !tan_pos || !d_radiance || !d_film) return -22;
-    rp::ReparamFwdArgs R;
-    memset(&R, 0, sizeof(R));
-    R.A.S = *scene; R.A.C = *sensor;
-    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
-    R.A.path_offset = path_offset; R.A.N = N;
     R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
     R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
 #pragma omp parallel for schedule(dynamic, 64)

@@ -3,12 +3,28 @@
 // point names as the product library; host pointers.  Not shipped, not a fallback.
 #include <math.h>
 #include <string.h>
-#include "../../epsm_mitsuba3_amd/csrc/epsm_trace_core.h"
+#include "../../epsm_mitsuba3_amd/csrc/epsm_trace_replay.h"
 #include "../../epsm_mitsuba3_amd/csrc/epsm_trace_wavefront.h"
 #include "../../epsm_mitsuba3_amd/csrc/epsm_trace_reparam.h"
 #include "../../epsm_mitsuba3_amd/csrc/epsm_probe_core.h"
 
 using namespace epsm;
+
+// Paths [lo, hi) of a tile one by one, each on its own stack with its primary ray traced: body(i, s, th0, st) -- what the device
+// kernels' prologue hands a lane (epsm_trace_packet.h) -- and the whole tile, OpenMP over chunks of 256 paths.
+template <class Body> void for_each_path(const TraceArgs &A, int64_t lo, int64_t hi, Body body) {
+    for (int64_t i = lo; i < hi; ++i) {
+        uint32_t stack[kBvhStack];
+        const BvhStack st{stack, 1};
+        PathState s = path_begin(A, i, false);
+        const TriHit th0 = intersect<false>(A.S, s.ray, st);
+        body(i, s, th0, st);
+    }
+}
+template <class Body> void for_each_path(const TraceArgs &A, Body body) {
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t lo = 0; lo < A.N; lo += 256) for_each_path(A, lo, lo + 256 < A.N ? lo + 256 : A.N, body);
+}
 
 extern "C" int epsm_trace_paths(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
                                 int rr_depth, int64_t path_offset, int64_t N, int K_log, float *ray_o, float *ray_d,
@@ -36,10 +52,8 @@ extern "C" int epsm_trace_paths_color(const EpsmScene *scene, const EpsmSensor *
                                       int rr_depth, int64_t path_offset, int64_t N, float *film_pos, float *radiance,
                                       uint8_t *valid, float *color_sum, int n_color, void *) {
     TraceArgs A;
-    memset(&A, 0, sizeof(A));
-    A.S = *scene; A.C = *sensor;
-    A.seed = seed; A.spp = spp; A.max_depth = max_depth; A.rr_depth = rr_depth; A.K_log = 0;
-    A.path_offset = path_offset; A.N = N;
+    if (replay_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return -22;
+    if (N == 0) return 0;
     A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
     A.color_sum = color_sum; A.n_color = n_color;
     memset(color_sum, 0, (size_t) N * n_color * 3 * sizeof(float));
@@ -56,12 +70,10 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
                                         const float *adj_radiance, const float *adj_film, int reparam_max_depth, int reparam_rays,
                                         float kappa, float exponent, uint32_t flags, float *grad_pos, float *grad_nrm, void *, size_t,
                                         void *) {
+    rp::ReparamArgs R = {};
+    if (replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return -22;
+    if (N == 0) return 0;
     if (reparam_rays < 1 || reparam_rays > rp::kMaxAux) return -22;
-    rp::ReparamArgs R;
-    memset(&R, 0, sizeof(R));
-    R.A.S = *scene; R.A.C = *sensor;
-    R.A.seed = seed; R.A.spp = spp; R.A.max_depth = max_depth; R.A.rr_depth = rr_depth; R.A.K_log = 0;
-    R.A.path_offset = path_offset; R.A.N = N;
     R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
     R.radiance = radiance; R.adj_radiance = adj_radiance; R.adj_film = adj_film;
     R.G.pos = grad_pos; R.G.nrm = grad_nrm;

@@ -32,17 +32,13 @@ extern "C" int epsm_trace_paths_texture_backward(const EpsmScene *scene, const E
                                                  const float *adj_radiance, float *const *grad_tex, float *grad_env, void *) {
     tx::TexArgs T;
     if (tx::tex_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, grad_tex, grad_env)) return -22;
-    if (N > 0 && !adj_radiance) return -22;
+    if (N == 0) return 0;
+    if (!adj_radiance) return -22;
     T.adj = adj_radiance;
-#pragma omp parallel for schedule(dynamic, 256)
-    for (int64_t i = 0; i < N; ++i) {
-        uint32_t stack[kBvhStack];
-        const BvhStack st{stack, 1};
-        PathState s = path_begin(T.A, i, false);
-        const TriHit th0 = intersect<false>(T.A.S, s.ray, st);
+    for_each_path(T.A, [&](int64_t i, PathState &s, const TriHit &th0, const BvhStack &st) {
         HostScatterSink sink{T, ld3(adj_radiance + 3 * i)};
         tx::texture_replay(T, i, true, s, th0, st, sink);
-    }
+    });
     return 0;
 }
 
@@ -53,16 +49,12 @@ extern "C" int epsm_trace_paths_texture_forward(const EpsmScene *scene, const Ep
     if (tx::tex_args_fill(T, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, (float *const *) tan_tex,
                           (float *) tan_env))
         return -22;
-    if (N > 0 && !d_radiance) return -22;
+    if (N == 0) return 0;
+    if (!d_radiance) return -22;
     T.d_radiance = d_radiance;
-#pragma omp parallel for schedule(dynamic, 256)
-    for (int64_t i = 0; i < N; ++i) {
-        uint32_t stack[kBvhStack];
-        const BvhStack st{stack, 1};
-        PathState s = path_begin(T.A, i, false);
-        const TriHit th0 = intersect<false>(T.A.S, s.ray, st);
+    for_each_path(T.A, [&](int64_t i, PathState &s, const TriHit &th0, const BvhStack &st) {
         tx::GatherSink sink{T, i, true, zero3<float>()};
         tx::texture_replay(T, i, true, s, th0, st, sink);
-    }
+    });
     return 0;
 }
