@@ -16,14 +16,16 @@ three HIP launches (tangent, gradient, scatter) on the current stream.
 """
 from __future__ import annotations
 
-import math
-from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence
+from contextlib import contextmanager, nullcontext
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional
 
 import torch
 
 from . import dist as _dist
 from . import profiler as _prof
+from .film import (_WEIGHT_ONE, develop_tangent, film_adjoint, film_adjoint_reparam, film_adjoint_reparam_torch,  # noqa: F401
+                   film_splat_tangent, film_splat_tangent_torch, film_weight_counts)
 from .manifold_grad import OUTLIER_CLIP, calc_grad as _calc_grad, manifold_grad_packed
 from .params import ParamGrads
 from .records import PackedLog, PackedRecords, PackedScatter
@@ -75,16 +77,27 @@ class PathTrace:
     log: Optional[PackedLog] = None   # the native log (then path_info / scatter_info may be None)
 
 
+def _max_depth_property(props: dict):
+    """``max_depth`` of an integrator's properties (common.py:31-37); -1 = infinite (the reference stores 0xffffffff)."""
+    max_depth = props.get("max_depth", 6)
+    if max_depth < 0 and max_depth != -1:
+        raise Exception("\"max_depth\" must be set to -1 (infinite) or a value >= 0")
+    return max_depth
+
+
+def _replay_depth(max_depth) -> int:
+    """``max_depth`` as the tracer's logging and replaying passes take it: their path loop stops after 6 bounces whatever the
+    integrator says (epsm.py:549) and -1 means "no limit" (common.py:31-37)."""
+    return 6 if max_depth < 0 else min(int(max_depth), 6)
+
+
 class EPSMIntegrator:
     """Base class; ``variant`` selects the calc_grad flavour."""
     variant: str = ""
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
-        max_depth = props.get("max_depth", 6)           # common.py:31-37
-        if max_depth < 0 and max_depth != -1:
-            raise Exception("\"max_depth\" must be set to -1 (infinite) or a value >= 0")
-        self.max_depth = max_depth            # -1 = infinite (the reference stores 0xffffffff, common.py:37)
+        self.max_depth = _max_depth_property(props)
         self.rr_depth = props.get("rr_depth", 5)        # common.py:39-41
         if self.rr_depth <= 0:
             raise Exception("\"rr_depth\" must be set to a value greater than zero!")
@@ -150,48 +163,42 @@ class EPSMIntegrator:
             # The manifold integrators move geometry through channels 3, 4 only (epsm.py:729-732 leaves the colour
             # adjoint's propagation into geometry commented out): what a 3-channel image can reach are the colour
             # parameters attached to the scene.
-            prb = PRBIntegrator({"max_depth": self.max_depth, "rr_depth": self.rr_depth})
-            return prb.render_backward(scene, params, grad_in, sensor=sensor, seed=seed, spp=spp)
+            return self._prb().render_backward(scene, params, grad_in, sensor=sensor, seed=seed, spp=spp)
+        # The one place that is handed something other than a `Scene` -- `SyntheticScene`, bench.py's records: any object with
+        # `trace_paths`.  What such an object may leave out is read here, by name with a default, and nowhere else.
+        tracer = getattr(scene, "iter_traces", None) or scene.trace_paths      # a generator: one tile resident at a time
+        packed_log = getattr(scene, "supports_packed_log", False)
+        gradient_only = getattr(scene, "supports_gradient_only", False)
+        first_hit = getattr(scene, "supports_first_hit_fusion", False)
+        rigid_slots = getattr(scene, "rigid_slots", ())
         if getattr(scene, "sensor_rotation", False):
             # this branch transports d / d ray.o alone (epsm.py:260-261): the sensor's rotation has no term in it
             raise NotImplementedError("the 5-channel manifold branch differentiates the sensor's position only (epsm.py:260-261); the "
                                       "gradient of its rotation is `prb_reparam`'s (attach_sensor(rotation=True))")
         rank, world = _dist.world()
-        # dr.backward ACCUMULATES into the gradients that are already there.  With more than one rank only THIS
-        # call's contribution may be summed over the ranks: what `params` held on entry is already a sum over the
-        # ranks (or the caller's own data) and must not be multiplied by the world size.  The rigid slots reduce this call's
-        # contribution too: then it is kept apart on one rank as well.
-        rigid = _rigid_slot_count(scene, params)
-        target = params.scratch() if world > 1 or rigid else params
-        tracer = getattr(scene, "iter_traces", None) or scene.trace_paths      # a generator: one tile resident at a time
-        kw = {}
-        if self.fused and self.fuse_tangent and self.packed_log and getattr(scene, "supports_packed_log", False):
-            kw["packed_log"] = True        # the tracer writes the backward kernel's native layout (EpsmPackedLog)
-        if self.gradient_only and getattr(scene, "supports_gradient_only", False):
-            kw["gradient_only"] = self.variant
-            if self.fuse_first_hit and kw.get("packed_log") and getattr(scene, "supports_first_hit_fusion", False):
-                kw["first_hit"] = (grad_in if grad_in.is_contiguous() else grad_in.contiguous(), target, self.outlier_clip, True)
-        traces = tracer(sensor=self.backward_sensor, seed=seed, spp=self.backward_spp,
-                        max_depth=self.tracer_depth(), max_log_depth=self.max_log_depth, rank=rank, world_size=world,
-                        sparse_log=True,   # the log is consumed here and nowhere else: skip the zeros of dead bounces
-                        **kw)
-        if isinstance(traces, PathTrace):
-            traces = [traces]
-        traces = iter(traces)
-        while True:                                # this rank's pixel/sample tiles
-            with _prof.phase("epsm.render_backward.trace"):          # (a generator: the tile is traced when asked for)
-                trace = next(traces, None)
-            if trace is None:
-                break
-            with _prof.phase("epsm.render_backward.backward_pass"):
-                self.backward_from_trace(trace, target, grad_in)
-            del trace
-        if world > 1:
-            with _prof.phase("epsm.render_backward.allreduce"):
-                _dist.allreduce_param_grads(target.flat)   # one RCCL all-reduce of the whole buffer
-        if target is not params:
-            params.flat += target.flat
-            _rigid_backward(scene, params, target)
+        with _call_contribution(scene, params, _rigid_slot_count(rigid_slots, params)) as target:
+            kw = {}
+            if self.fused and self.fuse_tangent and self.packed_log and packed_log:
+                kw["packed_log"] = True        # the tracer writes the backward kernel's native layout (EpsmPackedLog)
+            if self.gradient_only and gradient_only:
+                kw["gradient_only"] = self.variant
+                if self.fuse_first_hit and kw.get("packed_log") and first_hit:
+                    kw["first_hit"] = (grad_in if grad_in.is_contiguous() else grad_in.contiguous(), target, self.outlier_clip, True)
+            traces = tracer(sensor=self.backward_sensor, seed=seed, spp=self.backward_spp,
+                            max_depth=self.tracer_depth(), max_log_depth=self.max_log_depth, rank=rank, world_size=world,
+                            sparse_log=True,   # the log is consumed here and nowhere else: skip the zeros of dead bounces
+                            **kw)
+            if isinstance(traces, PathTrace):
+                traces = [traces]
+            traces = iter(traces)
+            while True:                                # this rank's pixel/sample tiles
+                with _prof.phase("epsm.render_backward.trace"):          # (a generator: the tile is traced when asked for)
+                    trace = next(traces, None)
+                if trace is None:
+                    break
+                with _prof.phase("epsm.render_backward.backward_pass"):
+                    self.backward_from_trace(trace, target, grad_in)
+                del trace
 
     # -- forward ------------------------------------------------------------
     def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
@@ -200,13 +207,15 @@ class EPSMIntegrator:
         integrator's depths -- the attached colour parameters; geometry tangents contribute nothing, as that branch leaves the
         geometry alone.  The 5-channel branch transports a requested pixel motion (epsm.py:236-272) and is no adjoint of a
         rendered quantity: it has no forward form."""
-        prb = PRBIntegrator({"max_depth": self.max_depth, "rr_depth": self.rr_depth})
-        return prb.render_forward(scene, params, sensor=sensor, seed=seed, spp=spp)
+        return self._prb().render_forward(scene, params, sensor=sensor, seed=seed, spp=spp)
+
+    def _prb(self) -> "PRBIntegrator":
+        """The colour phase at this integrator's depths: what the 3-channel branch and ``render_forward`` delegate to."""
+        return PRBIntegrator({"max_depth": self.max_depth, "rr_depth": self.rr_depth})
 
     def tracer_depth(self) -> int:
-        """``max_depth`` as the tracer takes it: the path loop stops after 6 bounces whatever the integrator says
-        (epsm.py:549) and -1 means "no limit" (common.py:31-37)."""
-        return 6 if self.max_depth < 0 else min(self.max_depth, 6)
+        """``max_depth`` as the backward trace takes it (``_replay_depth``)."""
+        return _replay_depth(self.max_depth)
 
     def backward_from_trace(self, trace: PathTrace, params: ParamGrads, grad_in: torch.Tensor,
                             packed=None, out=None, mark: Optional[Callable[[str], None]] = None,
@@ -215,7 +224,7 @@ class EPSMIntegrator:
         built once for records that stay resident; ``out`` = reusable output tensors; ``mark(name)`` is
         called after each stage (bench.py records HIP events there)."""
         mark = mark or (lambda name: None)
-        if isinstance(packed, PackedLog) or getattr(trace, "log", None) is not None:
+        if isinstance(packed, PackedLog) or trace.log is not None:
             # the native log (one 128-byte record per path vertex): one launch, nothing else
             log = packed if isinstance(packed, PackedLog) else trace.log
             mark("tangent")
@@ -267,199 +276,32 @@ class ManifoldCausticIntegrator(EPSMIntegrator):
     variant = "manifold_caustic"
 
 
-def _box_window(film_pos: torch.Tensor, H: int, W: int):
-    """The pixel under every sample, (X, Y) (n) each, and whether it is on the film."""
-    X, Y = torch.floor(film_pos[:, 0]).long(), torch.floor(film_pos[:, 1]).long()
-    return X, Y, (X >= 0) & (Y >= 0) & (X < W) & (Y < H)
+def _pass_frame(scene, sensor: int, spp: int, kind: str):
+    """What a pass over a sensor's wavefront starts from, resolved once for a ``(scene, sensor, spp)`` triple: the sensor's index
+    and the sensor, the sample count, the world size, the zero film (H,W,4) [r,g,b,w] the primal estimates are splatted into, and
+    this rank's tiles of the ``kind`` plan (``Scene.tile_plan``)."""
+    si = min(sensor, len(scene.sensors) - 1)
+    s = scene.sensors[si]
+    spp = spp or s.spp
+    rank, world = _dist.world()
+    accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+    return si, s, spp, world, accum, scene.tile_plan(s.wavefront_size(spp), kind, rank, world)
 
 
-def _gaussian_window(film_pos: torch.Tensor, H: int, W: int):
-    """The 5 x 5 window of the gaussian reconstruction filter (stddev 0.5, radius 2, src/rfilters/gaussian.cpp) around every
-    sample: pixel columns ``xs`` and rows ``ys`` (n,5) each, not clamped, and the separable weights ``wx``, ``wy`` (n,5), zero
-    off the film.  The weight of pixel (ys[i,a], xs[i,b]) is wy[i,a] wx[i,b]: what ``film_adjoint`` gathers with and what
-    ``film_weight_counts`` sums."""
-    px, py = film_pos[:, 0], film_pos[:, 1]
-    X, Y = torch.floor(px).long(), torch.floor(py).long()
-    radius, alpha = 2.0, -1.0 / (2.0 * 0.5 * 0.5)
-    bias = math.exp(alpha * radius * radius)
-    off = torch.arange(-2, 3, device=film_pos.device)
-    xs, ys = X[:, None] + off[None, :], Y[:, None] + off[None, :]             # (n,5)
-    dx, dy = (xs.float() + 0.5) - px[:, None], (ys.float() + 0.5) - py[:, None]
-    wx = torch.where(dx.abs() <= radius, (torch.exp(alpha * dx * dx) - bias).clamp_min(0), torch.zeros_like(dx))
-    wy = torch.where(dy.abs() <= radius, (torch.exp(alpha * dy * dy) - bias).clamp_min(0), torch.zeros_like(dy))
-    wx = wx * ((xs >= 0) & (xs < W)); wy = wy * ((ys >= 0) & (ys < H))
-    return xs, ys, wx, wy
-
-
-def film_adjoint(film_pos: torch.Tensor, grad_img: torch.Tensor, weight_img: torch.Tensor, rfilter: int) -> torch.Tensor:
-    """Adjoint of ImageBlock::put + film.develop (``epsm_film_splat`` / ``epsm_film_develop``) w.r.t. the radiance of
-    every sample: image[p] = sum_i w_ip L_i / W_p, so dL_i = sum_p grad[p] w_ip / W_p -- the box filter touches the
-    pixel under the sample, the gaussian (stddev 0.5, radius 2, src/rfilters/gaussian.cpp) its 5x5 window.
-    ``film_pos (n,2)``, ``grad_img (H,W,3)``, ``weight_img (H,W)`` = W_p of the primal pass; returns ``(n,3)``."""
-    H, W = weight_img.shape
-    g = grad_img[..., :3] / weight_img.clamp_min(1e-30)[..., None]
-    g = torch.where((weight_img > 0)[..., None], g, torch.zeros_like(g))
-    if rfilter == 0:                                      # EPSM_RFILTER_BOX
-        X, Y, ok = _box_window(film_pos, H, W)
-        return g[Y.clamp(0, H - 1), X.clamp(0, W - 1)] * ok[:, None]
-    xs, ys, wx, wy = _gaussian_window(film_pos, H, W)
-    gw = g[ys.clamp(0, H - 1)[:, :, None], xs.clamp(0, W - 1)[:, None, :]]      # (n,5,5,3)
-    return (gw * (wy[:, :, None] * wx[:, None, :])[..., None]).sum(dim=(1, 2))
-
-
-_WEIGHT_ONE = float(1 << 40)
-
-
-def film_weight_counts(counts: torch.Tensor, film_pos: torch.Tensor, rfilter: int) -> None:
-    """The film's weight channel W_p = sum_i w_ip of a tile's samples in FIXED POINT: adds round(w_ip 2^40) to ``counts`` (H,W)
-    int64.  Integer addition is associative, so the sums are the same bits in whatever order the adds land -- unlike the float
-    atomics of ``epsm_film_splat``, whose weight channel differs in its last bits from call to call.  The roughness adjoint is
-    summed without atomics so that a call repeats bit for bit; the adjoint radiance it is fed divides by W_p, so W_p must repeat
-    too.  (2^-40 per sample is far below float32's resolution; 2^23 samples of weight 1 fit a pixel.)"""
-    H, W = counts.shape
-    flat = counts.view(-1)
-    if rfilter == 0:                                      # EPSM_RFILTER_BOX
-        X, Y, ok = _box_window(film_pos, H, W)
-        flat.index_add_(0, Y.clamp(0, H - 1) * W + X.clamp(0, W - 1), ok.long() << 40)
-        return
-    xs, ys, wx, wy = _gaussian_window(film_pos, H, W)
-    w = torch.round((wy[:, :, None] * wx[:, None, :]).double() * _WEIGHT_ONE).long()              # (n,5,5)
-    idx = ys.clamp(0, H - 1)[:, :, None] * W + xs.clamp(0, W - 1)[:, None, :]
-    flat.index_add_(0, idx.reshape(-1), w.reshape(-1))
-
-
-def film_adjoint_reparam(film_pos: torch.Tensor, radiance: torch.Tensor, grad_img: torch.Tensor, accum: torch.Tensor):
-    """Adjoint of the gaussian splat + weight division w.r.t. a sample's radiance, its FILM POSITION and the determinant
-    of the reparameterisation that multiplies both its value and its weight (common.py:880-920):
-        image[p] = sum_i w_ip L_i det_i / sum_i w_ip det_i,   w_ip = f(p - pos_i)
-    ``accum (H,W,4)``: the film [r,g,b,w] of the primal pass.  Returns ``dL (n,3)`` and ``adj (n,3)`` =
-    [d loss / d pos.x, d loss / d pos.y, d loss / d det] at det = 1.
-    On the GPU: ONE kernel (``epsm_film_adjoint_reparam``, include/epsm_trace.h); the torch form below is what it is checked
-    against (tests/test_gpu_reparam.py) and what the host build of the tracer runs with."""
-    if film_pos.is_cuda:
-        import ctypes as C
-        from . import _lib
-        n = int(film_pos.shape[0])
-        fp, rad = film_pos.detach().float().contiguous(), radiance.detach().float().contiguous()
-        g, acc = grad_img.detach().float().contiguous(), accum.detach().float().contiguous()
-        dL = torch.empty((n, 3), device=film_pos.device, dtype=torch.float32)
-        adj = torch.empty((n, 3), device=film_pos.device, dtype=torch.float32)
-        stream = _lib.stream(film_pos.device)
-        _lib.check(_lib.lib().epsm_film_adjoint_reparam(n, fp.data_ptr(), rad.data_ptr(), g.data_ptr(), int(g.shape[-1]), acc.data_ptr(),
-                                                         int(acc.shape[1]), int(acc.shape[0]), dL.data_ptr(), adj.data_ptr(),
-                                                         C.c_void_p(stream)), "epsm_film_adjoint_reparam")
-        return dL, adj
-    return film_adjoint_reparam_torch(film_pos, radiance, grad_img, accum)
-
-
-def film_adjoint_reparam_torch(film_pos: torch.Tensor, radiance: torch.Tensor, grad_img: torch.Tensor, accum: torch.Tensor):
-    """``film_adjoint_reparam`` as dense torch operations (the checker of the HIP kernel; the CPU path of the host harness)."""
-    H, W = accum.shape[:2]
-    Wp = accum[..., 3]
-    ok = (Wp > 0)[..., None]
-    inv = torch.where(ok, 1.0 / Wp.clamp_min(1e-30)[..., None], torch.zeros_like(accum[..., :1]))
-    g = grad_img[..., :3] * inv                                     # grad / W_p
-    gi = (g * (accum[..., :3] * inv)).sum(-1)                       # (grad . image) / W_p
-    px, py = film_pos[:, 0], film_pos[:, 1]
-    X, Y = torch.floor(px).long(), torch.floor(py).long()
-    radius, alpha = 2.0, -1.0 / (2.0 * 0.5 * 0.5)
-    bias = math.exp(alpha * radius * radius)
-    off = torch.arange(-2, 3, device=film_pos.device)
-    xs, ys = X[:, None] + off[None, :], Y[:, None] + off[None, :]
-    dx, dy = (xs.float() + 0.5) - px[:, None], (ys.float() + 0.5) - py[:, None]
-
-    def weights(d_, inside):
-        e = torch.exp(alpha * d_ * d_)
-        w = (e - bias).clamp_min(0)
-        live = (d_.abs() <= radius) & inside & (w > 0)
-        w = torch.where(live, w, torch.zeros_like(w))
-        dw = torch.where(live, -2.0 * alpha * d_ * e, torch.zeros_like(w))      # d w / d pos  (d_ = pixel centre - pos)
-        return w, dw
-    wx, dwx = weights(dx, (xs >= 0) & (xs < W))
-    wy, dwy = weights(dy, (ys >= 0) & (ys < H))
-    yi, xi = ys.clamp(0, H - 1)[:, :, None], xs.clamp(0, W - 1)[:, None, :]
-    gw = g[yi, xi]                                                   # (n,5,5,3)
-    A = (gw * radiance[:, None, None, :]).sum(-1) - gi[yi, xi]       # (n,5,5): grad_p . (L_i - image_p) / W_p
-    w2 = wy[:, :, None] * wx[:, None, :]
-    dL = (gw * w2[..., None]).sum(dim=(1, 2))
-    adj = torch.stack([(A * (wy[:, :, None] * dwx[:, None, :])).sum(dim=(1, 2)),
-                       (A * (dwy[:, :, None] * wx[:, None, :])).sum(dim=(1, 2)), (A * w2).sum(dim=(1, 2))], dim=1)
-    return dL.contiguous(), adj.contiguous()
-
-
-def film_splat_tangent(d_accum: torch.Tensor, film_pos: torch.Tensor, radiance: torch.Tensor, d_radiance: torch.Tensor,
-                       d_film: Optional[torch.Tensor], rfilter: int) -> None:
-    """Forward mode of splat + weight division, the transpose of ``film_adjoint_reparam`` (and, with ``d_film`` None, of
-    ``film_adjoint``): ACCUMULATES into ``d_accum (H,W,4)``, per pixel p,
-        dA_p += (grad f(p - pos_i) . d pos_i + f d det_i) L_i + f d L_i,    dW_p += grad f . d pos_i + f d det_i
-    for the samples' film positions (n,2), radiance (n,3) and tangents ``d_radiance (n,3)``, ``d_film (n,3)`` = [d pos.x, d pos.y,
-    d det] (None: the samples do not move).  ``develop_tangent`` turns the film and this into the image's tangent.
-    On the GPU: ONE kernel (``epsm_film_splat_tangent``, include/epsm_trace.h); the torch form is its checker and the CPU path."""
-    if film_pos.is_cuda:
-        import ctypes as C
-        from . import _lib
-        n = int(film_pos.shape[0])
-        fp, rad, drad = film_pos.detach().float().contiguous(), radiance.detach().float().contiguous(), d_radiance.detach().float().contiguous()
-        dfilm = None if d_film is None else d_film.detach().float().contiguous()
-        assert d_accum.is_contiguous() and d_accum.dtype == torch.float32
-        _lib.check(_lib.lib().epsm_film_splat_tangent(n, fp.data_ptr(), rad.data_ptr(), drad.data_ptr(),
-                                                       None if dfilm is None else dfilm.data_ptr(), int(d_accum.shape[1]),
-                                                       int(d_accum.shape[0]), int(rfilter), d_accum.data_ptr(),
-                                                       C.c_void_p(_lib.stream(film_pos.device))), "epsm_film_splat_tangent")
-        return
-    d_accum += film_splat_tangent_torch(film_pos, radiance, d_radiance, d_film, d_accum.shape[0], d_accum.shape[1], rfilter)
-
-
-def film_splat_tangent_torch(film_pos: torch.Tensor, radiance: torch.Tensor, d_radiance: torch.Tensor, d_film: Optional[torch.Tensor],
-                             H: int, W: int, rfilter: int) -> torch.Tensor:
-    """``film_splat_tangent`` as dense torch operations: returns the (H,W,4) tangent film of the samples."""
-    out = torch.zeros((H * W, 4), device=film_pos.device, dtype=torch.float32)
-    px, py = film_pos[:, 0], film_pos[:, 1]
-    X, Y = torch.floor(px).long(), torch.floor(py).long()
-    if rfilter == 0:                                      # EPSM_RFILTER_BOX: the weight does not move with the sample
-        if d_film is not None:
-            raise ValueError("film_splat_tangent: a box filter has no derivative in the film position")
-        ok = (X >= 0) & (Y >= 0) & (X < W) & (Y < H)
-        out[:, :3].index_add_(0, (Y * W + X)[ok], d_radiance[ok].float())
-        return out.view(H, W, 4)
-    radius, alpha = 2.0, -1.0 / (2.0 * 0.5 * 0.5)
-    bias = math.exp(alpha * radius * radius)
-    off = torch.arange(-2, 3, device=film_pos.device)
-    xs, ys = X[:, None] + off[None, :], Y[:, None] + off[None, :]
-    dx, dy = (xs.float() + 0.5) - px[:, None], (ys.float() + 0.5) - py[:, None]
-
-    def weights(d_, inside):
-        e = torch.exp(alpha * d_ * d_)
-        w = (e - bias).clamp_min(0)
-        live = (d_.abs() <= radius) & inside & (w > 0)
-        return torch.where(live, w, torch.zeros_like(w)), torch.where(live, -2.0 * alpha * d_ * e, torch.zeros_like(w))
-    wx, dwx = weights(dx, (xs >= 0) & (xs < W))
-    wy, dwy = weights(dy, (ys >= 0) & (ys < H))
-    w2 = wy[:, :, None] * wx[:, None, :]                                     # (n,5,5)
-    if d_film is None:
-        dw = torch.zeros_like(w2)
-    else:
-        fx, fy, fd = d_film[:, 0, None, None], d_film[:, 1, None, None], d_film[:, 2, None, None]
-        dw = wy[:, :, None] * dwx[:, None, :] * fx + dwy[:, :, None] * wx[:, None, :] * fy + w2 * fd
-    rgb = dw[..., None] * radiance[:, None, None, :] + w2[..., None] * d_radiance[:, None, None, :]
-    inside = ((ys >= 0) & (ys < H))[:, :, None] & ((xs >= 0) & (xs < W))[:, None, :]
-    idx = (ys.clamp(0, H - 1)[:, :, None] * W + xs.clamp(0, W - 1)[:, None, :])[inside]
-    out.index_add_(0, idx, torch.cat([rgb, dw[..., None]], dim=-1)[inside])
-    return out.view(H, W, 4)
-
-
-def develop_tangent(accum: torch.Tensor, d_accum: torch.Tensor) -> torch.Tensor:
-    """The tangent of the developed image A / W: (dA - image dW) / W, zero where the primal film has no weight."""
-    Wp = accum[..., 3:4]
-    inv = torch.where(Wp > 0, 1.0 / Wp.clamp_min(1e-30), torch.zeros_like(Wp))
-    return (d_accum[..., :3] - accum[..., :3] * inv * d_accum[..., 3:4]) * inv
+def _refuse_box_filter(sensor) -> None:
+    if sensor.rfilter == 0:
+        raise Exception("ADIntegrator detected the potential for image-space motion due to differentiable shape or camera "
+                        "pose parameters. This is, however, incompatible with the box reconstruction filter that is "
+                        "currently used. Please specify a smooth reconstruction filter in your scene description (e.g. "
+                        "'gaussian', which is actually the default)")          # common.py:379-388
 
 
 def _develop_forward(scene, sensor: int, films) -> torch.Tensor:
-    """Sums the image tangents of the (primal film, tangent film) pairs of a forward pass; with several ranks ONE all-reduce of
-    all of them first."""
+    """Sums the image tangents of the (primal film, tangent film) pairs of a forward pass (None: a pass that had nothing
+    attached); with several ranks ONE all-reduce of all of them first."""
     s = scene.sensors[min(sensor, len(scene.sensors) - 1)]
     out = torch.zeros((s.height, s.width, 3), device=scene.device, dtype=torch.float32)
+    films = [pair for pair in films if pair is not None]
     if not films:
         return out
     _, world = _dist.world()
@@ -483,27 +325,23 @@ class _TexelBuffers:
             o += 3 * h * w
 
 
-def _texture_scratch(scene, params: ParamGrads) -> _TexelBuffers:
+def _texture_shapes(scene, params: ParamGrads, what: str):
+    """The shapes of the attached textures; ``params`` (``what``: "gradient buffer" / "tangent") must be laid out for them."""
     shapes = scene.texture_shapes()
-    if list(getattr(params, "tex_shapes", [])) != list(shapes):
-        raise ValueError("texture slots are attached: the gradient buffer must come from Scene.param_grads() after attach_texture")
-    return _TexelBuffers(shapes, scene.device)
+    if params.tex_shapes != list(shapes):
+        raise ValueError(f"texture slots are attached: the {what} must come from Scene.param_grads() after attach_texture")
+    return shapes
 
 
 def _texture_tangents(scene, params: ParamGrads):
     """The texel tangents the forward replay reads, per slot: the bitmap's tangent (``ParamGrads.texture``) times its scale."""
-    shapes = scene.texture_shapes()
-    if list(getattr(params, "tex_shapes", [])) != list(shapes):
-        raise ValueError("texture slots are attached: the tangent must come from Scene.param_grads() after attach_texture")
+    shapes = _texture_shapes(scene, params, "tangent")
     return [(params.texture(k).to(scene.device, torch.float32) * scene.texture_scale(k)).contiguous() for k in range(len(shapes))]
 
 
 def _alpha_slots(scene, params: ParamGrads) -> int:
     """The number of roughness slots the colour adjoint serves (``Scene.attach_alpha``); ``params.alpha`` must hold them."""
-    n = len(getattr(scene, "alpha_slots", None) or {})
-    if n and not hasattr(scene, "trace_alpha_backward"):
-        raise NotImplementedError("roughness slots are attached to a scene object without Scene.trace_alpha_backward: the colour "
-                                  "adjoint cannot differentiate them (and does not drop them)")
+    n = len(scene.alpha_slots)
     if n:
         scene._alpha_slot_count()                   # (refuses more than EPSM_MAX_ALPHA_GRADS)
         if params.B < n:
@@ -511,33 +349,64 @@ def _alpha_slots(scene, params: ParamGrads) -> int:
     return n
 
 
-def _rigid_slot_count(scene, params: ParamGrads) -> int:
-    """The number of rigid slots (``Scene.attach_rigid``); ``params.rigid`` must hold them."""
-    n = len(getattr(scene, "rigid_slots", None) or [])
-    if n and getattr(params, "R", 0) < n:
+def _rigid_slot_count(rigid_slots, params: ParamGrads) -> int:
+    """The number of rigid slots (``Scene.rigid_slots``, from ``Scene.attach_rigid``); ``params.rigid`` must hold them."""
+    n = len(rigid_slots)
+    if n and params.R < n:
         raise ValueError("rigid slots are attached: the gradient buffer must come from Scene.param_grads() after attach_rigid")
     return n
 
 
-def _rigid_backward(scene, params: ParamGrads, contrib: ParamGrads) -> None:
-    """``params.rigid`` += [force, torque] of every rigid slot over ONE call's contribution to the vertex rows, after its sum
+def _rigid_backward(scene, params: ParamGrads, contrib: ParamGrads, n: int) -> None:
+    """``params.rigid`` += [force, torque] of the ``n`` rigid slots over ONE call's contribution to the vertex rows, after its sum
     over the ranks (``epsm_rigid_reduce``: float64, a fixed order -- every rank adds the same bits)."""
-    n = _rigid_slot_count(scene, params)
     if n:
         with _prof.phase("epsm.render_backward.rigid_reduce"):
             scene.rigid_reduce(contrib.pos, contrib.nrm, params.rigid[:n], *scene.rigid_tables())
 
 
-def _sensor_pose_refusals(scene) -> bool:
-    """Whether the sensor's rotation is attached; refuses what the every-shape-moves argument cannot carry."""
-    if any(e["type"] == 1 for e in scene.emitter_desc):
-        raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
-                                  "sensor's gradient; scenes with point emitters keep the sensor fixed")
-    rot = bool(getattr(scene, "sensor_rotation", False))
-    if rot and any(e["type"] == 3 for e in scene.emitter_desc):
-        raise NotImplementedError("prb_reparam: an `envmap` would have to turn with the shapes for the gradient of the sensor's "
-                                  "rotation; scenes with an envmap take attach_sensor(rotation=False)")
-    return rot
+@contextmanager
+def _call_contribution(scene, params: ParamGrads, n_rigid: int, add: Optional[Callable[[ParamGrads], None]] = None):
+    """The buffer ONE ``render_backward`` writes its geometry gradients into.  dr.backward ACCUMULATES into the gradients that
+    are already there, and with more than one rank only THIS call's contribution may be summed over the ranks: what ``params``
+    held on entry is already a sum over the ranks (or the caller's own data) and must not be multiplied by the world size.  The
+    rigid slots reduce this call's contribution too, and the sensor's pass (``add``) sums every vertex row of it.  So: ``params``
+    itself with one rank, no rigid slot and no ``add``; else ``params.scratch()``, and on exit, in this order, ONE all-reduce
+    of the whole buffer when there are several ranks, ``params.flat += `` it (or ``add(contribution)`` in its place), the
+    rigid slots' reduction."""
+    world = _dist.world()[1]
+    if world == 1 and not n_rigid and add is None:
+        yield params
+        return
+    target = params.scratch()
+    yield target
+    if world > 1:
+        with _prof.phase("epsm.render_backward.allreduce"):
+            _dist.allreduce_param_grads(target.flat)
+    if add is None:
+        params.flat += target.flat
+    else:
+        add(target)
+    _rigid_backward(scene, params, target, n_rigid)
+
+
+def _pose_attached(scene, params: ParamGrads, what: str):
+    """(sensor attached?, its rotation too?, number of rigid slots) of a `prb_reparam` call.  Refuses what the every-shape-moves
+    argument of the sensor's pass cannot carry, and a ``params`` (``what``: "gradient buffer" / "tangent") laid out before the
+    rotation or the slots were attached -- before any pass runs: a refused call leaves nothing behind."""
+    cam = rot = False
+    if scene.sensor_attached:
+        if any(e["type"] == 1 for e in scene.emitter_desc):
+            raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
+                                      "sensor's gradient; scenes with point emitters keep the sensor fixed")
+        cam, rot = True, scene.sensor_rotation
+        if rot and any(e["type"] == 3 for e in scene.emitter_desc):
+            raise NotImplementedError("prb_reparam: an `envmap` would have to turn with the shapes for the gradient of the sensor's "
+                                      "rotation; scenes with an envmap take attach_sensor(rotation=False)")
+        if rot and params.cam_rotation is None:
+            raise ValueError(f"the sensor's rotation is attached: the {what} must come from Scene.param_grads() after "
+                             "attach_sensor(rotation=True)")
+    return cam, rot, _rigid_slot_count(scene.rigid_slots, params)
 
 
 class _EveryMeshAttached:
@@ -546,7 +415,7 @@ class _EveryMeshAttached:
 
     def __init__(self, scene, normals: bool):
         self.scene, self.normals = scene, normals
-        self.was = [(m, bool(getattr(m, "pos_attached", False)), bool(getattr(m, "nrm_attached", False))) for m in scene.meshes]
+        self.was = [(m, bool(m.pos_attached), bool(m.nrm_attached)) for m in scene.meshes]
 
     def __enter__(self):
         for m, _, n in self.was:
@@ -578,16 +447,13 @@ class PRBIntegrator:
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
-        max_depth = props.get("max_depth", 6)
-        if max_depth < 0 and max_depth != -1:
-            raise Exception("\"max_depth\" must be set to -1 (infinite) or a value >= 0")
-        self.max_depth = max_depth
-        self.rr_depth = props.get("rr_depth", 5)
+        self.max_depth = _max_depth_property(props)
+        self.rr_depth = props.get("rr_depth", 5)        # (not validated here: the C entries refuse rr_depth < 1)
 
     def _depth(self) -> int:
         """Depth of BOTH passes: ``epsm_trace_paths_color`` replays at most 6 bounces, and the image the adjoint is paired
         with must come from the same estimator (render() went to the full max_depth, the replay to 6)."""
-        return 6 if self.max_depth < 0 else min(int(self.max_depth), 6)
+        return _replay_depth(self.max_depth)
 
     def to_string(self):
         return f"PRBIntegrator[max_depth = {self.max_depth}, rr_depth = {self.rr_depth}, reparam = False]"
@@ -608,11 +474,19 @@ class PRBIntegrator:
         """common.py:118-197: the image's tangent d image / d theta . delta theta (H,W,3) for the tangent ``params`` (its
         ``color`` rows: the attached colour parameters), under the estimator and the random numbers of ``render`` /
         ``render_backward`` with the same seed and spp -- the exact transpose of ``render_backward``."""
-        films = []
-        c = self._color_forward(scene, params, sensor, seed, spp)
-        if c is not None:
-            films.append(c)
-        return _develop_forward(scene, sensor, films)
+        return _develop_forward(scene, sensor, [self._color_forward(scene, params, sensor, seed, spp)])
+
+    def _color_attached(self, scene, params: ParamGrads):
+        """(anything for the colour pass?, textures attached?, number of roughness slots).  Neither a colour, a texture nor a
+        roughness attached is nothing this phase differentiates: skipped -- and refused by `prb` when geometry is attached instead."""
+        texs = bool(scene.texture_slots)
+        n_alpha = _alpha_slots(scene, params)
+        if not scene.color_slots and not texs and not n_alpha and not self.reparam and scene.has_attached_geometry():
+            raise NotImplementedError(
+                "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
+                "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
+                "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
+        return bool(scene.color_slots or texs or n_alpha), texs, n_alpha
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
@@ -621,28 +495,16 @@ class PRBIntegrator:
         (primal film, tangent film), or None when neither a colour, a texture nor a roughness is attached.  (The tangent film is
         developed with the film's own float-atomic weights, while the backward pass of a call with a roughness divides by their
         fixed-point sums: ~1e-7 apart, far inside the transpose identity's bound.)"""
-        texs = bool(getattr(scene, "texture_slots", None))
-        n_alpha = _alpha_slots(scene, params)
-        if not getattr(scene, "color_slots", None) and not texs and not n_alpha:
-            if self.reparam:
-                return None
-            if getattr(scene, "has_attached_geometry", lambda: False)():
-                raise NotImplementedError(
-                    "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
-                    "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
-                    "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
+        any_attached, texs, n_alpha = self._color_attached(scene, params)
+        if not any_attached:
             return None
-        si = min(sensor, len(scene.sensors) - 1)
-        s = scene.sensors[si]
-        spp = spp or s.spp
-        rank, world = _dist.world()
-        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+        si, s, spp, _, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         d_accum = torch.zeros_like(accum)
         values = scene.color_values()                                   # (C,3)
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
         tex_t = _texture_tangents(scene, params) if texs else None
         alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
-        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "color", rank, world):
+        for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
             dL = (sums * t[None]).sum(dim=1)                            # (n,3)
@@ -654,24 +516,11 @@ class PRBIntegrator:
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        texs = bool(getattr(scene, "texture_slots", None))
-        n_alpha = _alpha_slots(scene, params)
-        if not getattr(scene, "color_slots", None) and not texs and not n_alpha:
-            if self.reparam:
-                return
-            if getattr(scene, "has_attached_geometry", lambda: False)():
-                raise NotImplementedError(
-                    "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
-                    "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
-                    "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
-            return                                  # nothing attached that this phase differentiates
-        si = min(sensor, len(scene.sensors) - 1)
-        s = scene.sensors[si]
-        spp = spp or s.spp
-        rank, world = _dist.world()
-        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+        any_attached, texs, n_alpha = self._color_attached(scene, params)
+        if not any_attached:
+            return
+        si, s, spp, world, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         kept, counts = [], None
-        tiles = scene.tile_plan(s.wavefront_size(spp), "color", rank, world)
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
@@ -689,7 +538,7 @@ class PRBIntegrator:
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
-        tex = _texture_scratch(scene, params) if texs else None
+        tex = _TexelBuffers(_texture_shapes(scene, params, "gradient buffer"), scene.device) if texs else None
         d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
@@ -742,31 +591,26 @@ class PRBReparamIntegrator(PRBIntegrator):
     __repr__ = to_string
 
     def render_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        cam = bool(getattr(scene, "sensor_attached", False))
-        rot = _sensor_pose_refusals(scene) if cam else False          # (before the colour pass: a refused call leaves nothing behind)
-        if rot and getattr(params, "cam_rotation", None) is None:
-            raise ValueError("the sensor's rotation is attached: the gradient buffer must come from Scene.param_grads() after "
-                             "attach_sensor(rotation=True)")
-        _rigid_slot_count(scene, params)
+        cam, rot, n_rigid = _pose_attached(scene, params, "gradient buffer")
         self._color_backward(scene, params, grad_in, sensor, seed, spp)
-        if not scene.has_attached_geometry() and not cam:
+        if not cam:
+            if scene.has_attached_geometry():
+                with _call_contribution(scene, params, n_rigid) as target:
+                    self._geometry_backward(scene, target, grad_in, sensor, seed, spp)
             return
-        if cam:
-            # Moving the sensor by t moves every shape (and every emitter that is one) by -t as the sensor sees it; environment
-            # emitters do not care.  So d loss / d sensor position = - sum over ALL vertices of d loss / d vertex position: the
-            # same reparameterised pass with every mesh attached, summed (the primary rays' warp field carries the silhouettes).
-            # Its rotation likewise: the sensor turning by omega about its position o is every shape turning by -omega about o, so
-            # d loss / d omega = - the torque about o of all vertex rows, normals included; a `constant` environment does not care.
-            # Both are ONE slot of epsm_rigid_reduce over every vertex with pivot o.
-            with _EveryMeshAttached(scene, normals=rot) as every:
-                full = ParamGrads(params.V, params.B, device=params.flat.device, mesh_slices=params.mesh_slices, n_colors=params.C,
-                                  tex_shapes=getattr(params, "tex_shapes", None))
-                self._geometry_backward(scene, full, grad_in, sensor, seed, spp)
+        # Moving the sensor by t moves every shape (and every emitter that is one) by -t as the sensor sees it; environment
+        # emitters do not care.  So d loss / d sensor position = - sum over ALL vertices of d loss / d vertex position: the
+        # same reparameterised pass with every mesh attached, summed (the primary rays' warp field carries the silhouettes).
+        # Its rotation likewise: the sensor turning by omega about its position o is every shape turning by -omega about o, so
+        # d loss / d omega = - the torque about o of all vertex rows, normals included; a `constant` environment does not care.
+        # Both are ONE slot of epsm_rigid_reduce over every vertex with pivot o.
+        every = _EveryMeshAttached(scene, normals=rot)
+
+        def add_sensor_pass(full: ParamGrads) -> None:
             o = scene.sensors[min(sensor, len(scene.sensors) - 1)].to_world[:3, 3]
             twist = torch.zeros((1, 6), device=full.flat.device, dtype=torch.float32)
             ranges, pivots = scene.rigid_tables(extra=[(0, params.V, o)])
-            k = len(getattr(scene, "rigid_slots", None) or [])
-            scene.rigid_reduce(full.pos, full.nrm if rot else None, twist, ranges[k:], pivots[k:])
+            scene.rigid_reduce(full.pos, full.nrm if rot else None, twist, ranges[n_rigid:], pivots[n_rigid:])
             params.cam_origin -= twist[0, :3]
             if rot:
                 params.cam_rotation -= twist[0, 3:]
@@ -776,30 +620,16 @@ class PRBReparamIntegrator(PRBIntegrator):
                     params.pos[lo:hi] += full.pos[lo:hi]
                 if n:
                     params.nrm[lo:hi] += full.nrm[lo:hi]
-            _rigid_backward(scene, params, full)
-            return
-        if _rigid_slot_count(scene, params):
-            contrib = params.scratch()                         # this call's contribution alone: what the rigid slots reduce
-            self._geometry_backward(scene, contrib, grad_in, sensor, seed, spp)
-            params.flat += contrib.flat
-            _rigid_backward(scene, params, contrib)
-            return
-        self._geometry_backward(scene, params, grad_in, sensor, seed, spp)
+        with _call_contribution(scene, params, n_rigid, add=add_sensor_pass) as full:
+            with every:
+                self._geometry_backward(scene, full, grad_in, sensor, seed, spp)
 
     def render_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0) -> torch.Tensor:
         """The transpose of ``render_backward``: the colour part of ``PRBIntegrator.render_forward`` plus the reparameterised
         forward pass (``Scene.trace_reparam_forward``) for the tangents of the attached meshes' vertex positions / normals and,
         with ``Scene.attach_sensor``, of the sensor's position (``params.cam_origin``)."""
-        films = []
-        cam = bool(getattr(scene, "sensor_attached", False))
-        rot = _sensor_pose_refusals(scene) if cam else False          # (before the colour pass, as the backward pass refuses)
-        if rot and getattr(params, "cam_rotation", None) is None:
-            raise ValueError("the sensor's rotation is attached: the tangent must come from Scene.param_grads() after "
-                             "attach_sensor(rotation=True)")
-        n_rigid = _rigid_slot_count(scene, params)
-        c = self._color_forward(scene, params, sensor, seed, spp)
-        if c is not None:
-            films.append(c)
+        cam, rot, n_rigid = _pose_attached(scene, params, "tangent")
+        films = [self._color_forward(scene, params, sensor, seed, spp)]
         if not scene.has_attached_geometry() and not cam:
             return _develop_forward(scene, sensor, films)
         dev = scene.device
@@ -817,34 +647,23 @@ class PRBReparamIntegrator(PRBIntegrator):
         tan_nrm = torch.zeros((params.V, 3), device=dev, dtype=torch.float32) if rot else own(params.nrm)
         for m in scene.meshes:
             lo, hi = params.mesh_slices[m.name]
-            if cam and getattr(m, "pos_attached", False):
+            if cam and m.pos_attached:
                 tan_pos[lo:hi] += params.pos[lo:hi].to(dev, torch.float32)
-            if rot and getattr(m, "nrm_attached", False):
+            if rot and m.nrm_attached:
                 tan_nrm[lo:hi] += params.nrm[lo:hi].to(dev, torch.float32)
         if twists:
             ranges, pivots = scene.rigid_tables(extra=extra)
             scene.rigid_expand(torch.cat(twists).contiguous(), tan_pos, tan_nrm, ranges, pivots)
-        if cam:
-            with _EveryMeshAttached(scene, normals=rot):
-                films.append(self._geometry_forward(scene, tan_pos, tan_nrm, sensor, seed, spp))
-        else:
+        with _EveryMeshAttached(scene, normals=rot) if cam else nullcontext():
             films.append(self._geometry_forward(scene, tan_pos, tan_nrm, sensor, seed, spp))
         return _develop_forward(scene, sensor, films)
 
     def _geometry_forward(self, scene, tan_pos: torch.Tensor, tan_nrm: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_geometry_backward``: this rank's (primal film, tangent film) of the reparameterised pass."""
-        si = min(sensor, len(scene.sensors) - 1)
-        s = scene.sensors[si]
-        if s.rfilter == 0:
-            raise Exception("ADIntegrator detected the potential for image-space motion due to differentiable shape or camera "
-                            "pose parameters. This is, however, incompatible with the box reconstruction filter that is "
-                            "currently used. Please specify a smooth reconstruction filter in your scene description (e.g. "
-                            "'gaussian', which is actually the default)")          # common.py:379-388
-        spp = spp or s.spp
-        rank, world = _dist.world()
-        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
+        si, s, spp, _, accum, tiles = _pass_frame(scene, sensor, spp, "reparam")
+        _refuse_box_filter(s)
         d_accum = torch.zeros_like(accum)
-        for lo, hi in scene.tile_plan(s.wavefront_size(spp), "reparam", rank, world):
+        for lo, hi in tiles:
             with _prof.phase("epsm.prb_reparam.primal_pass"):
                 tr = scene._trace(si, seed, spp, self._depth(), 0, lo, hi)
                 scene.film_splat(accum, s, tr.film_pos, tr.radiance)
@@ -857,19 +676,12 @@ class PRBReparamIntegrator(PRBIntegrator):
                 film_splat_tangent(d_accum, tr.film_pos, radiance, d_rad, d_film, s.rfilter)
         return accum, d_accum
 
-    def _geometry_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        si = min(sensor, len(scene.sensors) - 1)
-        s = scene.sensors[si]
-        if s.rfilter == 0:
-            raise Exception("ADIntegrator detected the potential for image-space motion due to differentiable shape or camera "
-                            "pose parameters. This is, however, incompatible with the box reconstruction filter that is "
-                            "currently used. Please specify a smooth reconstruction filter in your scene description (e.g. "
-                            "'gaussian', which is actually the default)")          # common.py:379-388
-        spp = spp or s.spp
-        rank, world = _dist.world()
+    def _geometry_backward(self, scene, out: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
+        """Adds this rank's vertex gradients of the reparameterised pass to ``out.pos`` / ``out.nrm``: the caller's buffer of one
+        call's contribution (``_call_contribution`` sums it over the ranks)."""
+        si, s, spp, world, accum, tiles = _pass_frame(scene, sensor, spp, "reparam")
+        _refuse_box_filter(s)
         # pass 1 (common.py:872-882): the primal estimate of every sample and the film they make
-        accum = torch.zeros((s.height, s.width, 4), device=scene.device, dtype=torch.float32)
-        tiles = scene.tile_plan(s.wavefront_size(spp), "reparam", rank, world)
         kept = []
         for lo, hi in tiles:
             with _prof.phase("epsm.prb_reparam.primal_pass"):
@@ -880,7 +692,6 @@ class PRBReparamIntegrator(PRBIntegrator):
             _dist.allreduce_param_grads(accum)
         # pass 2 (common.py:944-955): adjoint radiance, adjoint film position / determinant, the reparameterised replay
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
-        out = params.scratch() if world > 1 else params
         for lo, hi in tiles:
             film_pos, radiance = kept.pop(0)
             with _prof.phase("epsm.prb_reparam.film_adjoint"):
@@ -889,9 +700,6 @@ class PRBReparamIntegrator(PRBIntegrator):
                 scene.trace_reparam(si, seed, spp, self._depth(), lo, hi, radiance, dL, adj, out.pos, out.nrm,
                                     int(self.reparam_max_depth), self.reparam_rays, self.reparam_kappa, self.reparam_exp,
                                     antithetic=self.reparam_antithetic)
-        if world > 1:
-            _dist.allreduce_param_grads(out.flat)
-            params.flat += out.flat
 
 
 # -- plugin registry (mi.register_integrator / mi.load_dict) -------------------

@@ -45,6 +45,7 @@ class ParamGrads:
         self.rigid = self.flat[n1: n1 + 6 * self.R].view(self.R, 6) if self.R else None
         self.cam_rotation = self.flat[n1 + 6 * self.R: n] if self.has_cam_rotation else None
         self.mesh_slices = dict(mesh_slices or {})
+        self._scratch: Optional[ParamGrads] = None             # scratch(): allocated on first use
 
     def zero_(self):
         self.flat.zero_()
@@ -53,7 +54,7 @@ class ParamGrads:
     def scratch(self) -> "ParamGrads":
         """A zeroed buffer of the same layout (allocated once, cleared on every call): what ONE backward pass
         contributes before it is summed over the ranks and added to the accumulated gradients."""
-        s = getattr(self, "_scratch", None)
+        s = self._scratch
         if s is None:
             s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C,
                                            tex_shapes=self.tex_shapes, n_rigid=self.R, cam_rotation=self.has_cam_rotation)

@@ -353,6 +353,7 @@ class Mesh:
         self.bsdf, self.emitter = bsdf, emitter
         self.flip_normals, self.is_mesh = flip_normals, is_mesh
         self.pos_attached = self.nrm_attached = False
+        self.host_stale = False                    # set when the vertices moved on the device: v / n are then refreshed on demand
 
     def flags(self) -> int:
         return ((MESH_VERTEX_NORMALS if self.has_normals else 0) | (MESH_FLIP_NORMALS if self.flip_normals else 0) |
@@ -727,6 +728,7 @@ class Scene:
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
         self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoint: ("bsdf" | "envmap", index)
         self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
+        self.sensor_attached = self.sensor_rotation = False     # attach_sensor
         self._rigid_tables = {}                    # (ranges, pivots) -> their device tensors
         self.emitter_names = [f"emitter{i}" for i in range(len(self.emitter_desc))]     # (from_dict: the scene dict's keys)
         self.rr_depth = 5
@@ -886,8 +888,7 @@ class Scene:
         """What `dr.enable_grad` changes on the device: the mode bits of the meshes -- in the mesh table the tracer reads and
         in the last column of the triangle table the gradient kernels read.  Rewritten IN PLACE (the scene struct's pointers
         stay valid); nothing else of the upload is repeated."""
-        if (getattr(self, "_mesh_structs", None) is None or getattr(self, "tri_table", None) is None
-                or (sync_host and any(getattr(m, "host_stale", False) for m in self.meshes))):   # (vertices moved on the device: the full upload syncs the host copies)
+        if sync_host and any(m.host_stale for m in self.meshes):   # (vertices moved on the device: the full upload syncs the host copies)
             return self._upload()
         for c, m in zip(self._mesh_structs, self.meshes):
             c.flags = m.flags()
@@ -964,7 +965,7 @@ class Scene:
 
     def has_attached_geometry(self) -> bool:
         """Any mesh whose vertex positions / normals receive gradients?"""
-        return any(getattr(m, "pos_attached", False) or getattr(m, "nrm_attached", False) for m in self.meshes)
+        return any(m.pos_attached or m.nrm_attached for m in self.meshes)
 
     def attach_alpha(self, bsdf_name: str) -> int:
         i = self.bsdf_names.index(bsdf_name)
@@ -1177,7 +1178,7 @@ class Scene:
 
     def _sync_host_meshes(self):
         for m in self.meshes:
-            if getattr(m, "host_stale", False):
+            if m.host_stale:
                 lo, hi = self.mesh_slices[m.name]
                 m.v = self.positions[lo:hi].detach().cpu().double().numpy()
                 if m.has_normals:
@@ -1195,7 +1196,7 @@ class Scene:
     def param_grads(self) -> ParamGrads:
         return ParamGrads(self.V, len(self.alpha_slots), device=self.device, mesh_slices=self.mesh_slices,
                           n_colors=len(self.color_slots), tex_shapes=self.texture_shapes(), n_rigid=len(self.rigid_slots),
-                          cam_rotation=bool(getattr(self, "sensor_rotation", False)))
+                          cam_rotation=self.sensor_rotation)
 
     # -- upload ----------------------------------------------------------------------------------
     def _upload(self):
