@@ -173,6 +173,14 @@ def declare_scene_tables(lib):
     lib.epsm_vertex_normals.restype = C.c_int
     lib.epsm_vertex_normals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p]
+    lib.epsm_vertex_normals_backward_bytes.restype = C.c_size_t
+    lib.epsm_vertex_normals_backward_bytes.argtypes = [C.c_int64]
+    lib.epsm_vertex_normals_backward.restype = C.c_int
+    lib.epsm_vertex_normals_backward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_vertex_normals_forward.restype = C.c_int
+    lib.epsm_vertex_normals_forward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.epsm_emitter_tables_bytes.restype = C.c_size_t
     lib.epsm_emitter_tables_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.epsm_emitter_tables.restype = C.c_int

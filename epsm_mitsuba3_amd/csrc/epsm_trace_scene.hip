@@ -170,6 +170,179 @@ __global__ __launch_bounds__(kBlock) void vertex_normals_kernel(const float *pos
     }
 }
 
+// ------------------------------------------------------------------------------------------------ vertex normals: derivative
+// d n_v / d p_w of the rule above, both directions (epsm_vertex_normals_backward / _forward).  The primal's arithmetic is
+// repeated operation for operation, so every cut falls where the primal's does; where the primal is cut to a constant the
+// derivative is 0 (DESIGN 5h's rule): a face normal or a vertex sum whose length is on its floor (0, or below the 1e-30 of the
+// fmax), a cosine on or outside [-1, 1], a corner whose edge lengths' product is on that floor, a triangle naming an index >= V.
+// A launch covers one run [v_begin, v_end) of flagged vertex rows; positions outside the run are constants to it (a triangle of
+// a mesh names that mesh's vertices), which keeps the two directions exact transposes.  Corners are picked with selects, not
+// with indexed register arrays: no scratch.
+constexpr double kFloor = 1e-30;
+
+struct TriGeom {
+    uint32_t id[3];
+    double p[3][3], e1[3], e2[3], fn[3], ln;            // fn, ln: as vertex_normals_kernel forms them
+};
+
+__device__ __forceinline__ bool tri_geom(const float *pos, int64_t V, const uint32_t *tri, uint32_t t, TriGeom &g) {
+    for (int k = 0; k < 3; ++k) g.id[k] = tri[3 * (int64_t) t + k];
+    if (g.id[0] >= V || g.id[1] >= V || g.id[2] >= V) return false;
+    for (int k = 0; k < 3; ++k) load_p(pos, g.id[k], g.p[k]);
+    for (int k = 0; k < 3; ++k) { g.e1[k] = g.p[1][k] - g.p[0][k]; g.e2[k] = g.p[2][k] - g.p[0][k]; }
+    cross(g.e1, g.e2, g.fn);
+    g.ln = sqrt(dot(g.fn, g.fn));
+    for (int k = 0; k < 3; ++k) g.fn[k] = g.ln > 0.0 ? g.fn[k] / fmax(g.ln, kFloor) : 0.0;
+    return true;
+}
+
+__device__ __forceinline__ void pick(const double a[3][3], uint32_t c, double o[3]) {
+    for (int k = 0; k < 3; ++k) {
+        const double a0 = a[0][k], a1 = a[1][k], a2 = a[2][k];       // values, not addresses, go through the selects
+        o[k] = c == 0u ? a0 : (c == 1u ? a1 : a2);
+    }
+}
+
+// the corner at pc between d0 = pa - pc and d1 = pb - pc: the primal's angle, and d angle / d d0, d d1 (0 where it is cut)
+struct Corner { double ang, g0[3], g1[3]; };
+
+__device__ __forceinline__ Corner corner(const double pc[3], const double pa[3], const double pb[3], bool want_grad) {
+    Corner r;
+    const double d0[3] = {pa[0] - pc[0], pa[1] - pc[1], pa[2] - pc[2]}, d1[3] = {pb[0] - pc[0], pb[1] - pc[1], pb[2] - pc[2]};
+    const double q0 = dot(d0, d0), q1 = dot(d1, d1), den = mul(sqrt(q0), sqrt(q1));
+    const double cosang = dot(d0, d1) / fmax(den, kFloor);
+    r.ang = acos(fmin(fmax(cosang, -1.0), 1.0));
+    for (int k = 0; k < 3; ++k) r.g0[k] = r.g1[k] = 0.0;
+    if (want_grad && den > kFloor && cosang > -1.0 && cosang < 1.0) {
+        const double s = -1.0 / sqrt(mul(1.0 - cosang, 1.0 + cosang));          // d acos / d cos
+        for (int k = 0; k < 3; ++k) {
+            r.g0[k] = mul(s, d1[k] / den - mul(cosang, d0[k]) / q0);
+            r.g1[k] = mul(s, d0[k] / den - mul(cosang, d1[k]) / q1);
+        }
+    }
+    return r;
+}
+
+// N_v: the primal's sum over the CSR row of v, in its order
+__device__ __forceinline__ void vertex_sum(const float *pos, int64_t V, const uint32_t *tri, const uint32_t *row, const uint32_t *adj,
+                                           int64_t v, double n[3]) {
+    n[0] = n[1] = n[2] = 0.0;
+    for (uint32_t j = row[v]; j < row[v + 1]; ++j) {
+        const uint32_t e = adj[j], t = e / 3u, c = e - 3u * t;
+        TriGeom g;
+        if (!tri_geom(pos, V, tri, t, g)) continue;
+        double pc[3], pa[3], pb[3];
+        pick(g.p, c, pc); pick(g.p, (c + 1u) % 3u, pa); pick(g.p, (c + 2u) % 3u, pb);
+        const double ang = corner(pc, pa, pb, false).ang;
+        for (int k = 0; k < 3; ++k) n[k] += mul(g.fn[k], ang);
+    }
+}
+
+// backward, launch 1: a_v = (I - n_v n_v^T) g_nrm[v] / |N_v| (three doubles per vertex; 0 where the sum is cut)
+__global__ __launch_bounds__(kBlock) void normals_adjoint_sum(const float *pos, int64_t V, const uint32_t *tri, const uint32_t *row,
+                                                              const uint32_t *adj, int64_t v_begin, int64_t v_end, const float *g_nrm,
+                                                              double *a) {
+    const int64_t v = v_begin + (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (v >= v_end) return;
+    double n[3], o[3] = {0.0, 0.0, 0.0};
+    vertex_sum(pos, V, tri, row, adj, v, n);
+    const double ln = sqrt(dot(n, n));
+    if (ln > kFloor) {
+        const double g[3] = {g_nrm[3 * v], g_nrm[3 * v + 1], g_nrm[3 * v + 2]};
+        for (int k = 0; k < 3; ++k) n[k] /= ln;
+        const double ng = dot(n, g);
+        for (int k = 0; k < 3; ++k) o[k] = (g[k] - mul(n[k], ng)) / ln;
+    }
+    a[3 * v] = o[0]; a[3 * v + 1] = o[1]; a[3 * v + 2] = o[2];
+}
+
+// backward, launch 2: g_pos[w] += d / d p_w of sum_t sum_c a_{i_c} . (theta_c f_t) over the triangles at w, in triangle order
+__global__ __launch_bounds__(kBlock) void normals_adjoint_positions(const float *pos, int64_t V, const uint32_t *tri, const uint32_t *row,
+                                                                    const uint32_t *adj, int64_t v_begin, int64_t v_end, const double *a,
+                                                                    float *g_pos) {
+    const int64_t w = v_begin + (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (w >= v_end) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = row[w]; j < row[w + 1]; ++j) {
+        const uint32_t e = adj[j], t = e / 3u, c = e - 3u * t;       // w is corner c of triangle t
+        TriGeom g;
+        if (!tri_geom(pos, V, tri, t, g)) continue;
+        double av[3][3], b[3] = {0.0, 0.0, 0.0}, G[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i < 3; ++i) {
+            const bool in = (int64_t) g.id[i] >= v_begin && (int64_t) g.id[i] < v_end;
+            for (int k = 0; k < 3; ++k) av[i][k] = in ? a[3 * (int64_t) g.id[i] + k] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {                                // the three angle parts (a_i . f) d theta_i / d p_w
+            const int ia = (i + 1) % 3, ib = (i + 2) % 3;
+            const Corner cr = corner(g.p[i], g.p[ia], g.p[ib], true);
+            const double s = dot(av[i], g.fn);
+            for (int k = 0; k < 3; ++k) {
+                b[k] += mul(cr.ang, av[i][k]);
+                const double d = c == (uint32_t) i ? -(cr.g0[k] + cr.g1[k]) : (c == (uint32_t) ia ? cr.g0[k] : cr.g1[k]);
+                G[k] += mul(s, d);
+            }
+        }
+        if (g.ln > kFloor) {                                         // the face-normal part with weight b = sum_i theta_i a_i
+            const double fb = dot(g.fn, b);
+            double gx[3], ge1[3], ge2[3];
+            for (int k = 0; k < 3; ++k) gx[k] = (b[k] - mul(g.fn[k], fb)) / g.ln;
+            cross(g.e2, gx, ge1);                                    // d (gx . (e1 x e2)) / d e1, / d e2
+            cross(gx, g.e1, ge2);
+            for (int k = 0; k < 3; ++k) G[k] += c == 0u ? -(ge1[k] + ge2[k]) : (c == 1u ? ge1[k] : ge2[k]);
+        }
+        for (int k = 0; k < 3; ++k) acc[k] += G[k];
+    }
+    float *o = g_pos + 3 * w;
+    o[0] += (float) acc[0]; o[1] += (float) acc[1]; o[2] += (float) acc[2];
+}
+
+// forward: d_nrm[v] += (I - n n^T) / |N_v| sum over the corners at v of (d theta f + theta d f), in triangle order
+__global__ __launch_bounds__(kBlock) void normals_tangent(const float *pos, int64_t V, const uint32_t *tri, const uint32_t *row,
+                                                          const uint32_t *adj, int64_t v_begin, int64_t v_end, const float *d_pos,
+                                                          float *d_nrm) {
+    const int64_t v = v_begin + (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    if (v >= v_end) return;
+    double n[3] = {0.0, 0.0, 0.0}, dn[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = row[v]; j < row[v + 1]; ++j) {
+        const uint32_t e = adj[j], t = e / 3u, c = e - 3u * t;
+        TriGeom g;
+        if (!tri_geom(pos, V, tri, t, g)) continue;
+        double tp[3][3];
+        for (int i = 0; i < 3; ++i) {
+            const bool in = (int64_t) g.id[i] >= v_begin && (int64_t) g.id[i] < v_end;
+            for (int k = 0; k < 3; ++k) tp[i][k] = in ? (double) d_pos[3 * (int64_t) g.id[i] + k] : 0.0;
+        }
+        double df[3] = {0.0, 0.0, 0.0};
+        if (g.ln > kFloor) {
+            const double de1[3] = {tp[1][0] - tp[0][0], tp[1][1] - tp[0][1], tp[1][2] - tp[0][2]};
+            const double de2[3] = {tp[2][0] - tp[0][0], tp[2][1] - tp[0][1], tp[2][2] - tp[0][2]};
+            double x1[3], x2[3], dx[3];
+            cross(de1, g.e2, x1);
+            cross(g.e1, de2, x2);
+            for (int k = 0; k < 3; ++k) dx[k] = x1[k] + x2[k];
+            const double fx = dot(g.fn, dx);
+            for (int k = 0; k < 3; ++k) df[k] = (dx[k] - mul(g.fn[k], fx)) / g.ln;
+        }
+        double pc[3], pa[3], pb[3], tc[3], ta[3], tb[3];
+        pick(g.p, c, pc); pick(g.p, (c + 1u) % 3u, pa); pick(g.p, (c + 2u) % 3u, pb);
+        pick(tp, c, tc); pick(tp, (c + 1u) % 3u, ta); pick(tp, (c + 2u) % 3u, tb);
+        const Corner cr = corner(pc, pa, pb, true);
+        const double dd0[3] = {ta[0] - tc[0], ta[1] - tc[1], ta[2] - tc[2]}, dd1[3] = {tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2]};
+        const double dang = dot(cr.g0, dd0) + dot(cr.g1, dd1);
+        for (int k = 0; k < 3; ++k) {
+            n[k] += mul(g.fn[k], cr.ang);
+            dn[k] += mul(dang, g.fn[k]) + mul(cr.ang, df[k]);
+        }
+    }
+    const double ln = sqrt(dot(n, n));
+    if (!(ln > kFloor)) return;
+    for (int k = 0; k < 3; ++k) n[k] /= ln;
+    const double nd = dot(n, dn);
+    float *o = d_nrm + 3 * v;
+    for (int k = 0; k < 3; ++k) o[k] += (float) ((dn[k] - mul(n[k], nd)) / ln);
+}
+
 // ------------------------------------------------------------------------------------------------ emitter tables
 struct EmitterSpace { double *local, *chunk_sum, *chunk_off, *mesh_total; int *chunk_begin; };
 
@@ -424,6 +597,90 @@ int epsm_vertex_normals(const float *positions, int64_t V, const uint32_t *tri, 
             hipLaunchKernelGGL(vertex_normals_kernel, dim3(grid(v1 - v0)), dim3(kBlock), 0, st, positions, V, tri, top.row, top.adj,
                                v0, v1, normals);
     }
+    return launched(what);
+}
+
+size_t epsm_vertex_normals_backward_bytes(int64_t V) {
+    if (V < 1) V = 1;
+    return align_up(24 * (size_t) V);
+}
+
+}  // extern "C"
+
+namespace {
+
+// What both directions check of their host arguments, in this order: the counts, then (nothing to do: *done) V == 0, T == 0 or
+// an empty table, then the pointers and the host tables.
+int check_normals_derivative(const char *what, int64_t V, int64_t T, int32_t n_meshes, bool pointers, const void *topology,
+                             const EpsmMesh *meshes, const int64_t *vertex_begin, bool *done) {
+    *done = false;
+    if (T < 0 || T >= kMaxTriangles) return fail(EPSM_EINVAL, what, "T must be in 0 .. 2^28 - 1");
+    if (V < 0 || V >= kMaxVertices) return fail(EPSM_EINVAL, what, "V must be in 0 .. 2^31 - 1");
+    if (n_meshes < 0) return fail(EPSM_EINVAL, what, "n_meshes must be >= 0");
+    if (V == 0 || T == 0 || n_meshes == 0) { *done = true; return EPSM_OK; }
+    if (!pointers || !topology || !meshes || !vertex_begin) return fail(EPSM_EINVAL, what, "NULL argument");
+    if ((uintptr_t) topology % 16) return fail(EPSM_EINVAL, what, "topology must be 16-byte aligned");
+    int rc = check_meshes(what, meshes, n_meshes, T);
+    if (rc != EPSM_OK) return rc;
+    for (int32_t m = 0; m < n_meshes; ++m)
+        if (vertex_begin[m] < 0 || vertex_begin[m + 1] < vertex_begin[m] || vertex_begin[m + 1] > V)
+            return fail(EPSM_EINVAL, what, "vertex_begin must not decrease and must stay inside 0 .. V");
+    return EPSM_OK;
+}
+
+// f(v0, v1) for every run of consecutive meshes flagged EPSM_MESH_VERTEX_NORMALS that holds a vertex
+template <class F>
+void for_flagged_runs(const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, F f) {
+    for (int32_t m = 0; m < n_meshes;) {
+        if (!(meshes[m].flags & EPSM_MESH_VERTEX_NORMALS)) { ++m; continue; }
+        const int64_t v0 = vertex_begin[m];
+        while (m < n_meshes && (meshes[m].flags & EPSM_MESH_VERTEX_NORMALS)) ++m;
+        if (vertex_begin[m] > v0) f(v0, vertex_begin[m]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int epsm_vertex_normals_backward(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
+                                 const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, const float *g_nrm,
+                                 float *g_pos, void *workspace, size_t workspace_bytes, void *stream) {
+    epsm_host::err_buf()[0] = 0;
+    const char *what = "epsm_vertex_normals_backward";
+    bool done;
+    int rc = check_normals_derivative(what, V, T, n_meshes, positions && tri && g_nrm && g_pos && workspace, topology, meshes,
+                                      vertex_begin, &done);
+    if (rc != EPSM_OK || done) return rc;
+    if (workspace_bytes < epsm_vertex_normals_backward_bytes(V))
+        return fail(EPSM_EINVAL, what, "workspace smaller than epsm_vertex_normals_backward_bytes(V)");
+    if ((uintptr_t) workspace % 16) return fail(EPSM_EINVAL, what, "workspace must be 16-byte aligned");
+    const Topology top = topology_carve(V, (char *) topology);
+    hipStream_t st = (hipStream_t) stream;
+    double *a = (double *) workspace;
+    for_flagged_runs(meshes, vertex_begin, n_meshes, [&](int64_t v0, int64_t v1) {
+        hipLaunchKernelGGL(normals_adjoint_sum, dim3(grid(v1 - v0)), dim3(kBlock), 0, st, positions, V, tri, top.row, top.adj, v0, v1,
+                           g_nrm, a);
+        hipLaunchKernelGGL(normals_adjoint_positions, dim3(grid(v1 - v0)), dim3(kBlock), 0, st, positions, V, tri, top.row, top.adj,
+                           v0, v1, (const double *) a, g_pos);
+    });
+    return launched(what);
+}
+
+int epsm_vertex_normals_forward(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
+                                const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, const float *d_pos,
+                                float *d_nrm, void *stream) {
+    epsm_host::err_buf()[0] = 0;
+    const char *what = "epsm_vertex_normals_forward";
+    bool done;
+    int rc = check_normals_derivative(what, V, T, n_meshes, positions && tri && d_pos && d_nrm, topology, meshes, vertex_begin, &done);
+    if (rc != EPSM_OK || done) return rc;
+    const Topology top = topology_carve(V, (char *) topology);
+    hipStream_t st = (hipStream_t) stream;
+    for_flagged_runs(meshes, vertex_begin, n_meshes, [&](int64_t v0, int64_t v1) {
+        hipLaunchKernelGGL(normals_tangent, dim3(grid(v1 - v0)), dim3(kBlock), 0, st, positions, V, tri, top.row, top.adj, v0, v1, d_pos,
+                           d_nrm);
+    });
     return launched(what);
 }
 

@@ -365,17 +365,28 @@ def _rigid_backward(scene, params: ParamGrads, contrib: ParamGrads, n: int) -> N
             scene.rigid_reduce(contrib.pos, contrib.nrm, params.rigid[:n], *scene.rigid_tables())
 
 
+def _normals_chain_backward(scene, params: ParamGrads, contrib: ParamGrads) -> None:
+    """``params.pos`` += ONE call's ``nrm`` rows, after their sum over the ranks, carried through the recomputed vertex normals of
+    the meshes attached with ``recomputed_normals`` (``epsm_vertex_normals_backward``: float64, a fixed order -- every rank adds
+    the same bits).  It goes into ``params`` and not into ``contrib``: the rigid slots and the sensor's pass reduce ``contrib``
+    with their own n x g_nrm term, which is this chain's torque already (sum_w x_w x (J^T g)_w = sum_v n_v x g_v)."""
+    with _prof.phase("epsm.render_backward.normals_chain"):
+        scene.normals_backward(contrib.nrm, params.pos)
+
+
 @contextmanager
 def _call_contribution(scene, params: ParamGrads, n_rigid: int, add: Optional[Callable[[ParamGrads], None]] = None):
     """The buffer ONE ``render_backward`` writes its geometry gradients into.  dr.backward ACCUMULATES into the gradients that
     are already there, and with more than one rank only THIS call's contribution may be summed over the ranks: what ``params``
     held on entry is already a sum over the ranks (or the caller's own data) and must not be multiplied by the world size.  The
-    rigid slots reduce this call's contribution too, and the sensor's pass (``add``) sums every vertex row of it.  So: ``params``
-    itself with one rank, no rigid slot and no ``add``; else ``params.scratch()``, and on exit, in this order, ONE all-reduce
-    of the whole buffer when there are several ranks, ``params.flat += `` it (or ``add(contribution)`` in its place), the
-    rigid slots' reduction."""
+    rigid slots reduce this call's contribution too, the sensor's pass (``add``) sums every vertex row of it, and a mesh attached
+    with ``recomputed_normals`` has this call's ``nrm`` rows carried back to ``pos``.  So: ``params`` itself with one rank, no
+    rigid slot, no such mesh and no ``add``; else ``params.scratch()``, and on exit, in this order, ONE all-reduce of the whole
+    buffer when there are several ranks, the normals' chain of this call's rows into ``params.pos``, ``params.flat += `` the
+    buffer (or ``add(contribution)`` in its place), the rigid slots' reduction."""
     world = _dist.world()[1]
-    if world == 1 and not n_rigid and add is None:
+    chained = getattr(scene, "has_recomputed_normals", lambda: False)()       # (bench.py's SyntheticScene has no meshes to flag)
+    if world == 1 and not n_rigid and add is None and not chained:
         yield params
         return
     target = params.scratch()
@@ -383,6 +394,8 @@ def _call_contribution(scene, params: ParamGrads, n_rigid: int, add: Optional[Ca
     if world > 1:
         with _prof.phase("epsm.render_backward.allreduce"):
             _dist.allreduce_param_grads(target.flat)
+    if chained:
+        _normals_chain_backward(scene, params, target)
     if add is None:
         params.flat += target.flat
     else:
@@ -651,6 +664,14 @@ class PRBReparamIntegrator(PRBIntegrator):
                 tan_pos[lo:hi] += params.pos[lo:hi].to(dev, torch.float32)
             if rot and m.nrm_attached:
                 tan_nrm[lo:hi] += params.nrm[lo:hi].to(dev, torch.float32)
+        if scene.has_recomputed_normals():
+            # the transpose of _normals_chain_backward: the caller's own position tangents of those meshes move their normals (the
+            # twists' motion of a normal is rigid_expand's dw x n, below)
+            own_pos = params.pos.to(dev, torch.float32).contiguous()
+            if tan_nrm.data_ptr() == params.nrm.data_ptr():
+                tan_nrm = tan_nrm.clone()
+            with _prof.phase("epsm.render_forward.normals_chain"):
+                scene.normals_forward(own_pos, tan_nrm)
         if twists:
             ranges, pivots = scene.rigid_tables(extra=extra)
             scene.rigid_expand(torch.cat(twists).contiguous(), tan_pos, tan_nrm, ranges, pivots)

@@ -353,6 +353,8 @@ class Mesh:
         self.bsdf, self.emitter = bsdf, emitter
         self.flip_normals, self.is_mesh = flip_normals, is_mesh
         self.pos_attached = self.nrm_attached = False
+        self.nrm_chained = False                   # attach(recomputed_normals=True): its nrm rows are carried back to pos
+        self.normals_recomputed = False            # set_vertex_positions made the normals a function of the positions
         self.host_stale = False                    # set when the vertices moved on the device: v / n are then refreshed on demand
 
     def flags(self) -> int:
@@ -878,11 +880,61 @@ class Scene:
     def mesh(self, name: str) -> Mesh:
         return next(m for m in self.meshes if m.name == name)
 
-    def attach(self, mesh_name: str, positions: bool = True, normals: bool = False):
-        """``dr.enable_grad(params['<mesh>.vertex_positions' / '.vertex_normals'])``."""
+    def attach(self, mesh_name: str, positions: bool = True, normals: bool = False, recomputed_normals: bool = False):
+        """``dr.enable_grad(params['<mesh>.vertex_positions' / '.vertex_normals'])``.  ``recomputed_normals``: the mesh's vertex
+        normals are the function of its positions that ``set_vertex_positions`` recomputes (Mesh::parameters_changed,
+        mesh.cpp:82-87), so ``render_backward`` also carries this call's ``nrm`` rows back to ``pos`` through that function
+        (``epsm_vertex_normals_backward``; ``render_forward`` the transpose) -- what ``dr.grad`` of the positions holds in the
+        reference.  It implies ``positions`` and ``normals``; the ``nrm`` rows are kept."""
         m = self.mesh(mesh_name)
-        m.pos_attached, m.nrm_attached = positions, normals
+        if recomputed_normals:
+            if not m.has_normals:
+                raise ValueError(f"attach: {mesh_name!r} has face normals: there are no vertex normals to recompute")
+            if m.normals_given and not m.normals_recomputed:
+                raise ValueError(f"attach: the vertex normals of {mesh_name!r} came with the geometry and have never been recomputed "
+                                 "(set_vertex_positions): they are not a function of the positions")
+            positions = normals = True
+        m.pos_attached, m.nrm_attached, m.nrm_chained = positions, normals, bool(recomputed_normals)
         self._refresh_attach_flags()
+
+    def has_recomputed_normals(self) -> bool:
+        """Any mesh attached with ``recomputed_normals``?"""
+        return any(m.nrm_chained for m in self.meshes)
+
+    def _normals_chain_tables(self):
+        """(mesh table in which only the meshes attached with ``recomputed_normals`` carry EPSM_MESH_VERTEX_NORMALS, the first
+        vertex row of every mesh and the end of the last, the triangles' topology -- None on the host build of the tracer)."""
+        table = (EpsmMesh * max(1, len(self.meshes)))()
+        C.memmove(table, self._mesh_structs, C.sizeof(table))
+        vb = [0]
+        for c, m in zip(table, self.meshes):
+            if not m.nrm_chained:
+                c.flags &= ~MESH_VERTEX_NORMALS
+            vb.append(vb[-1] + (self.mesh_slices[m.name][1] - self.mesh_slices[m.name][0]))
+        top = None
+        if self._backend is None:
+            if self.scene_tables == "device":
+                top = self._topology
+            else:                                              # the host tables never needed it: built on first use, per triangle set
+                top = getattr(self, "_chain_topology", None)
+                if top is None or top.tri is not self.tri:
+                    from . import scene_tables as st
+                    top = self._chain_topology = st.SceneTopology(self.tri, self.V)
+        return table, vb, top
+
+    def normals_backward(self, g_nrm: torch.Tensor, g_pos: torch.Tensor) -> None:
+        """``g_pos += J^T g_nrm`` over the meshes attached with ``recomputed_normals`` (scene_tables.vertex_normals_backward)."""
+        from . import scene_tables as st
+        table, vb, top = self._normals_chain_tables()
+        st.vertex_normals_backward(self.positions, self.tri, table, vb, g_nrm, g_pos, topology=top, count=len(self.meshes),
+                                   host=self._backend is not None)
+
+    def normals_forward(self, d_pos: torch.Tensor, d_nrm: torch.Tensor) -> None:
+        """``d_nrm += J d_pos`` over the same meshes: the transpose (scene_tables.vertex_normals_forward)."""
+        from . import scene_tables as st
+        table, vb, top = self._normals_chain_tables()
+        st.vertex_normals_forward(self.positions, self.tri, table, vb, d_pos, d_nrm, topology=top, count=len(self.meshes),
+                                  host=self._backend is not None)
 
     def _refresh_attach_flags(self, sync_host: bool = True):
         """What `dr.enable_grad` changes on the device: the mode bits of the meshes -- in the mesh table the tracer reads and
@@ -1134,6 +1186,7 @@ class Scene:
             m.v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1, 3)
             if m.has_normals:
                 m.n = vertex_normals(m.v, m.f)
+                m.normals_recomputed = True
             self._upload()
             return
         v_t = torch.as_tensor(v, dtype=torch.float32, device=self.device).detach().reshape(-1, 3)
@@ -1143,6 +1196,7 @@ class Scene:
         m.host_stale = True                                   # m.v / m.n are refreshed when the host needs them
         if m.has_normals:
             t0, t1 = self.mesh_tri_slices[mesh_name]
+            m.normals_recomputed = True
             self.normals[lo:hi] = vertex_normals_torch(v_t, self.tri[t0:t1].long() - lo)
         self.bvh.refit(self.positions, self.tri)
 
@@ -1156,6 +1210,7 @@ class Scene:
         m.host_stale = True                                   # m.v / m.n are refreshed when the host needs them
         if m.has_normals:
             m.normals_given = False                           # recomputed on a move, as on the host tables' route
+            m.normals_recomputed = True
             st.vertex_normals(self.positions, self._topology, self._mesh_structs, self._vertex_begin, self.normals, first=i, count=1)
         st.emitter_tables(self.positions, self.tri, self._mesh_structs, self._mesh_buf, self.emitter_cdf, first=i, count=1)
         self.bvh.refit(self.positions, self.tri)

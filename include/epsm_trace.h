@@ -526,6 +526,28 @@ int epsm_scene_topology(const uint32_t *tri, int64_t V, int64_t T, void *topolog
 int epsm_vertex_normals(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
                         const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, float *normals, void *stream);
 
+/* epsm_vertex_normals_backward / _forward -- the derivative of epsm_vertex_normals with respect to the positions, for the same
+ *   table convention (only the vertex rows of the meshes flagged EPSM_MESH_VERTEX_NORMALS are read as normals and written as
+ *   positions; every other row of g_pos / d_nrm is left bit for bit).  With N_v the unnormalised sum and n_v = N_v / |N_v|:
+ *     backward   g_pos[w] += sum_v (d n_v / d p_w)^T g_nrm[v].  Two launches per run of flagged meshes: a_v = (I - n_v n_v^T)
+ *                g_nrm[v] / |N_v| into `workspace` (>= epsm_vertex_normals_backward_bytes(V), 16-byte aligned), then one thread
+ *                per vertex w gathers d / d p_w of sum_c a_{i_c} . (theta_c f_t) over its triangles in triangle order;
+ *     forward    d_nrm[v] += (I - n_v n_v^T) / |N_v| sum over the corners at v of (d theta f + theta d f): one gather, the exact
+ *                transpose, no workspace.
+ *   fp64 sums in a fixed order, rounded to float32 once and added: no atomics, two calls give identical bits.  Where the primal
+ *   is cut to a constant the derivative is 0: a face normal or a vertex sum of length 0 (or below the 1e-30 floor of its
+ *   division), a cosine on or outside [-1, 1], a corner with an edge of length 0, a triangle naming an index >= V.  A position
+ *   outside the run of consecutive flagged meshes a vertex belongs to is a constant to that vertex (a mesh's triangles name its own
+ *   vertices).  V == 0, T == 0 or an empty table: EPSM_OK, nothing is done.  Arrays as for epsm_vertex_normals; g_nrm, g_pos,
+ *   d_pos, d_nrm (V,3) f32: device. */
+size_t epsm_vertex_normals_backward_bytes(int64_t V);
+int epsm_vertex_normals_backward(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
+                                 const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, const float *g_nrm,
+                                 float *g_pos, void *workspace, size_t workspace_bytes, void *stream);
+int epsm_vertex_normals_forward(const float *positions, int64_t V, const uint32_t *tri, int64_t T, const void *topology,
+                                const EpsmMesh *meshes, const int64_t *vertex_begin, int32_t n_meshes, const float *d_pos,
+                                float *d_nrm, void *stream);
+
 /* epsm_emitter_tables -- for every mesh of the table, as Scene._upload does: the triangle areas 0.5 |(p1 - p0) x (p2 - p0)| from
  *   the float32 positions, their normalised running sum written to emitter_cdf[cdf_begin .. cdf_begin + tri_count) and their sum
  *   written IN PLACE to meshes_device[m].area (no other field is touched).  fp64 throughout, rounded to float32 once; the last
