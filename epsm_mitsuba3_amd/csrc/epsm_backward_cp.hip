@@ -248,10 +248,10 @@ struct Rounds {
         int q = 0;
 #pragma unroll
         for (int t = 1; t < kKeys; ++t) if (r >= rb[t]) q = t;
-        int cls_q = cls[0], n_q = cls[1] - cls[0], rb_q = rb[0];
+        int cls_q = cls[0], n_q = cls[1] - cls[0], rb_q = rb[0], ppr = 64;      // ppr = 64 / c: a constant per class, no division
 #pragma unroll
-        for (int t = 1; t < kKeys; ++t) if (q == t) { cls_q = cls[t]; n_q = cls[t + 1] - cls[t]; rb_q = rb[t]; }
-        const int c = q > 0 ? q : 1, ppr = 64 / c;
+        for (int t = 1; t < kKeys; ++t) if (q == t) { cls_q = cls[t]; n_q = cls[t + 1] - cls[t]; rb_q = rb[t]; ppr = 64 / t; }
+        const int c = q > 0 ? q : 1;
         const int j = div_small(lane, c), k = lane - j * c + 1;
         const int idx = (r - rb_q) * ppr + j;
         const bool lane_on = r >= 0 && r < rb[kKeys] && j < ppr && idx < n_q;      // (r < 0: past the last round handed out)
@@ -297,6 +297,8 @@ __device__ __forceinline__ F2v ld2(const float *p) { return *(const __attribute_
 // divisions (float reciprocal + one correction step each way, exact below 2^24) instead of two 32-bit integer divisions.
 struct WinBase {
     const float *verts, *rays;
+    const float *sub_rec;            // the first record of the window's first path: what a lane with nothing to read loads (own_issue)
+    int64_t sub_path;                // ... that path, where the windows run over a list
     const uint32_t *shadow;
     const uint32_t *list;            // EpsmPackedLog.path_list + the window's first slot: path of slot loc = list[loc] (null: base + loc)
     int64_t base;
@@ -304,10 +306,17 @@ struct WinBase {
     float rcp_spp, rcp_res;
     bool small;                      // pixel indices of this film stay below 2^24
 };
+template <bool LIST>
 __device__ __forceinline__ WinBase win_base(const FusedArgs &F, int64_t base) {
     WinBase B;
     B.base = base;
     B.verts = F.pk_verts + base * F.pk_path_stride;
+    B.sub_rec = B.verts; B.sub_path = 0;
+    if (LIST && F.pk_list) {         // windows over a list: the path of the window's first slot (the planning guards a bad entry the same way)
+        const int64_t p = (int64_t) lds_(F.pk_list, base);
+        B.sub_path = (p >= 0 && p < F.g.N) ? p : 0;
+        B.sub_rec = F.pk_verts + B.sub_path * F.pk_path_stride;
+    }
     B.rays = F.pk_rays + base * F.pk_ray_stride;
     B.shadow = F.pk_shadow ? F.pk_shadow + 4 * base : nullptr;
     B.list = F.pk_list ? F.pk_list + base : nullptr;
@@ -335,11 +344,13 @@ __device__ __forceinline__ LaneRole role_of(const FusedArgs &F, const LaneId &L,
     R.end_next = R.live && L.k == L.c && L.k + 1 <= cp::plan_nv(L.plan);      // vertex k+1 exists and has no lane
     R.d1 = R.ok && R.first && cp::plan_diffuse1(L.plan);
     R.act1 = (L.plan & cp::kPlanActive1) != 0;
-    R.loc = (uint32_t) L.loc;
+    // A lane without a path stands in for the window's FIRST path (loc 0): its rays and its pixel are addresses that a lane of this
+    // window may read, so geo_issue_rest loads them without a guard
+    R.loc = R.ok ? (uint32_t) L.loc : 0u;
     if (LIST && B.list) {
         // the windows run over a LIST of paths (the tracer's survivors, EPSM_TRACE_FUSE_FIRST_HIT): slot -> path by one more load -- a
         // line the planning has just read -- and the addresses from the path itself
-        const int64_t i = R.ok ? (int64_t) lds_(B.list, (int64_t) R.loc) : 0;
+        const int64_t i = R.ok ? (int64_t) lds_(B.list, (int64_t) R.loc) : B.sub_path;
         R.path = i;
         R.rec = F.pk_verts + i * F.pk_path_stride + (L.k - 1) * kRecWords;
         R.rays = F.pk_rays + i * F.pk_ray_stride;
@@ -379,16 +390,16 @@ typedef __attribute__((address_space(3))) F4v LdsF4w;
 template <bool LIST>
 __device__ __forceinline__ void geo_issue_rest(GeoFetch &X, const FusedArgs &F, const LaneId &L, const WinBase &B) {
     const LaneRole R = role_of<LIST>(F, L, B);
-    if (R.ok && R.first) {
-        const float *rays = R.rays;
-        X.p0 = ldq(rays, 0); X.p1 = ldq(rays, 1); X.p2 = ldq(rays, 2);
-        const F2v g = ld2(pixel_grad(F.tin, B, R.loc, R.path));
-        X.gx = g.x; X.gy = g.y;
-    }
-    if (R.end_next) {
-        const float *nx = R.rec + kRecWords;
-        X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
-    }
+    // No guards and no zero fill (own_issue): the other lanes of a path read the lines its first lane reads anyway, a lane without a
+    // path those of the window's first path (role_of), and a lane whose chain does not end on a foreign vertex the window's first
+    // record.  The readers: p0..p2, gx, gy under `ok && first` (`live && first` implies it), n0..n2 under `has_next && k == c`,
+    // which is end_next.
+    const float *rays = R.rays;
+    X.p0 = ldq(rays, 0); X.p1 = ldq(rays, 1); X.p2 = ldq(rays, 2);
+    const F2v g = ld2(pixel_grad(F.tin, B, R.loc, R.path));
+    X.gx = g.x; X.gy = g.y;
+    const float *nx = R.end_next ? R.rec + kRecWords : B.sub_rec;
+    X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
 }
 template <int VARIANT, bool LIST>
 __device__ __forceinline__ void addr_issue(AddrFetch &A, const FusedArgs &F, const LaneId &L, const WinBase &B) {
@@ -410,14 +421,18 @@ __device__ __forceinline__ void own_issue(GeoFetch &X, AddrFetch &A, const Fused
     const LaneRole R = role_of<LIST>(F, L, B);
     // (a path WITHOUT a constraint reads its first record only when its first hit is diffuse: diffuse_grad[0] = dldp needs the
     // triangle; otherwise all it gives is its share of d/d ray.o, which needs the rays alone -- 27 % of the bathroom paths)
-    if (R.live || R.d1) { X.o0 = ldq(R.rec, 0); X.o1 = ldq(R.rec, 1); X.o2 = ldq(R.rec, 2); }
-    if (R.live) { X.o3 = ldq(R.rec, 3); X.o4 = ldq(R.rec, 4); X.o5 = ldq(R.rec, 5); }
+    // A lane WITHOUT that need loads all the same -- from the window's first record, an address a guarded load of this round is
+    // entitled to read (base < n_slots inside the window loop; all such lanes of a wave read ONE line per instruction) -- and nobody
+    // looks at what it got: a select of the pointer instead of a zero fill of 24 registers and a branch around the loads.  Every
+    // reader of o0..o5 in the round loop stands under `live`, `d1` or `need_tri = act1 && (live || d1)`.
+    const float *rec012 = (R.live || R.d1) ? R.rec : B.sub_rec, *rec345 = R.live ? R.rec : B.sub_rec;
+    X.o0 = ldq(rec012, 0); X.o1 = ldq(rec012, 1); X.o2 = ldq(rec012, 2);
+    X.o3 = ldq(rec345, 3); X.o4 = ldq(rec345, 4); X.o5 = ldq(rec345, 5);
     addr_issue<VARIANT, LIST>(A, F, L, B);
 }
 __device__ __forceinline__ void fetch_zero(GeoFetch &X, AddrFetch &A) {
     const F4v z4 = {0.f, 0.f, 0.f, 0.f};
-    X.o0 = X.o1 = X.o2 = X.o3 = X.o4 = X.o5 = X.p0 = X.p1 = X.p2 = X.n0 = X.n1 = X.n2 = z4;
-    X.o_lz = X.gx = X.gy = 0.f;
+    // (of Xp only o0..o5 are used, and own_issue always loads them)
     A.q6 = A.q7 = z4; A.sh.x = kNoIndex; A.sh.y = A.sh.z = A.sh.w = 0u;
 }
 
@@ -453,7 +468,10 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
     float *const my_rep = F.rep ? F.rep + (blockIdx.x % (unsigned) F.replicas) * F.rep_stride : nullptr;
     const Table T{s_keys, s_vals, &s_used, my_rep ? my_rep : F.gpos, my_rep ? my_rep + 3 * F.V : F.gnrm,
                   my_rep ? my_rep + 6 * F.V : F.galpha, (uint32_t) F.V};
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave index through readfirstlane: the compiler does not know that threadIdx.x >> 6 is the same on all lanes of a wave, and
+    // without that the round index, the class of a round and everything derived from them live in vector registers -- the round
+    // loop leaves through the exec mask, lane_of's selects and `q > 0` / `c > 1` / the recursions' trip counts run per lane)
+    const int wv = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)), lane = threadIdx.x & 63;
     WaveQueue<kQueueCap> Q{s_queue[wv], 0};
     const Emitter<Table> E{F, T, Q};
     if (!PACKED && threadIdx.x < F.K) { s_ptrs.v[threadIdx.x] = F.g.v[threadIdx.x]; s_ptrs.s[threadIdx.x] = F.s[threadIdx.x]; }
@@ -486,7 +504,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
         const int64_t win = (int64_t) blockIdx.x * windows_per_block + wi;
         if (win >= n_windows) break;                                 // workgroup-uniform
         const int64_t base = win * window;
-        const WinBase WB = win_base(F, base);
+        const WinBase WB = win_base<kList>(F, base);
         // ---- plan + histogram of m: thread t plans paths base + j*kThreads + t.  With the caller's tangents a path WITHOUT ANY
         // TERM -- no constraint vertex, first hit not diffuse: 27 % of the bathroom paths -- gets key kKeys, a class sorted behind
         // the others and handed to no round.  (With in-kernel tangents such a path still owes its share of d/d ray.o = -sum grad_d,
@@ -593,8 +611,10 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             asm volatile("; EPSM_MARK round_begin");
             // ---- geometry: own vertex; the two neighbours from the lanes that hold them (or from the words fetched for that)
             cp::Own<float> own;
-            own.x = own.e1 = own.e2 = own.n = own.dn1 = own.dn2 = own.light = zero3<float>();
-            own.b0 = own.b1 = own.eta = 0.f;
+            if (!PACKED) {
+                own.x = own.e1 = own.e2 = own.n = own.dn1 = own.dn2 = own.light = zero3<float>();
+                own.b0 = own.b1 = own.eta = 0.f;
+            }
             cp::Nbr<float> prev, next;
             prev.x = prev.e1 = prev.e2 = next.x = next.e1 = next.e2 = zero3<float>();
             V2<float> dk = mk2<float>(0.f, 0.f);
@@ -607,13 +627,9 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             float eb0 = 0.f, eb1 = 0.f, ew = 0.f;
             U4 sh; sh.x = kNoIndex; sh.y = sh.z = sh.w = 0u;
             if (PACKED) {
-                GeoFetch X;                                          // (every field defined: a conditionally loaded, conditionally read
-                {                                                    //  struct with undefined fields is kept in scratch memory)
-                    const F4v z4 = {0.f, 0.f, 0.f, 0.f};
-                    X.o0 = X.o1 = X.o2 = X.o3 = X.o4 = X.o5 = X.p0 = X.p1 = X.p2 = X.n0 = X.n1 = X.n2 = z4;
-                    X.o_lz = X.gx = X.gy = 0.f;
-                }
+                GeoFetch X;                                          // (every field is loaded or assigned below, whatever the lane holds: a
                 geo_issue_rest<kList>(X, F, L, WB);
+                                                                     //  conditionally loaded struct is kept in scratch memory)
                 X.o0 = Xp.o0; X.o1 = Xp.o1; X.o2 = Xp.o2; X.o3 = Xp.o3; X.o4 = Xp.o4; X.o5 = Xp.o5;
                 // ONE trip to memory per record: the words only the emission needs (quads 6 and 7: the same line as the geometry,
                 // second sector) are requested together with it and parked in LDS until the emission -- 32 bytes per lane in the
@@ -632,14 +648,17 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     *(LdsF4w *) st = has_sh ? shv : A0.q6; *(LdsF4w *) (st + 4) = A0.q7;
                     X.o_lz = A0.q7.x;                                // light.z: word 28
                 }
-                if (live) {
+                {   // every lane, whatever it holds (a plain assignment instead of a zero fill and a copy under the exec mask per word): a
+                    // lane without a constraint forms its vertex from the words own_issue gave it -- the substitute record's -- and nobody
+                    // reads the result: its blocks and seeds stay on the lane (the recursions and the exchange below take from lanes of the
+                    // SAME path only, which are live when the taker is), and its rows stand under `on` / `live` in Emitter::vertex.  A lane
+                    // with d1 alone reads quads 0..2 of its own record: own.b0, own.b1 are its barycentrics.
                     const Geo<float> g = geo_from(X.o0, X.o1, X.o2);
                     const Nrm<float> nr = nrm_from(X.o3, X.o4, X.o5, g.b0, g.b1);
                     own.x = g.x; own.e1 = g.e1; own.e2 = g.e2; own.b0 = g.b0; own.b1 = g.b1;
                     own.n = nr.n; own.dn1 = nr.dn1; own.dn2 = nr.dn2;
                     own.eta = X.o3.w; own.light = mk3<float>(X.o5.z, X.o5.w, X.o_lz);
                 }
-                if (d1 && !live) { own.b0 = X.o2.y; own.b1 = X.o2.z; }
                 if (live || d1) tid_own = __float_as_uint(X.o2.w);
                 if (c > 1) {                                         // wave-uniform: paths on several lanes exchange their vertices
                     const V3<float> ux = up1(own.x), ue1 = up1(own.e1), ue2 = up1(own.e2);
