@@ -237,6 +237,14 @@ def declare_tracer(lib):
         lib.epsm_trace_paths_bsdf_backward.argtypes = bsdf_args + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.epsm_trace_paths_bsdf_forward.restype = C.c_int
         lib.epsm_trace_paths_bsdf_forward.argtypes = bsdf_args + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "epsm_trace_paths_material_backward"):  # (the HIP library; of the host builds, tests/host_harness/trace_material_host.cpp)
+        mat_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        lib.epsm_trace_material_workspace_bytes.restype = C.c_size_t
+        lib.epsm_trace_material_workspace_bytes.argtypes = [C.c_int64]
+        lib.epsm_trace_paths_material_backward.restype = C.c_int
+        lib.epsm_trace_paths_material_backward.argtypes = mat_args + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.epsm_trace_paths_material_forward.restype = C.c_int
+        lib.epsm_trace_paths_material_forward.argtypes = mat_args + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int

@@ -72,6 +72,9 @@ EPSM_HD void probe_row(int what, const float *in, float *out, const EpsmBsdf *bs
             const float dl = bsdf->type == EPSM_BSDF_ROUGHCONDUCTOR_T ? rough_dlog_dalpha(*bsdf, wi, wo) : 0.f;
             out[0] = v.x * dl; out[1] = v.y * dl; out[2] = v.z * dl; out[3] = dl;
         } break;
+        case EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD: {      // in: cos_theta_i, eta, k -> F, d F / d eta, d F / d k
+            out[0] = fresnel_conductor_grad(in[0], in[1], in[2], &out[1], &out[2]);
+        } break;
         default: break;
     }
 }

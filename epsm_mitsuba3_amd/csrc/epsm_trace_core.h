@@ -353,6 +353,38 @@ EPSM_HD float fresnel_conductor(float cos_i, float eta_r, float eta_i) {
     const float r_p = r_s * (term_3 - term_4) / (term_3 + term_4);
     return 0.5f * (r_s + r_p);
 }
+// F with d F / d eta and d F / d k in closed form (the material adjoint, epsm_trace_material.h); fresnel_conductor's own
+// arithmetic is untouched.  With a + i b = sqrt(eta^2 - k^2 - sin^2 + 2 i eta k):  a^2 - b^2 = t,  a b = eta k,  P = a^2 + b^2, hence
+//   d P / d eta = 2 eta (eta^2 + k^2 - sin^2) / P        d P / d k = 2 k (eta^2 + k^2 + sin^2) / P
+//   d a^2 / d eta = 2 eta (a^2 + k^2) / P                d a^2 / d k = 2 k a^2 sin^2 / ((a^2 + k^2) P)
+// (the second row from (a^2 - eta^2)(a^2 + k^2) = -a^2 sin^2: sums of positive terms, nothing is differentiated through the
+// difference 1/2 (P + t) -- for a metal, t < 0, a^2 is taken as 2 eta^2 k^2 / (P - t)).  Both derivatives are 0 where the value is
+// cut to a constant (an argument of either safe_sqrt <= 0: the `eta = 0, k = 1` mirror has a = 0, F = 1), where F = 0 and
+// where they are not finite.
+EPSM_HD float fresnel_conductor_grad(float cos_i, float eta_r, float eta_i, float *dF_deta, float *dF_dk) {
+    const float F = fresnel_conductor(cos_i, eta_r, eta_i);
+    *dF_deta = *dF_dk = 0.f;
+    const float c2 = cos_i * cos_i, s2 = 1.f - c2, s4 = s2 * s2;
+    const float e2 = eta_r * eta_r, k2 = eta_i * eta_i;
+    const float t = e2 - k2 - s2, arg_1 = t * t + 4.f * k2 * e2;
+    if (!(arg_1 > 0.f) || !(0.5f * (sqrtf(arg_1) + t) > 0.f) || F == 0.f) return F;
+    const float P = sqrtf(arg_1);
+    const float a2 = t >= 0.f ? 0.5f * (P + t) : 2.f * e2 * k2 / (P - t), a = sqrtf(a2);
+    const float A = P + c2, B = 2.f * cos_i * a, C = P * c2 + s4, D = B * s2;
+    const float r_s = (A - B) / (A + B), q = (C - D) / (C + D);
+    const float dP[2] = {2.f * eta_r * (e2 + k2 - s2) / P, 2.f * eta_i * (e2 + k2 + s2) / P};
+    const float da2[2] = {2.f * eta_r * (a2 + k2) / P, 2.f * eta_i * a2 * s2 / ((a2 + k2) * P)};
+    float dF[2];
+    for (int j = 0; j < 2; ++j) {
+        const float dB = cos_i * da2[j] / a;                                // d (2 cos a) = 2 cos d a^2 / (2 a)
+        const float dr_s = 2.f * (B * dP[j] - A * dB) / ((A + B) * (A + B));
+        const float dq = 2.f * (D * c2 * dP[j] - C * s2 * dB) / ((C + D) * (C + D));
+        dF[j] = 0.5f * (dr_s * (1.f + q) + r_s * dq);
+    }
+    if (!(fabsf(dF[0]) < __builtin_inff()) || !(fabsf(dF[1]) < __builtin_inff())) return F;
+    *dF_deta = dF[0]; *dF_dk = dF[1];
+    return F;
+}
 EPSM_HD F3 fresnel_conductor3(float cos_i, const EpsmBsdf &b) {
     return f3(fresnel_conductor(cos_i, b.eta[0], b.k[0]), fresnel_conductor(cos_i, b.eta[1], b.k[1]),
               fresnel_conductor(cos_i, b.eta[2], b.k[2]));
@@ -1095,7 +1127,7 @@ EPSM_HD void path_bounce(const TraceArgs &A, int64_t i, int iteration, PathState
     bsdf.type = EPSM_BSDF_DIFFUSE_T; bsdf.twosided = 0; bsdf.distr = 0; bsdf.sample_visible = 1; bsdf.alpha = 0.1f;
     bsdf.reflectance[0] = bsdf.reflectance[1] = bsdf.reflectance[2] = 0.f;
     bsdf.eta[0] = bsdf.eta[1] = bsdf.eta[2] = 0.f; bsdf.k[0] = bsdf.k[1] = bsdf.k[2] = 1.f;
-    bsdf.int_ior = 1.5046f; bsdf.ext_ior = 1.000277f; bsdf.alpha_slot = -1; bsdf.color_slot = -1; bsdf.texture = -1; bsdf.pad = 0;
+    bsdf.int_ior = 1.5046f; bsdf.ext_ior = 1.000277f; bsdf.alpha_slot = -1; bsdf.color_slot = -1; bsdf.texture = -1; bsdf.material = 0;
     uint32_t flags = 0;
     if (si.valid && si.bsdf >= 0) { bsdf = S.bsdfs[si.bsdf]; flags = bsdf_flags(bsdf); }
     if (si.valid && bsdf.texture >= 0 && bsdf.texture < S.n_textures) {   // the reflectance at this point: everything below sees it as a constant

@@ -349,6 +349,16 @@ def _alpha_slots(scene, params: ParamGrads) -> int:
     return n
 
 
+def _material_slots(scene, params: ParamGrads) -> int:
+    """The number of conductor material slots the colour adjoint serves (``Scene.attach_conductor``); ``params.conductor`` must
+    hold them."""
+    n = len(getattr(scene, "material_slots", ()))                 # (bench.py's SyntheticScene has none)
+    if n and (params.conductor is None or params.M < n):
+        raise ValueError("conductor materials are attached: the gradient buffer must come from Scene.param_grads() after "
+                         "attach_conductor")
+    return n
+
+
 def _rigid_slot_count(rigid_slots, params: ParamGrads) -> int:
     """The number of rigid slots (``Scene.rigid_slots``, from ``Scene.attach_rigid``); ``params.rigid`` must hold them."""
     n = len(rigid_slots)
@@ -490,25 +500,28 @@ class PRBIntegrator:
         return _develop_forward(scene, sensor, [self._color_forward(scene, params, sensor, seed, spp)])
 
     def _color_attached(self, scene, params: ParamGrads):
-        """(anything for the colour pass?, textures attached?, number of roughness slots).  Neither a colour, a texture nor a
-        roughness attached is nothing this phase differentiates: skipped -- and refused by `prb` when geometry is attached instead."""
+        """(anything for the colour pass?, textures attached?, number of roughness slots, number of conductor material slots).
+        Neither a colour, a texture, a roughness nor a conductor material attached is nothing this phase differentiates: skipped --
+        and refused by `prb` when geometry is attached instead."""
         texs = bool(scene.texture_slots)
         n_alpha = _alpha_slots(scene, params)
-        if not scene.color_slots and not texs and not n_alpha and not self.reparam and scene.has_attached_geometry():
+        n_mat = _material_slots(scene, params)
+        if not scene.color_slots and not texs and not n_alpha and not n_mat and not self.reparam and scene.has_attached_geometry():
             raise NotImplementedError(
                 "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
                 "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
                 "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
-        return bool(scene.color_slots or texs or n_alpha), texs, n_alpha
+        return bool(scene.color_slots or texs or n_alpha or n_mat), texs, n_alpha, n_mat
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
         primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``) and the
-        roughness tangents ``params.alpha`` of the attached roughconductors (``Scene.trace_alpha_forward``).  Returns this rank's
-        (primal film, tangent film), or None when neither a colour, a texture nor a roughness is attached.  (The tangent film is
-        developed with the film's own float-atomic weights, while the backward pass of a call with a roughness divides by their
-        fixed-point sums: ~1e-7 apart, far inside the transpose identity's bound.)"""
-        any_attached, texs, n_alpha = self._color_attached(scene, params)
+        roughness tangents ``params.alpha`` of the attached roughconductors (``Scene.trace_alpha_forward``) and the material tangents
+        ``params.conductor`` of the attached conductors (``Scene.trace_material_forward``).  Returns this rank's (primal film,
+        tangent film), or None when none of them is attached.  (The tangent film is developed with the film's own float-atomic
+        weights, while the backward pass of a call with a roughness or a material divides by their fixed-point sums: ~1e-7 apart,
+        far inside the transpose identity's bound.)"""
+        any_attached, texs, n_alpha, n_mat = self._color_attached(scene, params)
         if not any_attached:
             return None
         si, s, spp, _, accum, tiles = _pass_frame(scene, sensor, spp, "color")
@@ -517,6 +530,7 @@ class PRBIntegrator:
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
         tex_t = _texture_tangents(scene, params) if texs else None
         alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
+        mat_t = params.conductor[:n_mat].to(scene.device, torch.float32).contiguous() if n_mat else None
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
@@ -525,34 +539,39 @@ class PRBIntegrator:
                 dL = dL + scene.trace_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
             if n_alpha:
                 dL = dL + scene.trace_alpha_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), alpha_t)
+            if n_mat:
+                dL = dL + scene.trace_material_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), mat_t)
             film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        any_attached, texs, n_alpha = self._color_attached(scene, params)
+        any_attached, texs, n_alpha, n_mat = self._color_attached(scene, params)
         if not any_attached:
             return
+        exact = bool(n_alpha or n_mat)                                  # the call must repeat bit for bit: fixed-point film weights
         si, s, spp, world, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         kept, counts = [], None
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
-            kept.append((film_pos, sums, radiance.contiguous() if texs or n_alpha else None))
-            if n_alpha:
+            kept.append((film_pos, sums, radiance.contiguous() if texs or exact else None))
+            if exact:
                 if counts is None:
                     counts = torch.zeros((s.height, s.width), device=scene.device, dtype=torch.int64)
                 film_weight_counts(counts, film_pos, s.rfilter)
         if world > 1:
             _dist.allreduce_param_grads(accum)
-            if n_alpha:
+            if exact:
                 _dist.allreduce_param_grads(counts)
-        # (with a roughness attached the call repeats bit for bit: the weights the film adjoint divides by are the exact sums)
-        weight_img = accum[..., 3] if not n_alpha else (counts.double() / _WEIGHT_ONE).float()
+        # (with a roughness or a conductor material attached the call repeats bit for bit: the weights the film adjoint divides by
+        # are the exact sums)
+        weight_img = accum[..., 3] if not exact else (counts.double() / _WEIGHT_ONE).float()
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
         tex = _TexelBuffers(_texture_shapes(scene, params, "gradient buffer"), scene.device) if texs else None
         d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
+        d_mat = torch.zeros((n_mat, 3, 3), device=scene.device, dtype=torch.float32) if n_mat else None
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
@@ -560,6 +579,8 @@ class PRBIntegrator:
                 scene.trace_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
             if n_alpha:                                                 # the roughness adjoint: another replay of them
                 scene.trace_alpha_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_alpha)
+            if n_mat:                                                   # the conductor material adjoint: one more
+                scene.trace_material_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_mat)
         contrib = contrib / values.clamp_min(1e-12)
         if world > 1:
             _dist.allreduce_param_grads(contrib)
@@ -573,6 +594,10 @@ class PRBIntegrator:
             if world > 1:
                 _dist.allreduce_param_grads(d_alpha)                    # this call's roughness contribution, once
             params.alpha[:n_alpha] += d_alpha.to(params.alpha.device)
+        if n_mat:
+            if world > 1:
+                _dist.allreduce_param_grads(d_mat)                      # this call's material contribution, once
+            params.conductor[:n_mat] += d_mat.to(params.conductor.device)
 
 
 class PRBReparamIntegrator(PRBIntegrator):

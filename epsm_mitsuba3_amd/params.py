@@ -20,18 +20,22 @@ class ParamGrads:
     [translation, rotation about the slot's pivot] of the rigid slots (``Scene.attach_rigid``) as [force, torque];
     ``cam_rotation (3)``: d/d omega of ``to_world <- Rot(omega) to_world`` about the sensor's own position, world axes, at omega = 0
     (``Scene.attach_sensor(rotation=True)``).  These two sections exist only when asked for (``n_rigid``, ``cam_rotation``; None
-    otherwise) and follow the textures: a buffer constructed without them has the size and the offsets it always had.  Vertex
+    otherwise) and follow the textures: a buffer constructed without them has the size and the offsets it always had.
+    ``conductor (M,3,3)``: d/d [eta, k, specular_reflectance] x rgb of the material slots (``Scene.attach_conductor``), likewise
+    only when asked for (``n_conductors``), at the very END, after ``cam_rotation``.  Vertex
     indices are global: meshes are concatenated and a mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
 
     def __init__(self, n_vertices: int, n_bsdfs: int = 0, device="cuda", mesh_slices: Optional[dict] = None, n_colors: int = 0,
-                 tex_shapes: Optional[Sequence[Tuple[int, int]]] = None, n_rigid: int = 0, cam_rotation: bool = False):
+                 tex_shapes: Optional[Sequence[Tuple[int, int]]] = None, n_rigid: int = 0, cam_rotation: bool = False,
+                 n_conductors: int = 0):
         self.V, self.B, self.C = int(n_vertices), int(n_bsdfs), int(n_colors)
         self.tex_shapes = [(int(h), int(w)) for h, w in (tex_shapes or [])]
         n0 = 6 * self.V + self.B + 3 + 3 * self.C
         self.R, self.has_cam_rotation = int(n_rigid), bool(cam_rotation)
         n1 = n0 + sum(3 * h * w for h, w in self.tex_shapes)
         n = n1 + 6 * self.R + (3 if self.has_cam_rotation else 0)
-        self.flat = torch.zeros(n, device=device, dtype=torch.float32)
+        self.M = int(n_conductors)
+        self.flat = torch.zeros(n + 9 * self.M, device=device, dtype=torch.float32)
         self.pos = self.flat[: 3 * self.V].view(self.V, 3)
         self.nrm = self.flat[3 * self.V: 6 * self.V].view(self.V, 3)
         self.alpha = self.flat[6 * self.V: 6 * self.V + self.B]
@@ -44,6 +48,7 @@ class ParamGrads:
             o += 3 * h * w
         self.rigid = self.flat[n1: n1 + 6 * self.R].view(self.R, 6) if self.R else None
         self.cam_rotation = self.flat[n1 + 6 * self.R: n] if self.has_cam_rotation else None
+        self.conductor = self.flat[n:].view(self.M, 3, 3) if self.M else None
         self.mesh_slices = dict(mesh_slices or {})
         self._scratch: Optional[ParamGrads] = None             # scratch(): allocated on first use
 
@@ -57,7 +62,8 @@ class ParamGrads:
         s = self._scratch
         if s is None:
             s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C,
-                                           tex_shapes=self.tex_shapes, n_rigid=self.R, cam_rotation=self.has_cam_rotation)
+                                           tex_shapes=self.tex_shapes, n_rigid=self.R, cam_rotation=self.has_cam_rotation,
+                                           n_conductors=self.M)
         return s.zero_()
 
     def texture(self, slot: int) -> torch.Tensor:

@@ -29,6 +29,7 @@ from .params import ParamGrads
 
 MESH_VERTEX_NORMALS, MESH_FLIP_NORMALS, MESH_POS_ATTACHED, MESH_NRM_ATTACHED, MESH_IS_MESH, MESH_HAS_UV = 1, 2, 4, 8, 16, 32
 MAX_ALPHA_GRADS = 8          # EPSM_MAX_ALPHA_GRADS (include/epsm_trace.h; tests/test_alpha_abi.py holds the two together)
+MAX_MATERIAL_GRADS = 4       # EPSM_MAX_MATERIAL_GRADS (include/epsm_trace.h; tests/test_material_adjoint.py holds the two together)
 BSDF_TYPES = {"diffuse": 0, "conductor": 1, "roughconductor": 2, "dielectric": 3}
 
 # complex IORs at R,G,B for the `material` names the experiments use (approximate: Mitsuba
@@ -61,7 +62,7 @@ class EpsmBsdf(C.Structure):
     _fields_ = [("type", C.c_uint32), ("twosided", C.c_uint32), ("distr", C.c_uint32), ("sample_visible", C.c_uint32),
                 ("reflectance", C.c_float * 3), ("alpha", C.c_float), ("eta", C.c_float * 3), ("k", C.c_float * 3),
                 ("int_ior", C.c_float), ("ext_ior", C.c_float), ("alpha_slot", C.c_int32), ("color_slot", C.c_int32),
-                ("texture", C.c_int32), ("pad", C.c_uint32)]
+                ("texture", C.c_int32), ("material", C.c_uint32)]
 
 
 class EpsmTexture(C.Structure):
@@ -727,6 +728,7 @@ class Scene:
         self._tile_paths = int(tile_paths)
         self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it bounds prb_reparam's tiles (tile_plan)
         self.alpha_slots: Dict[int, int] = {}
+        self.material_slots: Dict[int, int] = {}   # conductors attached for the material adjoint (attach_conductor): BSDF index -> slot
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
         self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoint: ("bsdf" | "envmap", index)
         self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
@@ -1025,6 +1027,44 @@ class Scene:
         self._upload()
         return self.alpha_slots[i]
 
+    def attach_conductor(self, bsdf_name: str) -> int:
+        """``dr.enable_grad`` of ``params['<bsdf>.eta.value']``, ``['<bsdf>.k.value']`` and ``['<bsdf>.specular_reflectance.value']`` of
+        a ``conductor`` / ``roughconductor`` (inside ``twosided`` or not) for the material adjoint of the colour pass
+        (``epsm_trace_paths_material_backward``; PRBIntegrator).  Returns the slot: ``ParamGrads.conductor[slot]`` is (3,3) =
+        [eta, k, specular_reflectance] x rgb."""
+        i = self.bsdf_names.index(bsdf_name)
+        b = self.bsdf_desc[i]
+        if b["type"] not in (BSDF_TYPES["conductor"], BSDF_TYPES["roughconductor"]):
+            raise ValueError(f"attach_conductor: {bsdf_name!r} is neither a conductor nor a roughconductor")
+        if any(float(x) <= 0 for x in b["eta"]) or any(float(x) == 0 for x in b["reflectance"]):
+            raise ValueError(f"attach_conductor: {bsdf_name!r} has a channel with eta <= 0 or a zero specular_reflectance -- the default "
+                             "`eta = 0, k = 1` is the 100 % mirror, whose Fresnel term is the constant 1 and has no derivative; "
+                             "give the BSDF a material or eta / k to fit (set_conductor)")
+        if i not in self.material_slots:
+            if len(self.material_slots) >= MAX_MATERIAL_GRADS:
+                raise ValueError(f"at most {MAX_MATERIAL_GRADS} conductor material parameters (EPSM_MAX_MATERIAL_GRADS)")
+            self.material_slots[i] = len(self.material_slots)
+            self._upload()
+        return self.material_slots[i]
+
+    def conductor_values(self) -> torch.Tensor:
+        """(M,3,3) current [eta, k, specular_reflectance] x rgb of the attached conductors, slot order."""
+        rows = [[[float(x) for x in self.bsdf_desc[i][key]] for key in ("eta", "k", "reflectance")]
+                for i, _ in sorted(self.material_slots.items(), key=lambda kv: kv[1])]
+        return torch.tensor(rows, dtype=torch.float32, device=self.device).reshape(-1, 3, 3)
+
+    def set_conductor(self, bsdf_name: str, eta=None, k=None, specular_reflectance=None):
+        """``params['<bsdf>.eta.value'] = eta`` (and / or ``k``, ``specular_reflectance``; rgb each) ``; params.update()``: only the
+        BSDF table is rewritten (in place)."""
+        b = self.bsdf_desc[self.bsdf_names.index(bsdf_name)]
+        if b["type"] not in (BSDF_TYPES["conductor"], BSDF_TYPES["roughconductor"]):
+            raise ValueError(f"set_conductor: {bsdf_name!r} is neither a conductor nor a roughconductor")
+        for key, v in (("eta", eta), ("k", k), ("reflectance", specular_reflectance)):
+            if v is not None:
+                v = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32).reshape(-1)
+                b[key] = np.ascontiguousarray(np.broadcast_to(v, (3,)) if v.size == 1 else v.reshape(3))
+        self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
+
     def attach_color(self, bsdf_name: str) -> int:
         """``dr.enable_grad(params['<bsdf>.reflectance.value'])`` for the colour adjoint (PRBIntegrator): diffuse BSDFs."""
         i = self.bsdf_names.index(bsdf_name)
@@ -1166,6 +1206,7 @@ class Scene:
             c.alpha_slot = self.alpha_slots.get(i, -1)
             c.color_slot = self.color_slots.index(("bsdf", i)) if ("bsdf", i) in self.color_slots else -1
             c.texture = b.get("texture_index", -1)
+            c.material = self.material_slots.get(i, -1) + 1
         return bs
 
     def set_vertex_positions(self, mesh_name: str, v):
@@ -1251,7 +1292,7 @@ class Scene:
     def param_grads(self) -> ParamGrads:
         return ParamGrads(self.V, len(self.alpha_slots), device=self.device, mesh_slices=self.mesh_slices,
                           n_colors=len(self.color_slots), tex_shapes=self.texture_shapes(), n_rigid=len(self.rigid_slots),
-                          cam_rotation=self.sensor_rotation)
+                          cam_rotation=self.sensor_rotation, n_conductors=len(self.material_slots))
 
     # -- upload ----------------------------------------------------------------------------------
     def _upload(self):
@@ -1473,12 +1514,12 @@ class Scene:
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
-        if Cn == 0 and not self.texture_slots and not self.alpha_slots:
+        if Cn == 0 and not self.texture_slots and not self.alpha_slots and not self.material_slots:
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
         film_pos = torch.empty((n, 2), device=dev, dtype=torch.float32)
         radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
         valid = torch.empty((n,), device=dev, dtype=torch.uint8)
-        # (textures or roughnesses alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the replays
+        # (textures, roughnesses or conductor materials alone: one slot's sums, none of them returned -- the entry point takes 1..4 slots, and the replays
         # of the texel and roughness adjoints must see the radiance of this very estimator)
         sums = torch.empty((n, max(Cn, 1), 3), device=dev, dtype=torch.float32)
         self._replay("epsm_trace_paths_color", sensor_index, seed, spp, max_depth, lo, hi, film_pos, radiance, valid, sums, int(max(Cn, 1)))
@@ -1548,6 +1589,34 @@ class Scene:
         assert tangent_alpha.device.type == self.device.type
         d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
         self._replay("epsm_trace_paths_bsdf_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_alpha, int(B), d_radiance)
+        return d_radiance
+
+    def trace_material_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
+                                grad_material):
+        """``epsm_trace_paths_material_backward``: ADDS d loss / d [eta, k, specular_reflectance] x rgb of paths [lo, hi) to
+        ``grad_material`` (M,3,3), one (3,3) per material slot (``attach_conductor``), given the radiance of the primal pass
+        (``trace_color`` with the same seed) and its adjoint.  No atomics: the same call gives the same bits."""
+        n, M = hi - lo, len(self.material_slots)
+        for t_ in (radiance, adj_radiance):
+            self._rows(t_, n, 3)
+        assert grad_material.is_contiguous() and grad_material.dtype == torch.float32 and tuple(grad_material.shape) == (M, 3, 3)
+        assert grad_material.device.type == self.device.type
+        nbytes = int(self._runtime()[0].epsm_trace_material_workspace_bytes(C.c_int64(n)))
+        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_material_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance,
+                     grad_material, int(M), work, C.c_size_t(work.numel() * 4))
+
+    def trace_material_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance,
+                               tangent_material):
+        """``epsm_trace_paths_material_forward``: the transpose of ``trace_material_backward`` -- for one (3,3) tangent per material
+        slot returns d radiance (n, 3) of paths [lo, hi)."""
+        n, M = hi - lo, len(self.material_slots)
+        self._rows(radiance, n, 3)
+        assert tangent_material.is_contiguous() and tangent_material.dtype == torch.float32
+        assert tuple(tangent_material.shape) == (M, 3, 3) and tangent_material.device.type == self.device.type
+        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_material_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_material, int(M),
+                     d_radiance)
         return d_radiance
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,

@@ -116,7 +116,8 @@ typedef struct EpsmBsdf {
     int32_t color_slot;              /* diffuse: slot of `reflectance` in the colour adjoint of epsm_trace_paths_color,
                                         -1 = not optimised */
     int32_t texture;                 /* diffuse: index into EpsmScene.textures of the `bitmap` its reflectance is, -1 = `reflectance` */
-    uint32_t pad;
+    uint32_t material;               /* conductor / roughconductor: 0 = eta, k, specular_reflectance not optimised, s + 1 = material
+                                        slot s of epsm_trace_paths_material_backward (the word that was padding: 0 in every table) */
 } EpsmBsdf;
 
 /* A `bitmap` texture (src/textures/bitmap.cpp): linear RGB texels, looked up at si.uv as there -- uv * (width, height) - 0.5,
@@ -411,6 +412,45 @@ int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmSensor *sens
                                   const float *radiance, const float *tangent_alpha, int B,
                                   float *d_radiance, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_material_backward -- the CONDUCTOR MATERIAL adjoint of `prb` (prb.py:145-158, 209-226; sampling, Russian
+ *   roulette and the MIS weights detached): paths [path_offset, path_offset + N) are replayed under the primal seed as
+ *   epsm_trace_paths_color traced them, and d loss / d [eta, k, specular_reflectance], per colour channel, is ADDED to
+ *   grad_material[EpsmBsdf.material - 1] for every `conductor` / `roughconductor` BSDF with 1 <= material <= M.  The sample's
+ *   weight is F(cos; eta, k) x specular_reflectance x w (conductor.cpp:235-270, roughconductor.cpp:225-300; F: fresnel.h:92-117)
+ *   with w, the pdf and the direction free of the three, so nothing is lost to the detached sampling.  At an active bounce on
+ *   such a BSDF, per channel c,
+ *     - the sampled direction adds adj_c L_ind,c x [d F_c / d eta_c / F_c, d F_c / d k_c / F_c, 1 / R_c], L_ind = what the path
+ *       collects behind the bounce, cos = wi . normalize(wi + wo) (wi.z for the delta lobe);
+ *     - the emitter sample (roughconductor.cpp:302-400; a delta lobe evaluates to 0) adds the same with Lr_dir in place of
+ *       L_ind at the half vector of the emitter's direction (nothing when occluded).
+ *   A term whose denominator is 0 or which is not finite adds nothing; d F is 0 where F is cut to a constant (the
+ *   `eta = 0, k = 1` mirror).
+ *     radiance      (N,3) L of every path from the primal pass (epsm_trace_paths_color with the same seed / spp / depths)
+ *     adj_radiance  (N,3) d loss / d L
+ *     grad_material (M,3,3) f32 = [eta, k, specular_reflectance] x rgb per slot, added to; M <= EPSM_MAX_MATERIAL_GRADS
+ *                   (EPSM_EINVAL otherwise: nothing is dropped silently)
+ *     workspace     device memory, 16-byte aligned, >= epsm_trace_material_workspace_bytes(N); scratch
+ *   No float atomics: each workgroup of 128 paths reduces its sums to one row of 9 EPSM_MAX_MATERIAL_GRADS floats of the
+ *   workspace, a second launch adds the rows in float64 in a fixed order -- two calls with the same arguments give the same
+ *   bits.  No host synchronisation.
+ * epsm_trace_paths_material_forward -- its exact transpose: the same replay WRITES d_radiance (N,3), per channel the sum over
+ *   the path's terms of their coefficients x tangent_material[slot], so that sum(adj_radiance * d_radiance) =
+ *   sum(grad_material * tangent_material).  One launch.
+ * ------------------------------------------------------------------------- */
+#define EPSM_MAX_MATERIAL_GRADS 4
+size_t epsm_trace_material_workspace_bytes(int64_t N);
+int epsm_trace_paths_material_backward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                       uint32_t seed, int spp, int max_depth, int rr_depth,
+                                       int64_t path_offset, int64_t N,
+                                       const float *radiance, const float *adj_radiance, float *grad_material, int M,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+int epsm_trace_paths_material_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                      uint32_t seed, int spp, int max_depth, int rr_depth,
+                                      int64_t path_offset, int64_t N,
+                                      const float *radiance, const float *tangent_material, int M,
+                                      float *d_radiance, void *stream);
+
 /* epsm_film_splat -- ImageBlock::put + weight division (film.develop): accumulates
  * radiance with the reconstruction filter into accum (height,width,4) [r,g,b,w] (atomics);
  * epsm_film_develop divides into image (height,width,3). */
@@ -453,11 +493,13 @@ int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radia
  *   EPSM_PROBE_BSDF_EVAL          in wi (3), wo (3); cfg = EpsmBsdf             out value incl. cosine (3), pdf              eval_pdf() (src/bsdfs/tests/test_diffuse.py:13-35, test_twosided.py:29-45)
  *   EPSM_PROBE_MICROFACET_DALPHA  in m (3), v (3); cfg = EpsmBsdf                out d ln D(m) / d alpha, d ln smith_g1(v, m) / d alpha, D(m), smith_g1(v, m)   the closed forms of the roughness adjoint (epsm_trace_paths_bsdf_backward)
  *   EPSM_PROBE_BSDF_DALPHA        in wi (3), wo (3); cfg = EpsmBsdf             out d value / d alpha (3), d ln value / d alpha   roughconductor; 0 for the others
+ *   EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD  in cos_theta_i, eta, k                   out F, d F / d eta, d F / d k                the closed forms of the material adjoint (epsm_trace_paths_material_backward; fresnel.h:92-117)
  * in: (n, EPSM_PROBE_IN) floats, out: (n, EPSM_PROBE_OUT) floats, device pointers; cfg: HOST pointer to the struct named
  * above (NULL otherwise).  Not on any hot path. */
 enum { EPSM_PROBE_TEA = 0, EPSM_PROBE_PCG32 = 1, EPSM_PROBE_SAMPLER = 2, EPSM_PROBE_MICROFACET = 3, EPSM_PROBE_MICROFACET_SAMPLE = 4,
        EPSM_PROBE_FRESNEL = 5, EPSM_PROBE_FRESNEL_CONDUCTOR = 6, EPSM_PROBE_RFILTER = 7, EPSM_PROBE_PRIMARY_RAY = 8, EPSM_PROBE_BSDF_SAMPLE = 9,
-       EPSM_PROBE_BSDF_EVAL = 10, EPSM_PROBE_MICROFACET_DALPHA = 11, EPSM_PROBE_BSDF_DALPHA = 12, EPSM_PROBE_COUNT = 13 };
+       EPSM_PROBE_BSDF_EVAL = 10, EPSM_PROBE_MICROFACET_DALPHA = 11, EPSM_PROBE_BSDF_DALPHA = 12,
+       EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD = 13, EPSM_PROBE_COUNT = 14 };
 #define EPSM_PROBE_IN 8
 #define EPSM_PROBE_OUT 16
 int epsm_probe(int what, int64_t n, const float *in, float *out, const void *cfg, void *stream);
