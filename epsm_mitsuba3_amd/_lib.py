@@ -245,6 +245,12 @@ def declare_tracer(lib):
         lib.epsm_trace_paths_material_backward.argtypes = mat_args + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.epsm_trace_paths_material_forward.restype = C.c_int
         lib.epsm_trace_paths_material_forward.argtypes = mat_args + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "epsm_trace_paths_alpha_texture_backward"):   # (the HIP library; of the host builds, tests/host_harness/trace_alphamap_host.cpp)
+        am_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        lib.epsm_trace_paths_alpha_texture_backward.restype = C.c_int
+        lib.epsm_trace_paths_alpha_texture_backward.argtypes = am_args + [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.epsm_trace_paths_alpha_texture_forward.restype = C.c_int
+        lib.epsm_trace_paths_alpha_texture_forward.argtypes = am_args + [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int

@@ -597,6 +597,25 @@ EPSM_HD F3 tex_eval(const EpsmTexture &T, float u, float v, F3 *du = nullptr, F3
     if (dv) *dv = ((c - a) * (1.f - fx) + (e - b) * fx) * (float) T.height;
     return a * ((1.f - fx) * (1.f - fy)) + b * (fx * (1.f - fy)) + c * ((1.f - fx) * fy) + e * (fx * fy);
 }
+// the same lookup in a 1-channel bitmap (EpsmTexture.channels = 1: a roughconductor's alpha, roughconductor.cpp:195-198)
+EPSM_HD float tex_eval_1(const EpsmTexture &T, float u, float v, float *du = nullptr, float *dv = nullptr) {
+    const float x = u * (float) T.width - 0.5f, y = v * (float) T.height - 0.5f;
+    if (du) *du = 0.f;
+    if (dv) *dv = 0.f;
+    if (T.nearest) {
+        const int i = tex_wrap((int) floorf(x + 0.5f), T.width), j = tex_wrap((int) floorf(y + 0.5f), T.height);
+        return T.texels[(int64_t) j * T.width + i];
+    }
+    const float fxf = floorf(x), fyf = floorf(y);
+    const int i0 = tex_wrap((int) fxf, T.width), j0 = tex_wrap((int) fyf, T.height), i1 = tex_wrap((int) fxf + 1, T.width),
+              j1 = tex_wrap((int) fyf + 1, T.height);
+    const float fx = x - fxf, fy = y - fyf;
+    const float a = T.texels[(int64_t) j0 * T.width + i0], b = T.texels[(int64_t) j0 * T.width + i1],
+                c = T.texels[(int64_t) j1 * T.width + i0], e = T.texels[(int64_t) j1 * T.width + i1];
+    if (du) *du = ((b - a) * (1.f - fy) + (e - c) * fy) * (float) T.width;
+    if (dv) *dv = ((c - a) * (1.f - fx) + (e - b) * fx) * (float) T.height;
+    return a * ((1.f - fx) * (1.f - fy)) + b * (fx * (1.f - fy)) + c * ((1.f - fx) * fy) + e * (fx * fy);
+}
 
 // ---------------------------------------------------------------------------
 // emitters (src/emitters/area.cpp, point.cpp; src/render/scene.cpp:226-300; src/render/mesh.cpp sample_position)
@@ -1130,9 +1149,14 @@ EPSM_HD void path_bounce(const TraceArgs &A, int64_t i, int iteration, PathState
     bsdf.int_ior = 1.5046f; bsdf.ext_ior = 1.000277f; bsdf.alpha_slot = -1; bsdf.color_slot = -1; bsdf.texture = -1; bsdf.material = 0;
     uint32_t flags = 0;
     if (si.valid && si.bsdf >= 0) { bsdf = S.bsdfs[si.bsdf]; flags = bsdf_flags(bsdf); }
-    if (si.valid && bsdf.texture >= 0 && bsdf.texture < S.n_textures) {   // the reflectance at this point: everything below sees it as a constant
-        const F3 r = tex_eval(S.textures[bsdf.texture], si.uvx, si.uvy);
-        bsdf.reflectance[0] = r.x; bsdf.reflectance[1] = r.y; bsdf.reflectance[2] = r.z;
+    if (si.valid && bsdf.texture >= 0 && bsdf.texture < S.n_textures) {   // the reflectance / the roughness at this point: everything below sees it as a constant
+        const EpsmTexture &T = S.textures[bsdf.texture];
+        if (T.channels == 1) {                                            // (a texture of the other kind is ignored: a 1-channel array is never read as three)
+            if (bsdf.type == EPSM_BSDF_ROUGHCONDUCTOR_T) bsdf.alpha = tex_eval_1(T, si.uvx, si.uvy);
+        } else if (bsdf.type == EPSM_BSDF_DIFFUSE_T) {
+            const F3 r = tex_eval(T, si.uvx, si.uvy);
+            bsdf.reflectance[0] = r.x; bsdf.reflectance[1] = r.y; bsdf.reflectance[2] = r.z;
+        }
     }
 
     // ---- EPSM_TRACE_GRADIENT_ONLY, native log: a vertex at which the path is retired BY THE RULE (cp::gradient_live: a Diffuse,

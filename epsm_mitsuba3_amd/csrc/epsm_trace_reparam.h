@@ -492,7 +492,8 @@ EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, con
     // ---- a `bitmap` reflectance follows the point the ray sees: rho(uv') / rho(uv) per channel multiplies both BSDF values below
     //      (bitmap.cpp:366-418: the texture lookup is attached to si.uv, mesh.cpp:736-745)
     V3<T> tex = mk3<T>(T(1.f), T(1.f), T(1.f));
-    if (cur.bsdf.texture >= 0 && cur.bsdf.texture < S.n_textures && cur.bsdf.type == EPSM_BSDF_DIFFUSE_T) {
+    if (cur.bsdf.texture >= 0 && cur.bsdf.texture < S.n_textures && cur.bsdf.type == EPSM_BSDF_DIFFUSE_T &&
+        S.textures[cur.bsdf.texture].channels != 1) {
         float a0[2] = {0.f, 0.f}, a1[2] = {1.f, 0.f}, a2[2] = {0.f, 1.f};                    // no texture coordinates: uv = (b1, b2)
         if ((c.mesh_flags & EPSM_MESH_HAS_UV) && S.texcoords)
             for (int j = 0; j < 2; ++j) { a0[j] = S.texcoords[2 * (int64_t) c.vi[0] + j]; a1[j] = S.texcoords[2 * (int64_t) c.vi[1] + j]; a2[j] = S.texcoords[2 * (int64_t) c.vi[2] + j]; }

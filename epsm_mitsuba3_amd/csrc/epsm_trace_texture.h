@@ -110,7 +110,9 @@ struct TexObserver {
         const EpsmScene &S = T.A.S;
         const bool env_on = S.env.kind == EPSM_ENV_ENVMAP && T.buf[kEnvBuf] != nullptr;
         if (si.valid) {
-            const int k = bsdf.type == EPSM_BSDF_DIFFUSE_T && bsdf.texture >= 0 && bsdf.texture < S.n_textures ? buffer_of(bsdf.texture) : -1;
+            // (a 1-channel texture is a roughness map: its buffer is (H, W) and belongs to epsm_trace_alphamap.h)
+            const int k = bsdf.type == EPSM_BSDF_DIFFUSE_T && bsdf.texture >= 0 && bsdf.texture < S.n_textures &&
+                          S.textures[bsdf.texture].channels != 1 ? buffer_of(bsdf.texture) : -1;
             if (k >= 0) {
                 const F3 rho = ld3(bsdf.reflectance);                          // tex_eval(uv) (path_bounce)
                 const F3 after = radiance - (L + Le);                           // (the order in which InlineVis::direct sums)

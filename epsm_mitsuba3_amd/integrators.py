@@ -27,7 +27,7 @@ from . import profiler as _prof
 from .film import (_WEIGHT_ONE, develop_tangent, film_adjoint, film_adjoint_reparam, film_adjoint_reparam_torch,  # noqa: F401
                    film_splat_tangent, film_splat_tangent_torch, film_weight_counts)
 from .manifold_grad import OUTLIER_CLIP, calc_grad as _calc_grad, manifold_grad_packed
-from .params import ParamGrads
+from .params import ParamGrads, tex_numel, tex_shape, tex_view
 from .records import PackedLog, PackedRecords, PackedScatter
 from .tangent_scatter import (backward_pass, backward_pass_packed, first_vertex_tangent, manifold_grad_scatter,
                               scatter)
@@ -171,6 +171,12 @@ class EPSMIntegrator:
         gradient_only = getattr(scene, "supports_gradient_only", False)
         first_hit = getattr(scene, "supports_first_hit_fusion", False)
         rigid_slots = getattr(scene, "rigid_slots", ())
+        if getattr(scene, "alpha_map_slots", lambda: ())():
+            # the logged half vector depends on alpha, so the map's gradient is not zero here -- and the record carries no uv to
+            # scatter it by
+            raise NotImplementedError("the 5-channel manifold branch has no gradient for a roughness map (a '<bsdf>.alpha.data' slot "
+                                      "is attached): the vertex log carries no texture coordinates to scatter it by; `prb` "
+                                      "differentiates it (a 3-channel gradient image)")
         if getattr(scene, "sensor_rotation", False):
             # this branch transports d / d ray.o alone (epsm.py:260-261): the sensor's rotation has no term in it
             raise NotImplementedError("the 5-channel manifold branch differentiates the sensor's position only (epsm.py:260-261); the "
@@ -315,20 +321,21 @@ def _develop_forward(scene, sensor: int, films) -> torch.Tensor:
 
 
 class _TexelBuffers:
-    """One flat buffer of the texel gradients of a backward call, (H, W, 3) views per texture slot."""
+    """One flat buffer of the texel gradients of a backward call, one view per texture slot: (H, W, 3), or (H, W) for a
+    roughness map (``shapes``: ``ParamGrads.tex_shapes``)."""
 
     def __init__(self, shapes, device):
-        self.flat = torch.zeros(sum(3 * h * w for h, w in shapes), device=device, dtype=torch.float32)
+        self.flat = torch.zeros(sum(tex_numel(t) for t in shapes), device=device, dtype=torch.float32)
         self.views, o = [], 0
-        for h, w in shapes:
-            self.views.append(self.flat[o: o + 3 * h * w].view(h, w, 3))
-            o += 3 * h * w
+        for t in shapes:
+            self.views.append(self.flat[o: o + tex_numel(t)].view(tex_view(t)))
+            o += tex_numel(t)
 
 
 def _texture_shapes(scene, params: ParamGrads, what: str):
     """The shapes of the attached textures; ``params`` (``what``: "gradient buffer" / "tangent") must be laid out for them."""
-    shapes = scene.texture_shapes()
-    if params.tex_shapes != list(shapes):
+    shapes = [tex_shape(t) for t in scene.texture_shapes()]
+    if params.tex_shapes != shapes:
         raise ValueError(f"texture slots are attached: the {what} must come from Scene.param_grads() after attach_texture")
     return shapes
 
@@ -337,6 +344,12 @@ def _texture_tangents(scene, params: ParamGrads):
     """The texel tangents the forward replay reads, per slot: the bitmap's tangent (``ParamGrads.texture``) times its scale."""
     shapes = _texture_shapes(scene, params, "tangent")
     return [(params.texture(k).to(scene.device, torch.float32) * scene.texture_scale(k)).contiguous() for k in range(len(shapes))]
+
+
+def _texture_kinds(scene):
+    """(any RGB texture slot -- a diffuse bitmap, the envmap -- attached?, any roughness-map slot?): each has its own replay."""
+    n_alpha = len(scene.alpha_map_slots())
+    return len(scene.texture_slots) > n_alpha, n_alpha > 0
 
 
 def _alpha_slots(scene, params: ParamGrads) -> int:
@@ -418,6 +431,12 @@ def _pose_attached(scene, params: ParamGrads, what: str):
     argument of the sensor's pass cannot carry, and a ``params`` (``what``: "gradient buffer" / "tangent") laid out before the
     rotation or the slots were attached -- before any pass runs: a refused call leaves nothing behind."""
     cam = rot = False
+    if scene.has_alpha_map() and (scene.sensor_attached or scene.has_attached_geometry() or scene.rigid_slots):
+        # the point a ray sees slides over the map: d f / d alpha x d alpha / d uv x d uv / d theta needs alpha as a dual number
+        # in bsdf_eval_t -- without it the geometry's gradient would silently lack a term
+        raise NotImplementedError("prb_reparam: the scene has a roughness map (a roughconductor whose alpha is a bitmap) and geometry "
+                                  "or the sensor is attached -- the term through the map's uv derivative is not differentiated "
+                                  "here; with nothing geometric attached prb_reparam differentiates the map itself")
     if scene.sensor_attached:
         if any(e["type"] == 1 for e in scene.emitter_desc):
             raise NotImplementedError("prb_reparam: a `point` emitter's position would have to move with the shapes for the "
@@ -529,14 +548,17 @@ class PRBIntegrator:
         values = scene.color_values()                                   # (C,3)
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
         tex_t = _texture_tangents(scene, params) if texs else None
+        rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
         alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
         mat_t = params.conductor[:n_mat].to(scene.device, torch.float32).contiguous() if n_mat else None
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
             dL = (sums * t[None]).sum(dim=1)                            # (n,3)
-            if texs:
+            if rgb_maps:
                 dL = dL + scene.trace_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
+            if alpha_maps:
+                dL = dL + scene.trace_alpha_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
             if n_alpha:
                 dL = dL + scene.trace_alpha_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), alpha_t)
             if n_mat:
@@ -570,13 +592,16 @@ class PRBIntegrator:
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
         tex = _TexelBuffers(_texture_shapes(scene, params, "gradient buffer"), scene.device) if texs else None
+        rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
         d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
         d_mat = torch.zeros((n_mat, 3, 3), device=scene.device, dtype=torch.float32) if n_mat else None
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
-            if texs:                                                    # the texel adjoint: a replay of the same paths
+            if rgb_maps:                                                # the texel adjoint: a replay of the same paths
                 scene.trace_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
+            if alpha_maps:                                              # the roughness maps': its own replay, into the same flat buffer
+                scene.trace_alpha_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
             if n_alpha:                                                 # the roughness adjoint: another replay of them
                 scene.trace_alpha_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_alpha)
             if n_mat:                                                   # the conductor material adjoint: one more

@@ -11,12 +11,32 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 
+def tex_shape(t) -> tuple:
+    """An entry of ``tex_shapes`` as ints: (H, W) -- three channels -- or (H, W, 1) -- a roughness map."""
+    t = tuple(int(x) for x in t)
+    if len(t) not in (2, 3) or (len(t) == 3 and t[2] != 1):
+        raise ValueError(f"tex_shapes: an entry is (H, W) -- three channels -- or (H, W, 1) -- a roughness map --, not {t}")
+    return t
+
+
+def tex_numel(t: tuple) -> int:
+    """Floats of the section of a ``tex_shapes`` entry."""
+    return t[0] * t[1] * (3 if len(t) == 2 else 1)
+
+
+def tex_view(t: tuple) -> tuple:
+    """The shape of the view of a ``tex_shapes`` entry's section: (H, W, 3), or (H, W) for a roughness map."""
+    return (t[0], t[1], 3) if len(t) == 2 else (t[0], t[1])
+
+
 class ParamGrads:
     """``pos (V,3)``: d/d vertex_positions; ``nrm (V,3)``: d/d vertex_normals;
     ``alpha (B)``: d/d per-BSDF roughness; ``cam_origin (3)``: d/d ray origin
     (epsm.py:260-261); ``color (C,3)``: d/d the attached colour parameters (PRBIntegrator); ``texture(slot) (H,W,3)``: d/d the
     texels of an attached bitmap (``Scene.attach_texture``), one section per entry of ``tex_shapes`` at the END of ``flat`` -- every
-    other offset, and the buffer of a scene without textures, are what they are without them.  ``rigid (R,6)``: d/d the twist
+    other offset, and the buffer of a scene without textures, are what they are without them.  An entry of ``tex_shapes`` is
+    ``(H, W)``: three channels, a section of 3 H W floats -- or ``(H, W, 1)``: a roughness map (``'<bsdf>.alpha.data'``), a section of
+    H W floats whose ``texture(slot)`` is (H, W); a buffer built with pairs alone has the size and the offsets it always had.  ``rigid (R,6)``: d/d the twist
     [translation, rotation about the slot's pivot] of the rigid slots (``Scene.attach_rigid``) as [force, torque];
     ``cam_rotation (3)``: d/d omega of ``to_world <- Rot(omega) to_world`` about the sensor's own position, world axes, at omega = 0
     (``Scene.attach_sensor(rotation=True)``).  These two sections exist only when asked for (``n_rigid``, ``cam_rotation``; None
@@ -29,10 +49,10 @@ class ParamGrads:
                  tex_shapes: Optional[Sequence[Tuple[int, int]]] = None, n_rigid: int = 0, cam_rotation: bool = False,
                  n_conductors: int = 0):
         self.V, self.B, self.C = int(n_vertices), int(n_bsdfs), int(n_colors)
-        self.tex_shapes = [(int(h), int(w)) for h, w in (tex_shapes or [])]
+        self.tex_shapes = [tex_shape(t) for t in (tex_shapes or [])]
         n0 = 6 * self.V + self.B + 3 + 3 * self.C
         self.R, self.has_cam_rotation = int(n_rigid), bool(cam_rotation)
-        n1 = n0 + sum(3 * h * w for h, w in self.tex_shapes)
+        n1 = n0 + sum(tex_numel(t) for t in self.tex_shapes)
         n = n1 + 6 * self.R + (3 if self.has_cam_rotation else 0)
         self.M = int(n_conductors)
         self.flat = torch.zeros(n + 9 * self.M, device=device, dtype=torch.float32)
@@ -43,9 +63,9 @@ class ParamGrads:
         # colour parameters of the hybrid scheme's second phase (diffuse reflectances, emitter radiances): (C,3)
         self.color = self.flat[6 * self.V + self.B + 3: n0].view(self.C, 3)
         self._tex, o = [], n0
-        for h, w in self.tex_shapes:
-            self._tex.append(self.flat[o: o + 3 * h * w].view(h, w, 3))
-            o += 3 * h * w
+        for t in self.tex_shapes:
+            self._tex.append(self.flat[o: o + tex_numel(t)].view(tex_view(t)))
+            o += tex_numel(t)
         self.rigid = self.flat[n1: n1 + 6 * self.R].view(self.R, 6) if self.R else None
         self.cam_rotation = self.flat[n1 + 6 * self.R: n] if self.has_cam_rotation else None
         self.conductor = self.flat[n:].view(self.M, 3, 3) if self.M else None
@@ -67,7 +87,8 @@ class ParamGrads:
         return s.zero_()
 
     def texture(self, slot: int) -> torch.Tensor:
-        """(H, W, 3) view of texture slot ``slot`` (``Scene.attach_texture``): d/d the bitmap the user gave."""
+        """(H, W, 3) view of texture slot ``slot`` (``Scene.attach_texture``): d/d the bitmap the user gave; (H, W) for a
+        roughness map."""
         return self._tex[slot]
 
     def mesh_pos(self, name: str) -> torch.Tensor:

@@ -66,7 +66,7 @@ class EpsmBsdf(C.Structure):
 
 
 class EpsmTexture(C.Structure):
-    _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("nearest", C.c_uint32), ("pad", C.c_uint32)]
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("nearest", C.c_uint32), ("channels", C.c_uint32)]
 
 
 class EpsmEmitter(C.Structure):
@@ -604,6 +604,43 @@ def _bitmap_texture(val: dict, base_dir: str) -> dict:
     return {"bitmap": np.ascontiguousarray(a[:, :, :3]), "nearest": 1 if ft == "nearest" else 0}
 
 
+def _alpha_bitmap_values(a, what: str) -> np.ndarray:
+    """(H, W) float32 texels of a roughness map from what the user gave; refuses what a roughness cannot be."""
+    a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim == 3:
+        raise ValueError(f"{what}: a roughness map has ONE channel, (H, W); the array is {a.shape} -- Mitsuba would take the "
+                         "luminance of an RGB bitmap here: convert it and give that one channel")
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError(f"{what}: the array must be (H, W)")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: a roughness map must be finite everywhere (it holds NaN or inf)")
+    if float(a.min()) <= 0:
+        raise ValueError(f"{what}: every texel of a roughness map must be > 0 (the smallest is {float(a.min())!r}: the microfacet "
+                         "distribution divides by alpha)")
+    return np.array(a, dtype=np.float32, order="C", copy=True)         # (the scene's own: on the CPU the texel buffer aliases it)
+
+
+def _alpha_bitmap_texture(val: dict, base_dir: str) -> dict:
+    """The ``bitmap`` a ``roughconductor``'s ``alpha`` is (roughconductor.cpp:195-198): ``_bitmap_texture``'s rules -- ``bitmap``
+    / ``data`` (an array) or a .npy ``filename``, ``filter_type``, ``wrap_mode`` repeat, no ``to_uv`` -- for ONE channel."""
+    a = val.get("bitmap", val.get("data"))
+    if a is None:
+        fn = val.get("filename")
+        if fn is None or not fn.endswith(".npy"):
+            raise ValueError(f"bitmap: give 'bitmap' (an array) or a .npy 'filename' (got {fn!r}: no image readers here)")
+        a = np.load(os.path.join(base_dir, fn))
+    if val.get("wrap_mode", "repeat") != "repeat":
+        raise ValueError("bitmap: only wrap_mode 'repeat'")
+    if "to_uv" in val:
+        raise ValueError("bitmap: to_uv is not supported (scale the mesh's texture coordinates instead)")
+    ft = val.get("filter_type", "bilinear")
+    if ft not in ("bilinear", "nearest"):
+        raise ValueError("bitmap: filter_type 'bilinear' or 'nearest'")
+    return {"bitmap": _alpha_bitmap_values(a, "roughconductor alpha bitmap"), "nearest": 1 if ft == "nearest" else 0}
+
+
 def _envmap_bitmap(val: dict, base_dir: str) -> np.ndarray:
     """(H, W, 3) float32 radiance of an ``envmap`` emitter, ``scale`` applied: ``bitmap`` / ``data`` (an array, as
     ``mi.Bitmap(array)`` would carry it) or ``filename`` (.npy -- there is no OpenEXR reader here; the reference's experiments
@@ -730,7 +767,7 @@ class Scene:
         self.alpha_slots: Dict[int, int] = {}
         self.material_slots: Dict[int, int] = {}   # conductors attached for the material adjoint (attach_conductor): BSDF index -> slot
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
-        self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoint: ("bsdf" | "envmap", index)
+        self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoints: ("bsdf" | "envmap" | "alpha", index)
         self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
         self.sensor_attached = self.sensor_rotation = False     # attach_sensor
         self._rigid_tables = {}                    # (ranges, pivots) -> their device tensors
@@ -793,7 +830,11 @@ class Scene:
                 if t == "roughconductor":
                     o["distr"] = {"beckmann": 0, "ggx": 1}[b.get("distribution", "beckmann")]
                     a = b.get("alpha", 0.1)
-                    o["alpha"] = float(a["value"] if isinstance(a, dict) else a)
+                    if isinstance(a, dict) and a.get("type") == "bitmap":
+                        o["alpha_texture"] = _alpha_bitmap_texture(a, base_dir)
+                        o["alpha"] = float(o["alpha_texture"]["bitmap"].mean())          # (a stand-in: the tracer looks the map up)
+                    else:
+                        o["alpha"] = float(a["value"] if isinstance(a, dict) else a)
                     o["sample_visible"] = 1 if b.get("sample_visible", True) else 0
             elif t == "dielectric":
                 o["int_ior"], o["ext_ior"] = _ior(b.get("int_ior"), 1.5046), _ior(b.get("ext_ior"), 1.000277)
@@ -1021,8 +1062,16 @@ class Scene:
         """Any mesh whose vertex positions / normals receive gradients?"""
         return any(m.pos_attached or m.nrm_attached for m in self.meshes)
 
-    def attach_alpha(self, bsdf_name: str) -> int:
+    def _refuse_alpha_map(self, what: str, bsdf_name: str) -> int:
+        """The index of BSDF ``bsdf_name``; a roughness MAP has no scalar to attach or set."""
         i = self.bsdf_names.index(bsdf_name)
+        if "alpha_texture" in self.bsdf_desc[i]:
+            raise ValueError(f"{what}: the roughness of {bsdf_name!r} is a bitmap -- attach_texture('{bsdf_name}.alpha.data') "
+                             "attaches it, set_texture sets it")
+        return i
+
+    def attach_alpha(self, bsdf_name: str) -> int:
+        i = self._refuse_alpha_map("attach_alpha", bsdf_name)
         self.alpha_slots.setdefault(i, len(self.alpha_slots))
         self._upload()
         return self.alpha_slots[i]
@@ -1105,14 +1154,27 @@ class Scene:
     def attach_texture(self, name) -> int:
         """``dr.enable_grad(params['<bsdf>.reflectance.data'])`` -- the ``bitmap`` reflectance of a diffuse BSDF, by BSDF name -- or
         ``dr.enable_grad(params['<emitter>.data'])`` -- the envmap's bitmap, by emitter name or index -- for the texel adjoint
-        (``epsm_trace_paths_texture_backward``; PRBIntegrator).  Returns the slot: ``ParamGrads.texture(slot)``."""
+        (``epsm_trace_paths_texture_backward``; PRBIntegrator) -- or ``dr.enable_grad(params['<bsdf>.alpha.data'])``, the
+        1-channel ``bitmap`` a roughconductor's ``alpha`` is, by that full name, for the roughness-map adjoint
+        (``epsm_trace_paths_alpha_texture_backward``).  Returns the slot: ``ParamGrads.texture(slot)``, (H, W, 3) -- (H, W) for a
+        roughness map.  The slots of all three kinds share one numbering and one limit of 8."""
         key = None
-        if isinstance(name, str):
+        if isinstance(name, str) and name.endswith(".alpha.data") and name[: -len(".alpha.data")] in self.bsdf_names:
+            bname = name[: -len(".alpha.data")]
+            i = self.bsdf_names.index(bname)
+            if self.bsdf_desc[i]["type"] != BSDF_TYPES["roughconductor"]:
+                raise ValueError(f"attach_texture: {bname!r} is not a roughconductor (only its alpha may be a bitmap here)")
+            if "alpha_texture" not in self.bsdf_desc[i]:
+                raise ValueError(f"attach_texture: the roughness of {bname!r} is not a bitmap (attach_alpha takes a scalar one)")
+            key = ("alpha", i)
+        elif isinstance(name, str):
             for suffix in (".reflectance.data", ".data"):
                 if name.endswith(suffix) and name[: -len(suffix)] in self.bsdf_names + self.emitter_names:
                     name = name[: -len(suffix)]
                     break
-        if isinstance(name, str) and name in self.bsdf_names:
+        if key is not None:
+            pass
+        elif isinstance(name, str) and name in self.bsdf_names:
             i = self.bsdf_names.index(name)
             if self.bsdf_desc[i]["type"] != 0:
                 raise ValueError(f"attach_texture: {name!r} is not a diffuse BSDF (only a diffuse reflectance may be a bitmap here)")
@@ -1137,19 +1199,25 @@ class Scene:
         return self.texture_slots.index(key)
 
     def texture_shapes(self):
-        """(H, W) of every attached texture slot, slot order (ParamGrads' ``tex_shapes``)."""
-        return [self._texture_shape(k)[:2] for k in range(len(self.texture_slots))]
+        """(H, W) of every attached texture slot -- (H, W, 1) of a roughness-map slot -- slot order (ParamGrads' ``tex_shapes``)."""
+        return [self._texture_shape(k)[:2] + ((1,) if self.texture_slots[k][0] == "alpha" else ())
+                for k in range(len(self.texture_slots))]
 
     def _texture_shape(self, slot: int):
+        """The shape of the slot's buffers: (H, W, 3), or (H, W) for a roughness map."""
         kind, i = self.texture_slots[slot]
-        a = self.bsdf_desc[i]["texture"]["bitmap"] if kind == "bsdf" else self.emitter_desc[i]["bitmap"]
+        a = (self.bsdf_desc[i]["texture"]["bitmap"] if kind == "bsdf" else self.bsdf_desc[i]["alpha_texture"]["bitmap"] if kind == "alpha"
+             else self.emitter_desc[i]["bitmap"])
         return tuple(int(x) for x in a.shape)
 
     def texture_values(self, slot: int) -> torch.Tensor:
-        """(H, W, 3) current bitmap of texture slot ``slot`` -- an envmap's as the user gave it, before its ``scale``."""
+        """(H, W, 3) current bitmap of texture slot ``slot`` -- an envmap's as the user gave it, before its ``scale``; (H, W) for
+        a roughness map."""
         kind, i = self.texture_slots[slot]
         if kind == "bsdf":
             a = self.bsdf_desc[i]["texture"]["bitmap"]
+        elif kind == "alpha":
+            a = self.bsdf_desc[i]["alpha_texture"]["bitmap"]
         else:
             e = self.emitter_desc[i]
             a = e["bitmap"] / np.float32(e.get("scale", 1.0))
@@ -1165,6 +1233,16 @@ class Scene:
         device (same shape only); for the envmap its sampling tables are rebuilt too -- ``environment_tables`` (host tables) or
         ``epsm_environment_tables`` (``scene_tables="device"``)."""
         kind, i = self.texture_slots[slot]
+        if kind == "alpha":                                    # (H, W), every texel > 0 and finite, as from_dict asks
+            a = _alpha_bitmap_values(array, "set_texture")
+            if a.shape != self._texture_shape(slot):
+                raise ValueError(f"set_texture: shape {a.shape} is not the slot's {self._texture_shape(slot)}")
+            b = self.bsdf_desc[i]
+            b["alpha_texture"]["bitmap"] = a
+            b["alpha"] = float(a.mean())                        # (the stand-in of from_dict)
+            self._tex_buf[b["texture_index"]][0].copy_(torch.from_numpy(a).to(self.device))
+            self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
+            return
         a = np.asarray(array.detach().cpu().numpy() if torch.is_tensor(array) else array, dtype=np.float32)
         if a.ndim == 2:
             a = np.repeat(a[:, :, None], 3, axis=2)
@@ -1191,7 +1269,7 @@ class Scene:
 
     def set_alpha(self, bsdf_name: str, alpha: float):
         """``params['<bsdf>.alpha.value'] = alpha; params.update()``: only the BSDF table is rewritten (in place)."""
-        self.bsdf_desc[self.bsdf_names.index(bsdf_name)]["alpha"] = float(alpha)
+        self.bsdf_desc[self._refuse_alpha_map("set_alpha", bsdf_name)]["alpha"] = float(alpha)
         self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
 
     def _bsdf_structs(self):
@@ -1372,9 +1450,13 @@ class Scene:
             if "texture" in b:
                 b["texture_index"] = len(self._tex_buf)
                 self._tex_buf.append((f32(b["texture"]["bitmap"]), b["texture"]["nearest"]))
+            elif "alpha_texture" in b:                         # a roughness map: (H, W), EpsmTexture.channels = 1
+                b["texture_index"] = len(self._tex_buf)
+                self._tex_buf.append((f32(b["alpha_texture"]["bitmap"]), b["alpha_texture"]["nearest"]))
         tx = (EpsmTexture * max(1, len(self._tex_buf)))()
         for i, (t_, nearest) in enumerate(self._tex_buf):
             tx[i].texels, tx[i].height, tx[i].width, tx[i].nearest = t_.data_ptr(), int(t_.shape[0]), int(t_.shape[1]), int(nearest)
+            tx[i].channels = 1 if t_.dim() == 2 else 0          # (0: RGB, what every table held before there were roughness maps)
         bs = self._bsdf_structs()
         em = (EpsmEmitter * max(1, len(self.emitter_desc)))()
         for i, e in enumerate(self.emitter_desc):
@@ -1525,18 +1607,50 @@ class Scene:
         self._replay("epsm_trace_paths_color", sensor_index, seed, spp, max_depth, lo, hi, film_pos, radiance, valid, sums, int(max(Cn, 1)))
         return film_pos, radiance, sums[:, :Cn]
 
-    def _texture_pointers(self, bufs):
-        """The (n_textures) pointer array and the envmap pointer of the texture entry points for per-slot (H, W, 3) buffers."""
+    def _texture_pointers(self, bufs, alpha: bool = False):
+        """The (n_textures) pointer array and the envmap pointer of the texture entry points for per-slot buffers (one per slot of
+        ``texture_slots``, shaped like ``_texture_shape``): the RGB slots' (H, W, 3) buffers, or with ``alpha`` the roughness
+        maps' (H, W) ones -- each entry point is handed the buffers of its own kind only."""
         n_tex = len(getattr(self, "_tex_buf", []))
         arr, env = (C.c_void_p * max(1, n_tex))(), None
+        assert len(bufs) == len(self.texture_slots)
         for (kind, i), t_ in zip(self.texture_slots, bufs):
             assert t_.is_contiguous() and t_.dtype == torch.float32 and t_.device.type == self.device.type
             assert tuple(t_.shape) == self._texture_shape(self.texture_slots.index((kind, i)))
-            if kind == "bsdf":
+            if (kind == "alpha") != alpha:
+                continue
+            if kind in ("bsdf", "alpha"):
                 arr[self.bsdf_desc[i]["texture_index"]] = t_.data_ptr()
             else:
                 env = C.c_void_p(t_.data_ptr())
         return C.cast(arr, C.c_void_p), env
+
+    def has_alpha_map(self) -> bool:
+        """Any roughconductor whose alpha is a bitmap?"""
+        return any("alpha_texture" in b for b in self.bsdf_desc)
+
+    def alpha_map_slots(self):
+        """The texture slots that are roughness maps."""
+        return [k for k, (kind, _) in enumerate(self.texture_slots) if kind == "alpha"]
+
+    def trace_alpha_texture_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance,
+                                     adj_radiance, grads):
+        """``epsm_trace_paths_alpha_texture_backward``: ACCUMULATES d loss / d texel of the attached roughness maps over paths
+        [lo, hi) into ``grads`` -- one buffer per texture slot, of which the roughness maps' (H, W) ones are written -- given the
+        radiance of the primal pass (``trace_color`` with the same seed) and its adjoint."""
+        for t_ in (radiance, adj_radiance):
+            self._rows(t_, hi - lo, 3)
+        arr, _ = self._texture_pointers(grads, alpha=True)
+        self._replay("epsm_trace_paths_alpha_texture_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, arr)
+
+    def trace_alpha_texture_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangents):
+        """``epsm_trace_paths_alpha_texture_forward``: the transpose of ``trace_alpha_texture_backward`` -- for one tangent per
+        texture slot (the roughness maps' (H, W) ones are read) returns d radiance (n, 3) of paths [lo, hi)."""
+        self._rows(radiance, hi - lo, 3)
+        arr, _ = self._texture_pointers(tangents, alpha=True)
+        d_radiance = torch.empty((hi - lo, 3), device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_alpha_texture_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, arr, d_radiance)
+        return d_radiance
 
     def trace_texture_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                                grads):

@@ -115,18 +115,23 @@ typedef struct EpsmBsdf {
     int32_t alpha_slot;              /* slot of this BSDF's alpha in grad_alpha, -1 = not optimised */
     int32_t color_slot;              /* diffuse: slot of `reflectance` in the colour adjoint of epsm_trace_paths_color,
                                         -1 = not optimised */
-    int32_t texture;                 /* diffuse: index into EpsmScene.textures of the `bitmap` its reflectance is, -1 = `reflectance` */
+    int32_t texture;                 /* diffuse: index into EpsmScene.textures of the `bitmap` its reflectance is (a texture whose
+                                        channels are 0 or 3), -1 = `reflectance`.  roughconductor: index of the 1-channel `bitmap`
+                                        its alpha is (channels = 1), -1 = `alpha`; such a BSDF has alpha_slot = -1.  A texture of the
+                                        other kind is ignored, never read through; no table written so far sets this word on
+                                        anything but a diffuse BSDF */
     uint32_t material;               /* conductor / roughconductor: 0 = eta, k, specular_reflectance not optimised, s + 1 = material
                                         slot s of epsm_trace_paths_material_backward (the word that was padding: 0 in every table) */
 } EpsmBsdf;
 
-/* A `bitmap` texture (src/textures/bitmap.cpp): linear RGB texels, looked up at si.uv as there -- uv * (width, height) - 0.5,
- * bilinear between the four texels around it (or the nearest one), indices wrapped (`repeat`). */
+/* A `bitmap` texture (src/textures/bitmap.cpp): linear RGB texels -- or scalar ones, the roughness map of a roughconductor
+ * (roughconductor.cpp:195-198) -- looked up at si.uv as there: uv * (width, height) - 0.5, bilinear between the four texels
+ * around it (or the nearest one), indices wrapped (`repeat`). */
 typedef struct EpsmTexture {
-    const float *texels;             /* (height, width, 3), row 0 at v = 0 */
+    const float *texels;             /* (height, width, 3), or (height, width) when channels = 1; row 0 at v = 0 */
     int32_t width, height;
     uint32_t nearest;                /* filter_type: 0 bilinear, 1 nearest */
-    uint32_t pad;
+    uint32_t channels;               /* 0 or 3: RGB texels; 1: scalar texels (the word that was padding: 0 in every table) */
 } EpsmTexture;
 
 typedef struct EpsmEmitter {
@@ -379,6 +384,37 @@ int epsm_trace_paths_texture_forward(const EpsmScene *scene, const EpsmSensor *s
                                      int64_t path_offset, int64_t N,
                                      const float *radiance, const float *const *tan_tex, const float *tan_env,
                                      float *d_radiance, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_alpha_texture_backward -- the ROUGHNESS-MAP adjoint of `prb`: the rule of epsm_trace_paths_bsdf_backward
+ *   (below) for a `roughconductor` whose alpha is a 1-channel `bitmap` (EpsmBsdf.texture = t, EpsmScene.textures[t].channels
+ *   = 1), scattered like epsm_trace_paths_texture_backward.  Paths [path_offset, path_offset + N) are replayed under the primal
+ *   seed as epsm_trace_paths_color traced them; at an active bounce on such a BSDF, alpha = the map's value at the vertex's uv,
+ *     - the sampled direction gives L_ind  d f / d alpha / (weight pdf) per channel (a channel with weight pdf = 0: nothing),
+ *     - the emitter sample gives Lr_dir  d ln f / d alpha (nothing when occluded),
+ *   and adj . (their sum) x w is ACCUMULATED into each texel of the lookup's footprint (4 bilinear, 1 nearest; wrap as the
+ *   lookup): float atomics, after a merge over the lanes of a wave that share a footprint.  Sampling, Russian roulette and the
+ *   MIS weights are detached.
+ *     radiance      (N,3) L of every path from the primal pass (epsm_trace_paths_color with the same seed / spp / depths)
+ *     adj_radiance  (N,3) d loss / d L
+ *     grad_tex      NULL or an array of n_textures HOST pointers; entry t NULL = texture t not attached, otherwise (height_t,
+ *                   width_t) f32, added to.  An entry for a texture that is not 1-channel is never touched.  At most
+ *                   EPSM_MAX_TEXTURE_GRADS entries non-NULL (EPSM_EINVAL).  With no entry the call does nothing
+ *   One launch.  No host synchronisation.  Float atomics: the bits depend on the order of the adds.
+ * epsm_trace_paths_alpha_texture_forward -- its exact transpose: the same replay GATHERS the tangents tan_tex (same layout,
+ *   read only where attached) and WRITES d_radiance (N,3), so that sum(adj_radiance * d_radiance) = sum(grad_tex . tan_tex).
+ *   No atomics.
+ * ------------------------------------------------------------------------- */
+int epsm_trace_paths_alpha_texture_backward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                            uint32_t seed, int spp, int max_depth, int rr_depth,
+                                            int64_t path_offset, int64_t N,
+                                            const float *radiance, const float *adj_radiance,
+                                            float *const *grad_tex, void *stream);
+int epsm_trace_paths_alpha_texture_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                           uint32_t seed, int spp, int max_depth, int rr_depth,
+                                           int64_t path_offset, int64_t N,
+                                           const float *radiance, const float *const *tan_tex,
+                                           float *d_radiance, void *stream);
 
 /* ---------------------------------------------------------------------------
  * epsm_trace_paths_bsdf_backward -- the ROUGHNESS adjoint of `prb` (prb.py:145-158, 209-226; sampling, Russian roulette and the
