@@ -79,6 +79,36 @@ EPSM_HD void probe_row(int what, const float *in, float *out, const EpsmBsdf *bs
     }
 }
 
+// ---- epsm_probe_rays (include/epsm_trace.h): one row of caller-given rays in, one hit out.  The traversal itself is the
+// tracer's (intersect, packet_intersect) on the stack the caller of these helpers hands over; nothing of it is restated here.
+EPSM_HD bool probe_ray_load(const float *row, Ray &r) {                  // -> the row carries a ray
+    r.o = f3(row[0], row[1], row[2]); r.d = f3(row[3], row[4], row[5]); r.maxt = row[6];
+    return row[7] != 0.f;
+}
+EPSM_HD TriHit probe_ray_miss(const Ray &r) { TriHit th; th.hit = false; th.tri = 0; th.t = r.maxt; th.u = th.v = 0.f; return th; }
+EPSM_HD void probe_ray_store(uint32_t *out, const TriHit &th) {
+    out[0] = th.hit ? th.tri : 0xffffffffu; out[1] = f2u(th.t); out[2] = f2u(th.u); out[3] = f2u(th.v);
+}
+template <bool ANY_HIT>
+EPSM_HD void probe_ray_row(const EpsmScene &S, const float *row, uint32_t *out, const BvhStack &st) {
+    Ray r;
+    const bool on = probe_ray_load(row, r);
+    probe_ray_store(out, on ? intersect<ANY_HIT>(S, r, st) : probe_ray_miss(r));
+}
+EPSM_HD bool probe_rays_wavefront_form(int form) { return form == EPSM_RAYS_WAVEFRONT || form == EPSM_RAYS_WAVEFRONT_ANY; }
+// what every build of epsm_probe_rays refuses before it touches anything (NULL: fine); `need` = the form's workspace bytes
+EPSM_HD const char *probe_rays_refusal(const EpsmScene *scene, int form, int64_t n, const float *rays, const uint32_t *out,
+                                       const void *workspace, size_t workspace_bytes, size_t need) {
+    if (form < 0 || form >= EPSM_RAYS_FORM_COUNT) return "epsm_probe_rays: unknown form";
+    if (n < 0) return "epsm_probe_rays: n < 0";
+    if (n == 0) return nullptr;
+    if (!scene || !rays || !out) return "epsm_probe_rays: NULL argument";
+    if (scene->n_nodes < 0 || (scene->n_nodes > 0 && (!scene->bvh || !scene->prim_index || !scene->tri_verts)))
+        return "epsm_probe_rays: the scene has nodes but no bvh / prim_index / tri_verts";
+    if (need > 0 && (!workspace || workspace_bytes < need)) return "epsm_probe_rays: workspace NULL or too small";
+    return nullptr;
+}
+
 EPSM_HD bool probe_needs_bsdf(int what) {
     return what == EPSM_PROBE_MICROFACET || what == EPSM_PROBE_MICROFACET_SAMPLE || what == EPSM_PROBE_BSDF_SAMPLE || what == EPSM_PROBE_BSDF_EVAL ||
            what == EPSM_PROBE_MICROFACET_DALPHA || what == EPSM_PROBE_BSDF_DALPHA;

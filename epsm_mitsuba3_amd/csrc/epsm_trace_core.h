@@ -170,8 +170,12 @@ struct Traversal {
 EPSM_HD void trav_begin(Traversal &T, const EpsmScene &S, const Ray &r) {
     T.r = r;
     T.best.hit = false; T.best.tri = 0; T.best.t = r.maxt; T.best.u = T.best.v = 0.f;
-    // finite reciprocals: a ray parallel to a slab sees its planes at +-1e18 x distance (or at 0 when it lies IN one,
-    // which counts as inside) instead of +-inf / NaN
+    // finite reciprocals: a ray parallel to a slab sees its planes at +-1e18 x distance instead of +-inf / NaN.  A ray that lies
+    // IN a plane (o == lo bit for bit) does not see it at 0: fmaf(lo, inv, -(o * inv)) returns the rounding residue of the
+    // product, up to 2^-24 |o| 1e18 ~ 6e10 |o| of either sign, and with the wrong sign the box is missed.  No hit is lost to it:
+    // a plane one ulp of o away already lies at 1.2e11 |o|, twice the residue, on its proper side, and a box is wider than its
+    // triangles by the refit's padding (1e-6 (1 + |lo|)), so a ray IN a box's plane touches none of the triangles inside it
+    // (the in-plane axis rays of tests/_ray_query.py)
     T.inv_d = f3(fminf(fmaxf(1.f / r.d.x, -1e18f), 1e18f), fminf(fmaxf(1.f / r.d.y, -1e18f), 1e18f), fminf(fmaxf(1.f / r.d.z, -1e18f), 1e18f));
     T.noid = f3(-r.o.x * T.inv_d.x, -r.o.y * T.inv_d.y, -r.o.z * T.inv_d.z);
     T.best_e = -1;

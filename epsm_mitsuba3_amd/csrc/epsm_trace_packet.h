@@ -24,7 +24,11 @@
 
 namespace epsm {
 
-constexpr int kPacketStack = 64;            // entries per wave (depth <= 16, three pushes per level: never reached)
+// entries per wave.  The wave descends ONE chain of nodes, whatever its lanes want: a node pushes at most three references (the
+// union over the lanes is still only its four children) and the chain is at most kMaxWideDepth = 16 nodes long, so at most
+// 3 x 16 = 48 <= 64 entries are ever in use and the `sp < kPacketStack` below never drops a push.  What holds it: the packets of
+// 64 deep rays and of incoherent lanes on the geometric chain, tests/test_gpu_ray_query.py.
+constexpr int kPacketStack = 64;
 constexpr int kPacketMaxSteps = 1 << 20;    // termination guard (never reached)
 
 typedef const __attribute__((address_space(4))) float *ConstF;

@@ -540,6 +540,29 @@ enum { EPSM_PROBE_TEA = 0, EPSM_PROBE_PCG32 = 1, EPSM_PROBE_SAMPLER = 2, EPSM_PR
 #define EPSM_PROBE_OUT 16
 int epsm_probe(int what, int64_t n, const float *in, float *out, const void *cfg, void *stream);
 
+/* epsm_probe_rays -- the ray-query counterpart of epsm_probe: the tracer's own BVH traversal (csrc/epsm_trace_core.h intersect,
+ * csrc/epsm_trace_packet.h packet_intersect) on n rays the CALLER gives, with the stack forms the tracer's kernels use.  It exists so
+ * that closest-hit and any-hit answers can be checked ray by ray on rays no sensor produces (tests/test_gpu_ray_query.py).
+ *   form  EPSM_RAYS_LANE / _LANE_ANY            intersect<false> / intersect<true>, one ray per lane of a 128-lane workgroup on the
+ *                                               one-launch kernels' stack: 32 entries per lane in LDS, the rest in a private array
+ *         EPSM_RAYS_WAVEFRONT / _WAVEFRONT_ANY  the same on the wavefront kernels' stack: 16 entries per lane in LDS, the rest in
+ *                                               `workspace`, entry k of ray i at word (k - 16) n + i
+ *         EPSM_RAYS_PACKET                      packet_intersect: rows 64 w .. 64 w + 63 are the lanes of one wave; a lane carries a
+ *                                               ray when its row exists and its mask is set; every lane of the wave calls it
+ *   scene      only bvh, n_nodes, prim_index and tri_verts are read (n_nodes = 0: every ray misses, nothing is read)
+ *   rays       (n,8) f32, device: o (3), d (3), maxt, mask (0 = the row carries no ray: it reports a miss)
+ *   out        (n,4) u32, device: triangle id or 0xffffffff, then t, u, v as bits (maxt, 0, 0 for a miss)
+ *   workspace  device, >= epsm_probe_rays_workspace_bytes(form, n); scratch.  May be NULL where that is 0
+ * EPSM_EINVAL, before any launch: an unknown form, n < 0, a NULL scene / rays / out with n > 0, n_nodes > 0 with a NULL table, a
+ * workspace that is NULL or too small.  n = 0 returns EPSM_OK.  Not on any hot path. */
+enum { EPSM_RAYS_LANE = 0, EPSM_RAYS_LANE_ANY = 1, EPSM_RAYS_WAVEFRONT = 2, EPSM_RAYS_WAVEFRONT_ANY = 3, EPSM_RAYS_PACKET = 4,
+       EPSM_RAYS_FORM_COUNT = 5 };
+#define EPSM_RAYS_IN 8
+#define EPSM_RAYS_OUT 4
+size_t epsm_probe_rays_workspace_bytes(int form, int64_t n);
+int epsm_probe_rays(const EpsmScene *scene, int form, int64_t n, const float *rays, uint32_t *out,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------
  * epsm_bvh_build -- the four-wide BVH of T triangles on the device (csrc/epsm_trace_bvh.hip).  Replaces the native scene
  *   construction of the reference (src/render/scene.cpp:66-74, scene_native.inl:10-36: the acceleration structure built

@@ -89,3 +89,31 @@ def furnace_with_ball(bsdf, wall_reflectance=0.0, res=8, spp=64, smooth=False, d
     d["cam"] = sensor([0.2, -0.1, 0.3], centre, up=(0, 0, 1), fov=70, res=res, spp=spp)
     d["ball"] = {"type": "mesh", "vertices": v * 0.25 + centre, "faces": f, "face_normals": not smooth, "bsdf": bsdf}
     return S.Scene.from_dict(d, device=device)
+
+
+def chain_scene(res=16, spp=8, device="cpu", bvh_builder="host"):
+    """The whole tracer on the tree whose walk fills the traversal stack: the geometric chain of tests/_ray_query.py (1 500
+    diffuse triangles, scaled by 2^36) under an area light, seen from its corner (0, 0, 0) along (3, 2, 1) through 2 degrees --
+    the chain's own angular size.  The near plane lies at 2^-30, far in front of the smallest triangle (2^-24)."""
+    import _ray_query as Q
+    pos, tri = Q.geometry("chain")
+    size = Q.CHAIN_SCALE
+    lv, lf = quad(2.0 * size, 2.0 * size, up=False)
+    d = {"type": "scene",
+         "cam": sensor([0.0, 0.0, 0.0], [3.0, 2.0, 1.0], up=(0, 0, 1), fov=2, res=res, spp=spp, near=2.0 ** -30, far=2.0 ** 40),
+         "chain": {"type": "mesh", "vertices": np.array(pos), "faces": np.array(tri), "face_normals": True,
+                   "bsdf": {"type": "twosided", "bsdf": {"type": "diffuse", "reflectance": {"type": "rgb", "value": [0.6, 0.5, 0.4]}}}},
+         "light": {"type": "mesh", "vertices": lv + np.array([1.5 * size, size, 0.0]), "faces": lf, "face_normals": True,
+                   "bsdf": {"type": "diffuse", "reflectance": {"type": "rgb", "value": [0, 0, 0]}},
+                   "emitter": {"type": "area", "radiance": {"type": "rgb", "value": 10.0}}}}
+    return S.Scene.from_dict(d, device=device, bvh_builder=bvh_builder)
+
+
+def primary_stack_depth(scene, trace):
+    """Peak traversal-stack depth of the logged primary rays of `trace` on the scene's tree (tests/_ray_query.py)."""
+    import _ray_query as Q
+    n = trace.ray_o.shape[0]
+    rays = np.empty((n, 8), dtype=np.float32)
+    rays[:, 0:3], rays[:, 3:6] = trace.ray_o.cpu().numpy(), trace.ray_d.cpu().numpy()
+    rays[:, 6], rays[:, 7] = Q.K_INF, 1.0
+    return Q.peak_stack_depth(scene.bvh.nodes.cpu().numpy(), scene.bvh.tri_verts.cpu().numpy(), rays)

@@ -235,3 +235,25 @@ extern "C" int epsm_probe(int what, int64_t n, const float *in, float *out, cons
     for (int64_t i = 0; i < n; ++i) probe_row(what, in + i * EPSM_PROBE_IN, out + i * EPSM_PROBE_OUT, &bsdf, &sensor);
     return 0;
 }
+
+// epsm_probe_rays (include/epsm_trace.h) on host pointers: the tracer's intersect on caller-given rays, on the two stacks the
+// entry points above give a path -- kBvhStack words of its own (epsm_trace_paths), or kWfStackLds words and the rest in the
+// workspace at ovf + i, stride n (epsm_trace_paths_wavefront).  The wave-packet walk is device code: refused here.
+extern "C" size_t epsm_probe_rays_workspace_bytes(int form, int64_t n) {
+    return probe_rays_wavefront_form(form) && n > 0 ? (size_t) n * 4 * kWfStackOvf : 0;
+}
+extern "C" int epsm_probe_rays(const EpsmScene *scene, int form, int64_t n, const float *rays, uint32_t *out, void *workspace,
+                               size_t workspace_bytes, void *) {
+    if (probe_rays_refusal(scene, form, n, rays, out, workspace, workspace_bytes, epsm_probe_rays_workspace_bytes(form, n))) return -22;
+    if (form == EPSM_RAYS_PACKET) return -22;
+    const bool any = form == EPSM_RAYS_LANE_ANY || form == EPSM_RAYS_WAVEFRONT_ANY;
+    WfState W = {};
+    W.stack_ovf = (uint32_t *) workspace; W.N = n;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t stack[kBvhStack];
+        const BvhStack st = probe_rays_wavefront_form(form) ? wf_stack(W, i, stack, 1) : BvhStack{stack, 1};
+        if (any) probe_ray_row<true>(*scene, rays + i * EPSM_RAYS_IN, out + i * EPSM_RAYS_OUT, st);
+        else probe_ray_row<false>(*scene, rays + i * EPSM_RAYS_IN, out + i * EPSM_RAYS_OUT, st);
+    }
+    return 0;
+}

@@ -17,13 +17,9 @@ def _scene(device):
     return sc
 
 
-def test_gpu_records_match_host_build():
-    from _scenes import on_host
-    dev = torch.device("cuda", 0)
-    g, h = _scene(dev), on_host(_scene("cpu"))
-    n = 32 * 32 * 8
-    a = g._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
-    b = h._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
+def _records_match(a, b, unit=1.0):
+    """a: the device's trace, b: the host build's, same arguments.  Positions are compared in units of `unit`, the scene's
+    length scale (a power of two: exact): the absolute 1e-3 below was written for scenes a few units across."""
     assert torch.allclose(a.ray_d.cpu(), b.ray_d, atol=1e-6) and torch.allclose(a.film_pos.cpu(), b.film_pos, atol=1e-5)
     for k in (1, 2, 3):
         ra, rb = a.path_info[k], b.path_info[k]
@@ -31,13 +27,44 @@ def test_gpu_records_match_host_build():
         assert float(same.float().mean()) > 0.995, k           # fma contraction can flip a borderline decision
         for name in ("light", "hf", "eta"):
             x, y = ra[name].cpu()[same], rb[name][same]
+            if name == "light":
+                x, y = x / unit, y / unit
             close = (x - y).abs().reshape(x.shape[0], -1).amax(dim=1) < 1e-3
             assert float(close.float().mean()) > 0.99, (k, name)
-        x, y = ra["points"][3].cpu()[same], rb["points"][3][same]
+        x, y = ra["points"][3].cpu()[same] / unit, rb["points"][3][same] / unit
         assert float(((x - y).abs().amax(dim=1) < 1e-3).float().mean()) > 0.99
     ta, tb = a.scatter_info[0]["tri"].cpu(), b.scatter_info[0]["tri"]
     assert float((ta == tb).float().mean()) > 0.995            # triangle ids
     assert torch.allclose(a.radiance.cpu().mean(0), b.radiance.mean(0), rtol=2e-2)
+
+
+def test_gpu_records_match_host_build():
+    from _scenes import on_host
+    dev = torch.device("cuda", 0)
+    g, h = _scene(dev), on_host(_scene("cpu"))
+    n = 32 * 32 * 8
+    a = g._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
+    b = h._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
+    _records_match(a, b)
+
+
+@pytest.mark.parametrize("tracer", ["mega", "wavefront"])
+def test_gpu_records_match_host_build_on_the_deep_chain(tracer):
+    """The same comparison, same thresholds, on the tree whose walk fills the traversal stack (tests/_scenes.py chain_scene:
+    the primary rays peak at 47 of 48 entries): the device's two stack homes against the host build's one array."""
+    import _ray_query as Q
+    from _scenes import chain_scene, on_host, primary_stack_depth
+    dev = torch.device("cuda", 0)
+    g, h = chain_scene(device=dev), on_host(chain_scene())
+    g.tracer = tracer
+    n = 16 * 16 * 8
+    a = g._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
+    b = h._trace(0, seed=3, spp=8, max_depth=4, K=3, lo=0, hi=n)
+    torch.cuda.synchronize()
+    peak = primary_stack_depth(g, a)
+    assert (peak > 32).sum() >= 64 and peak.max() >= 40
+    assert int((a.path_info[1]["active"] > 0).sum()) > n // 2
+    _records_match(a, b, unit=Q.CHAIN_SCALE)
 
 
 def test_primal_render_and_backward_on_a_scene():
@@ -83,26 +110,9 @@ def test_primal_render_and_backward_on_a_scene():
     assert float((img2 - img).abs().mean()) > 1e-4
 
 
-@pytest.mark.parametrize("tail", [True, False])
-@pytest.mark.parametrize("max_depth,K", [(5, 5), (3, 2)])
-def test_gpu_wavefront_tracer_equals_one_launch(max_depth, K, tail):
-    """epsm_trace_paths_wavefront (queues of live paths, extend / shade / shadow kernels per bounce, ballot +
-    prefix-count compaction) against epsm_trace_paths on the GPU: the same per-path code in another visiting order.
-    The host builds of the two forms agree bit for bit (tests/test_tracer_wavefront_host.py); on the device the
-    compiler may contract a product into an fma in one kernel and not in the other, so a borderline decision
-    (hit / miss at a triangle's edge) may flip on a handful of paths.  ``tail``: with fewer than 2^19 paths alive the
-    bounces >= 1 are ONE launch (wf_tail, csrc/epsm_trace_wavefront.h); EPSM_TRACE_NO_TAIL keeps the three stages."""
-    from test_tracer_wavefront_host import _rich_scene, _all_arrays
-    dev = torch.device("cuda", 0)
-    res, spp = 48, 16
-    sc = _rich_scene(res, spp, point_light=True, occluder=max_depth <= 3, device=dev)
-    sc.wavefront_tail = tail
-    n = res * res * spp
-    sc.tracer = "mega"
-    a = sc._trace(0, seed=5, spp=spp, max_depth=max_depth, K=K, lo=0, hi=n)
-    sc.tracer = "wavefront"
-    b = sc._trace(0, seed=5, spp=spp, max_depth=max_depth, K=K, lo=0, hi=n)
-    torch.cuda.synchronize()
+def _forms_agree(a, b, n, dev):
+    """a: epsm_trace_paths, b: epsm_trace_paths_wavefront, same arguments: fewer than 2e-3 of the paths may differ"""
+    from test_tracer_wavefront_host import _all_arrays
     x, y = _all_arrays(a), _all_arrays(b)
     assert x.keys() == y.keys()
     bad = torch.zeros(n, dtype=torch.bool, device=dev)
@@ -122,6 +132,51 @@ def test_gpu_wavefront_tracer_equals_one_launch(max_depth, K, tail):
             assert not bool(differ.any()), name
         bad |= differ
     assert float(bad.float().mean()) < 2e-3, f"{int(bad.sum())} of {n} paths differ"
+
+
+@pytest.mark.parametrize("lo,hi", [(0, 16 * 16 * 8), (100, 1001)])
+@pytest.mark.parametrize("tail", [True, False])
+def test_gpu_wavefront_tracer_equals_one_launch_on_the_deep_chain(tail, lo, hi):
+    """The same comparison, same threshold, on the tree whose walk fills the traversal stack (tests/_scenes.py chain_scene): the
+    one-launch kernel keeps 32 entries per lane in LDS and 16 in a private array, the wavefront kernels 16 in LDS and 32 in the
+    workspace at stack_ovf + i, stride N, i the TILE-LOCAL path -- the whole wavefront and a tile [100, 1 001)."""
+    from _scenes import chain_scene, primary_stack_depth
+    dev = torch.device("cuda", 0)
+    sc = chain_scene(device=dev)
+    sc.wavefront_tail = tail
+    sc.tracer = "mega"
+    a = sc._trace(0, seed=5, spp=8, max_depth=4, K=3, lo=lo, hi=hi)
+    sc.tracer = "wavefront"
+    b = sc._trace(0, seed=5, spp=8, max_depth=4, K=3, lo=lo, hi=hi)
+    torch.cuda.synchronize()
+    peak = primary_stack_depth(sc, a)
+    assert (peak > 32).sum() >= 64 and peak.max() >= 40
+    assert int((a.path_info[1]["active"] > 0).sum()) > (hi - lo) // 2
+    _forms_agree(a, b, hi - lo, dev)
+    assert torch.allclose(a.radiance.mean(0), b.radiance.mean(0), rtol=1e-3)
+
+
+@pytest.mark.parametrize("tail", [True, False])
+@pytest.mark.parametrize("max_depth,K", [(5, 5), (3, 2)])
+def test_gpu_wavefront_tracer_equals_one_launch(max_depth, K, tail):
+    """epsm_trace_paths_wavefront (queues of live paths, extend / shade / shadow kernels per bounce, ballot +
+    prefix-count compaction) against epsm_trace_paths on the GPU: the same per-path code in another visiting order.
+    The host builds of the two forms agree bit for bit (tests/test_tracer_wavefront_host.py); on the device the
+    compiler may contract a product into an fma in one kernel and not in the other, so a borderline decision
+    (hit / miss at a triangle's edge) may flip on a handful of paths.  ``tail``: with fewer than 2^19 paths alive the
+    bounces >= 1 are ONE launch (wf_tail, csrc/epsm_trace_wavefront.h); EPSM_TRACE_NO_TAIL keeps the three stages."""
+    from test_tracer_wavefront_host import _rich_scene
+    dev = torch.device("cuda", 0)
+    res, spp = 48, 16
+    sc = _rich_scene(res, spp, point_light=True, occluder=max_depth <= 3, device=dev)
+    sc.wavefront_tail = tail
+    n = res * res * spp
+    sc.tracer = "mega"
+    a = sc._trace(0, seed=5, spp=spp, max_depth=max_depth, K=K, lo=0, hi=n)
+    sc.tracer = "wavefront"
+    b = sc._trace(0, seed=5, spp=spp, max_depth=max_depth, K=K, lo=0, hi=n)
+    torch.cuda.synchronize()
+    _forms_agree(a, b, n, dev)
     v1, v2 = a.path_info[1], a.path_info[2]
     assert 0 < int((v2["active"] > 0).sum()) < int((v1["active"] > 0).sum())
     if max_depth <= 3:

@@ -257,3 +257,22 @@ def test_packed_record_words_are_where_the_header_says():
         if s.get("aux") is not None:
             assert torch.equal(iw[live, k, 29:32], s["aux"][live][:, 1:4].to(torch.int32))
     assert seen > n
+
+
+@pytest.mark.parametrize("lo,hi", [(0, 16 * 16 * 8), (100, 1001)])
+def test_wavefront_equals_one_launch_on_the_deep_chain(lo, hi):
+    """The tree whose walk fills the traversal stack (tests/_scenes.py chain_scene: peak 47 of 48 entries): the one-launch form
+    keeps all 48 in one array, the wavefront form 16 and the rest in the workspace at stack_ovf + i, stride N, with i the
+    TILE-LOCAL path -- whole wavefront and a tile [100, 1 001).  Bit for bit."""
+    from _scenes import chain_scene, primary_stack_depth
+    sc = on_host(chain_scene())
+    sc.tracer = "mega"
+    a = sc._trace(0, seed=5, spp=8, max_depth=4, K=3, lo=lo, hi=hi)
+    sc.tracer = "wavefront"
+    b = sc._trace(0, seed=5, spp=8, max_depth=4, K=3, lo=lo, hi=hi)
+    _same(a, b)
+    peak = primary_stack_depth(sc, a)
+    hit1, hit2 = int((a.path_info[1]["active"] > 0).sum()), int((a.path_info[2]["active"] > 0).sum())
+    print("chain scene: primary rays' peak stack depth", int(peak.max()), "above 32:", int((peak > 32).sum()), "first / second hits", hit1, hit2)
+    assert (peak > 32).sum() >= 64 and peak.max() >= 40                  # the overflow of both forms is in use
+    assert hit1 > (hi - lo) // 4 and hit2 > 0
