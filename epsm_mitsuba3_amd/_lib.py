@@ -223,34 +223,20 @@ def declare_tracer(lib):
                                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                                          C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                          C.c_void_p]
-    if hasattr(lib, "epsm_trace_paths_texture_backward"):  # (the HIP library; of the host builds, tests/host_harness/trace_tex_host.cpp)
-        tex_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
-        lib.epsm_trace_paths_texture_backward.restype = C.c_int
-        lib.epsm_trace_paths_texture_backward.argtypes = tex_args + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.epsm_trace_paths_texture_forward.restype = C.c_int
-        lib.epsm_trace_paths_texture_forward.argtypes = tex_args + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "epsm_trace_paths_bsdf_backward"):     # (the HIP library; of the host builds, tests/host_harness/trace_bsdf_host.cpp)
-        bsdf_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
-        lib.epsm_trace_bsdf_workspace_bytes.restype = C.c_size_t
-        lib.epsm_trace_bsdf_workspace_bytes.argtypes = [C.c_int64]
-        lib.epsm_trace_paths_bsdf_backward.restype = C.c_int
-        lib.epsm_trace_paths_bsdf_backward.argtypes = bsdf_args + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.epsm_trace_paths_bsdf_forward.restype = C.c_int
-        lib.epsm_trace_paths_bsdf_forward.argtypes = bsdf_args + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "epsm_trace_paths_material_backward"):  # (the HIP library; of the host builds, tests/host_harness/trace_material_host.cpp)
-        mat_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
-        lib.epsm_trace_material_workspace_bytes.restype = C.c_size_t
-        lib.epsm_trace_material_workspace_bytes.argtypes = [C.c_int64]
-        lib.epsm_trace_paths_material_backward.restype = C.c_int
-        lib.epsm_trace_paths_material_backward.argtypes = mat_args + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.epsm_trace_paths_material_forward.restype = C.c_int
-        lib.epsm_trace_paths_material_forward.argtypes = mat_args + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "epsm_trace_paths_alpha_texture_backward"):   # (the HIP library; of the host builds, tests/host_harness/trace_alphamap_host.cpp)
-        am_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
-        lib.epsm_trace_paths_alpha_texture_backward.restype = C.c_int
-        lib.epsm_trace_paths_alpha_texture_backward.argtypes = am_args + [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.epsm_trace_paths_alpha_texture_forward.restype = C.c_int
-        lib.epsm_trace_paths_alpha_texture_forward.argtypes = am_args + [C.c_void_p, C.c_void_p, C.c_void_p]
+    # The colour adjoint's replays: scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, then the pass's own.
+    # (hasattr: the HIP library has them all; of the host builds, tests/host_harness/trace_{tex,bsdf,material,alphamap}_host.cpp)
+    replay_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+    reduced = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]    # adj, grad, slots, workspace, bytes, stream
+    for entry, tail in (("texture_backward", [C.c_void_p] * 4), ("texture_forward", [C.c_void_p] * 4),
+                        ("bsdf_backward", reduced), ("bsdf_forward", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+                        ("material_backward", reduced), ("material_forward", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+                        ("alpha_texture_backward", [C.c_void_p] * 3), ("alpha_texture_forward", [C.c_void_p] * 3)):
+        if hasattr(lib, "epsm_trace_paths_" + entry):
+            fn = getattr(lib, "epsm_trace_paths_" + entry)
+            fn.restype, fn.argtypes = C.c_int, replay_args + tail
+    for name in ("epsm_trace_bsdf_workspace_bytes", "epsm_trace_material_workspace_bytes"):
+        if hasattr(lib, name):
+            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_size_t, [C.c_int64]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int

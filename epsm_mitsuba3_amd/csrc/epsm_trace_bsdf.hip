@@ -1,76 +1,33 @@
 // epsm_trace_bsdf.hip -- kernels + C ABI of the roughness adjoint and its transpose (include/epsm_trace.h,
-// epsm_trace_paths_bsdf_backward / epsm_trace_paths_bsdf_forward; per-path code: epsm_trace_bsdf.h).
-#include <stdio.h>
-#include <string.h>
-
-#include "epsm_common.h"
+// epsm_trace_paths_bsdf_backward / epsm_trace_paths_bsdf_forward; per-path code: epsm_trace_bsdf.h; the device frame:
+// epsm_trace_adjoint.h).
+#include "epsm_trace_adjoint.h"
 #include "epsm_trace_bsdf.h"
-#include "epsm_trace_packet.h"
 
 using namespace epsm;
 using epsm_host::fail;
 
 namespace {
 
-struct BackwardSink {
-    ba::SlotSums sums;
-    __device__ __forceinline__ void item(const ba::Item &it) { sums.item(it); }
-    __device__ __forceinline__ void finish() {}
+// Backward: at most kMaxSlots numbers to reduce, so no atomics -- one row of kMaxSlots partial sums per workgroup
+// (block_row_reduce), epsm_rows_sum_kernel adds the rows up.
+struct BsdfPass {
+    using Args = ba::BsdfArgs;
+    using Backward = SumSink<ba::SlotSums>;
+    using Forward = ba::TangentSink;
+    template <class Sink> __device__ __forceinline__ static void replay(const Args &T, int64_t i, bool has, PathState &s,
+                                                                        const TriHit &th0, const BvhStack &st, Sink &sink) {
+        ba::bsdf_replay(T, i, has, s, th0, st, sink);
+    }
 };
 
-// the sum of v over the 64 lanes of the wave, in every lane (a butterfly: the same order of additions in every launch)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One lane = one path, as epsm_texture_kernel replays it (the primary rays walked by the wave, the same LDS stacks); lanes past N
-// ride along without a path so that both waves reach the reduction.  Backward: there are at most kMaxSlots numbers to reduce, so
-// no atomics -- a butterfly over each wave, the workgroup's two waves through LDS, one row of kMaxSlots partial sums per
-// workgroup; epsm_bsdf_sum_kernel adds the rows up.
 template <bool BACKWARD>
 __global__ __launch_bounds__(128, 2) void epsm_bsdf_kernel(ba::BsdfArgs T) {
     __shared__ uint32_t s_stack[kLaneStackLds * 128];
     __shared__ float s_part[2][ba::kMaxSlots];
-    uint32_t deep[kBvhStack - kLaneStackLds];
-    const int64_t i = (int64_t) blockIdx.x * 128 + threadIdx.x;
-    const BvhStack st = lane_stack(s_stack, deep, 128);
-    PrimaryHit p = primary_hit(T.A, i, false, s_stack);           // (no early exit: an idle wave still owes the reduction its zeros)
-    if (BACKWARD) {
-        BackwardSink sink;
-        sink.sums.adj = p.has ? ld3(T.adj + 3 * i) : zero3<float>();
-        sink.sums.clear();
-        ba::bsdf_replay(T, p.i, p.has, p.s, p.th0, st, sink);
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-        for (int k = 0; k < ba::kMaxSlots; ++k) {
-            const float v = k < T.n_slots ? wave_sum(sink.sums.acc[k]) : 0.f;      // (wave-uniform condition)
-            if (lane == 0) s_part[wave][k] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < ba::kMaxSlots)
-            T.partial[(int64_t) blockIdx.x * ba::kMaxSlots + threadIdx.x] = s_part[0][threadIdx.x] + s_part[1][threadIdx.x];
-    } else {
-        ba::TangentSink sink{T, p.i, p.has, zero3<float>()};
-        ba::bsdf_replay(T, p.i, p.has, p.s, p.th0, st, sink);
-    }
-}
-
-// grad_alpha[slot] += sum over the rows of partial[row][slot], in float64 and in a fixed order: thread t sums rows t, t + 256, ...,
-// then a tree over the 256 threads.  One workgroup per slot.
-__global__ __launch_bounds__(256) void epsm_bsdf_sum_kernel(const float *partial, int64_t rows, float *grad_alpha) {
-    __shared__ double s_sum[256];
-    const int slot = blockIdx.x;
-    double acc = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += 256) acc += (double) partial[r * ba::kMaxSlots + slot];
-    s_sum[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int) threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) grad_alpha[slot] += (float) s_sum[0];
+    BsdfPass::Backward sink;
+    replay_lane<BsdfPass, BACKWARD>(T, s_stack, sink);
+    if (BACKWARD) block_row_reduce(sink.sums.acc, T.n_slots, s_part, T.partial + (int64_t) blockIdx.x * ba::kMaxSlots);
 }
 
 }  // namespace
@@ -90,18 +47,10 @@ extern "C" int epsm_trace_paths_bsdf_backward(const EpsmScene *scene, const Epsm
     if (!adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
     if (B > 0 && !grad_alpha) return fail(EPSM_EINVAL, what, "NULL grad_alpha");
     if (B == 0) return EPSM_OK;
-    if (!workspace || workspace_bytes < ba::workspace_bytes(N) || ((uintptr_t) workspace & 15u))
+    if (!workspace_ok(workspace, workspace_bytes, ba::workspace_bytes(N)))
         return fail(EPSM_EINVAL, what, "workspace NULL, misaligned or smaller than epsm_trace_bsdf_workspace_bytes(N)");
     T.adj = adj_radiance; T.partial = (float *) workspace;
-    const int64_t rows = ba::partial_rows(N);
-    hipLaunchKernelGGL(epsm_bsdf_kernel<true>, dim3((unsigned) rows), dim3(128), 0, (hipStream_t) stream, T);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    hipLaunchKernelGGL(epsm_bsdf_sum_kernel, dim3((unsigned) B), dim3(256), 0, (hipStream_t) stream, (const float *) T.partial, rows,
-                       grad_alpha);
-    e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    return EPSM_OK;
+    return launch_reduced<ba::kMaxSlots>(what, epsm_bsdf_kernel<true>, T, ba::partial_rows(N), B, grad_alpha, stream);
 }
 
 extern "C" int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
@@ -116,8 +65,5 @@ extern "C" int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmS
     if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     if (B > 0 && !tangent_alpha) return fail(EPSM_EINVAL, what, "NULL tangent_alpha");
     T.tangent = tangent_alpha; T.d_radiance = d_radiance;
-    hipLaunchKernelGGL(epsm_bsdf_kernel<false>, dim3((unsigned) ba::partial_rows(N)), dim3(128), 0, (hipStream_t) stream, T);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    return EPSM_OK;
+    return launch_adjoint(what, epsm_bsdf_kernel<false>, ba::partial_rows(N), 128, stream, T);
 }

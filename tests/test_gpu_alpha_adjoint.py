@@ -11,14 +11,15 @@ from test_alpha_adjoint import TRANSPOSE, attach_two, transpose_gap, two_plate_s
 pytestmark = pytest.mark.gpu
 
 
-def _replay(sc, seed, spp, depth, adj, tangent):
-    """Both passes over every path of sensor 0: (d loss / d alpha per slot, d radiance for `tangent`, the primal radiance)."""
-    n = sc.sensors[0].wavefront_size(spp)
-    _, radiance, _ = sc.trace_color(0, seed, spp, depth, 0, n)
+def _replay(sc, seed, spp, depth, adj, tangent, lo=0, hi=None):
+    """Both passes over the paths [lo, hi) of sensor 0, by default all of them: (d loss / d alpha per slot, d radiance for
+    `tangent`, the primal radiance)."""
+    hi = sc.sensors[0].wavefront_size(spp) if hi is None else hi
+    _, radiance, _ = sc.trace_color(0, seed, spp, depth, lo, hi)
     radiance = radiance.contiguous()
     grad = torch.zeros(len(sc.alpha_slots), device=sc.device)
-    sc.trace_alpha_backward(0, seed, spp, depth, 0, n, radiance, adj.to(sc.device), grad)
-    d_rad = sc.trace_alpha_forward(0, seed, spp, depth, 0, n, radiance, tangent.to(sc.device))
+    sc.trace_alpha_backward(0, seed, spp, depth, lo, hi, radiance, adj.to(sc.device), grad)
+    d_rad = sc.trace_alpha_forward(0, seed, spp, depth, lo, hi, radiance, tangent.to(sc.device))
     return grad.cpu(), d_rad.cpu(), radiance.cpu()
 
 
@@ -95,6 +96,41 @@ def test_one_large_tile_equals_the_sum_of_its_halves():
     print(f"whole tile vs halves: relative gap {rel.tolist()}")
     assert float(halves.abs().min()) > 0
     assert float(rel.max()) <= 1e-6, (whole, halves)
+
+
+def _ragged_pair(lo, hi):
+    """The two-plate scene at 16 x 16 @ 8 spp (2048 paths), both passes over [lo, hi) on the device and on the host twin."""
+    spp, seed, depth = 8, 7, 3
+    dev, host = two_plate_scene("cuda", 16, spp), two_plate_scene("cpu", 16, spp)
+    attach_two(dev); attach_two(host)
+    assert dev.sensors[0].wavefront_size(spp) >= hi
+    adj = torch.randn((hi - lo, 3), generator=torch.Generator().manual_seed(lo))
+    tangent = torch.tensor([0.7, -1.3])
+    return _replay(dev, seed, spp, depth, adj, tangent, lo, hi), _replay(host, seed, spp, depth, adj, tangent, lo, hi)
+
+
+@pytest.mark.parametrize("lo,hi", [(1000, 1040), (960, 1025), (960, 1089), (960, 1153), (900, 1901)])
+def test_ragged_path_counts(lo, hi):
+    """Path counts that leave lanes and whole waves of the reducing kernel without a path: 40 paths that start inside a wave of
+    the full launch (the workgroup's second wave is idle), 65 (one lane in the second wave), 129 (the second workgroup has one
+    lane: its second wave is idle and still owes the reduction its zeros), 193, and a ragged tile of eight workgroups."""
+    (gd, fd_, rd), (gh, fh, rh) = _ragged_pair(lo, hi)
+    print(f"[{lo}, {hi}): radiance gap {float((rd - rh).abs().sum()) / float(rh.abs().sum()):.3e}, backward gap "
+          f"{float((gd - gh).abs().sum()) / float(gh.abs().sum()):.3e}, forward gap {float((fd_ - fh).abs().sum()) / float(fh.abs().sum()):.3e}")
+    assert float((rd - rh).abs().sum()) <= 1e-3 * float(rh.abs().sum())
+    assert float(gh.abs().min()) > 0
+    assert float((gd - gh).abs().sum()) <= 2e-3 * float(gh.abs().sum()), (gd, gh)
+    assert float(fh.abs().sum()) > 0
+    assert float((fd_ - fh).abs().sum()) <= 2e-3 * float(fh.abs().sum())
+
+
+def test_one_path_that_misses_the_plates_gives_zeros():
+    """[1000, 1001): 127 of the workgroup's 128 lanes ride along; the one path sees no plate, and zero is the answer."""
+    (gd, fd_, rd), (gh, fh, rh) = _ragged_pair(1000, 1001)
+    print(f"[1000, 1001): radiance {rd.tolist()} / {rh.tolist()}, backward {gd.tolist()} / {gh.tolist()}, forward {fd_.tolist()} / {fh.tolist()}")
+    assert float((rd - rh).abs().sum()) <= 1e-3 * float(rh.abs().sum())
+    assert float(gh.abs().sum()) == 0 and torch.equal(gd, gh)
+    assert float((fd_ - fh).abs().sum()) <= 2e-3 * float(fh.abs().sum())      # (exact where the twin gives zeros)
 
 
 def test_roughness_experiment_recovers_alpha():

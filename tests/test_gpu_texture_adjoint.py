@@ -32,16 +32,17 @@ def _attach(sc):
     return slots
 
 
-def _replay(sc, seed, spp, depth, adj):
-    """Both texel passes over every path of sensor 0: (texel gradients per slot, d radiance for the tangent 1 + texel index)."""
-    n = sc.sensors[0].wavefront_size(spp)
-    _, radiance, _ = sc.trace_color(0, seed, spp, depth, 0, n)
+def _replay(sc, seed, spp, depth, adj, lo=0, hi=None):
+    """Both texel passes over the paths [lo, hi) of sensor 0, by default all of them: (texel gradients per slot, d radiance for
+    the tangent 1 + texel index)."""
+    hi = sc.sensors[0].wavefront_size(spp) if hi is None else hi
+    _, radiance, _ = sc.trace_color(0, seed, spp, depth, lo, hi)
     radiance = radiance.contiguous()
     shapes = sc.texture_shapes()
     grads = [torch.zeros((h, w, 3), device=sc.device) for h, w in shapes]
-    sc.trace_texture_backward(0, seed, spp, depth, 0, n, radiance, adj.to(sc.device), grads)
+    sc.trace_texture_backward(0, seed, spp, depth, lo, hi, radiance, adj.to(sc.device), grads)
     tans = [torch.from_numpy(np.cos(np.arange(h * w * 3, dtype=np.float32) * 0.37).reshape(h, w, 3)).to(sc.device) for h, w in shapes]
-    d_rad = sc.trace_texture_forward(0, seed, spp, depth, 0, n, radiance, tans)
+    d_rad = sc.trace_texture_forward(0, seed, spp, depth, lo, hi, radiance, tans)
     return [g.cpu() for g in grads], d_rad.cpu(), radiance.cpu()
 
 
@@ -55,6 +56,27 @@ def test_device_passes_match_the_host_twin(name, depth):
     adj = torch.randn((n, 3), generator=torch.Generator().manual_seed(depth))
     gd, fd_, rd = _replay(dev, seed, spp, depth, adj)
     gh, fh, rh = _replay(host, seed, spp, depth, adj)
+    assert float((rd - rh).abs().sum()) <= 1e-3 * float(rh.abs().sum())
+    for a, b in zip(gd, gh):
+        assert float(b.abs().sum()) > 0
+        assert float((a - b).abs().sum()) <= 2e-3 * float(b.abs().sum()), (float((a - b).abs().sum()), float(b.abs().sum()))
+    assert float(fh.abs().sum()) > 0
+    assert float((fd_ - fh).abs().sum()) <= 2e-3 * float(fh.abs().sum())
+
+
+@pytest.mark.parametrize("res,spp,lo,hi", [(5, 5, 0, 125), (9, 3, 0, 243), (16, 8, 100, 1001)])
+def test_ragged_path_counts(res, spp, lo, hi):
+    """The count shapes of test_gpu_alpha_texture.py: 125 paths, less than one workgroup; 243, a workgroup and a ragged second;
+    a tile that starts at path 100 -- inside a wave of the full launch -- and ends at 1001.  Floor texture and envmap attached."""
+    dev, host = _pair("shared_footprints", res, spp)
+    _attach(dev); _attach(host)
+    assert dev.sensors[0].wavefront_size(spp) >= hi and (lo == 0 or lo % 64 != 0)
+    adj = torch.randn((hi - lo, 3), generator=torch.Generator().manual_seed(3 + lo))
+    gd, fd_, rd = _replay(dev, 7, spp, 3, adj, lo, hi)
+    gh, fh, rh = _replay(host, 7, spp, 3, adj, lo, hi)
+    print(f"{res}x{res} @ {spp} [{lo}, {hi}): radiance gap {float((rd - rh).abs().sum()) / float(rh.abs().sum()):.3e}, backward gaps "
+          f"{[float((a - b).abs().sum()) / float(b.abs().sum()) for a, b in zip(gd, gh)]}, forward gap "
+          f"{float((fd_ - fh).abs().sum()) / float(fh.abs().sum()):.3e}")
     assert float((rd - rh).abs().sum()) <= 1e-3 * float(rh.abs().sum())
     for a, b in zip(gd, gh):
         assert float(b.abs().sum()) > 0
