@@ -1,8 +1,9 @@
-// epsm_trace.hip -- kernels + C ABI of the wavefront tracer (include/epsm_trace.h).
+// epsm_trace.hip -- the tracer's kernels + C ABI (include/epsm_trace.h): the one-launch form and the wavefront form with its stages.
 #include <stdio.h>
 #include <string.h>
 
 #include "epsm_common.h"
+#include "epsm_trace_launch.h"
 #include "epsm_trace_replay.h"
 #include "epsm_trace_wavefront.h"
 #include "epsm_trace_packet.h"
@@ -334,234 +335,6 @@ __global__ __launch_bounds__(256) void epsm_wf_finish_kernel(TraceArgs A, WfStat
     for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < A.N; i += (int64_t) gridDim.x * 256) wf_finish(A, W, i);
 }
 
-// ImageBlock::put (src/render/imageblock.cpp) with the reconstruction filter evaluated
-// exactly (box: the pixel under the sample; gaussian: stddev 0.5, radius 4 sigma = 2,
-// src/rfilters/gaussian.cpp) -- separable weights, float atomics into [r,g,b,w].
-//
-// The wavefront is ordered pixel-major, sample-minor (common.py:320-330), so the lanes of a wave are the
-// samples of one pixel (spp >= 64) or of a few pixels (8, 16, 32 spp).  Lanes of an aligned group of G
-// lanes that sit in the same pixel splat onto the same 5x5 window: their weighted radiances are summed
-// with DPP adds and ONE lane issues the four atomics of a window pixel -- 100 atomics per group instead
-// of 64 x 16 x 4 per wave (the render was bound by the atomic rate: 68 ms at 512x512 @ 64 spp).
-// Arbitrary sample positions are still correct: a wave whose groups are not uniform splats lane by lane.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float splat_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-// Sum over aligned groups of G lanes (all 64 lanes active); the last lane of each group holds the total.
-template <int G> __device__ __forceinline__ float group_total(float v) {
-    v = splat_dpp_add<0xB1, 0xf>(v);                    // quad_perm [1,0,3,2]
-    v = splat_dpp_add<0x4E, 0xf>(v);                    // quad_perm [2,3,0,1]
-    v = splat_dpp_add<0x141, 0xf>(v);                   // row_half_mirror: 8 lanes
-    if (G >= 16) v = splat_dpp_add<0x140, 0xf>(v);      // row_mirror: 16 lanes
-    if (G == 64) {
-        v = splat_dpp_add<0x142, 0xa>(v);               // row_bcast15
-        v = splat_dpp_add<0x143, 0xc>(v);               // row_bcast31
-    }
-    return v;
-}
-struct SplatWeights { float wx[5], wy[5]; int X, Y; };
-__device__ __forceinline__ SplatWeights gaussian_window(float px, float py) {
-    SplatWeights w;
-    w.X = (int) floorf(px); w.Y = (int) floorf(py);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const float dx = (w.X + j - 2 + 0.5f) - px, dy = (w.Y + j - 2 + 0.5f) - py;
-        // pixel centres farther than the radius get weight 0: the 5x5 window holds
-        // exactly the pixels ImageBlock::put visits (ceil(p - r - 0.5) .. floor(p + r - 0.5))
-        w.wx[j] = gaussian_rfilter(dx);
-        w.wy[j] = gaussian_rfilter(dy);
-    }
-    return w;
-}
-template <int G>
-__device__ __forceinline__ void splat_groups(const SplatWeights &w, float r, float g, float b, int W, int H, float *accum) {
-    const bool carrier = (threadIdx.x & (G - 1)) == G - 1;
-#pragma unroll
-    for (int jy = 0; jy < 5; ++jy) {
-        const int y = w.Y + jy - 2;
-#pragma unroll
-        for (int jx = 0; jx < 5; ++jx) {
-            const int x = w.X + jx - 2;
-            const float wt = w.wy[jy] * w.wx[jx];
-            const float sr = group_total<G>(r * wt), sg = group_total<G>(g * wt), sb = group_total<G>(b * wt),
-                        sw = group_total<G>(wt);
-            if (carrier && sw != 0.f && x >= 0 && y >= 0 && x < W && y < H) {
-                float *a = accum + 4 * ((int64_t) y * W + x);
-                atomicAdd(a + 0, sr); atomicAdd(a + 1, sg); atomicAdd(a + 2, sb); atomicAdd(a + 3, sw);
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void epsm_film_splat_kernel(int64_t N, const float *pos, const float *rad, int W, int H,
-                                                              int rfilter, float *accum) {
-    const int64_t i0 = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    const bool live = i0 < N;
-    const int64_t i = live ? i0 : N - 1;                // lanes past the end take part in the sums with weight 0
-    const float px = pos[2 * i], py = pos[2 * i + 1];
-    float r = rad[3 * i], g = rad[3 * i + 1], b = rad[3 * i + 2];
-    if (rfilter == EPSM_RFILTER_BOX) {
-        const int x = (int) floorf(px), y = (int) floorf(py);
-        if (!live || x < 0 || y < 0 || x >= W || y >= H) return;
-        float *a = accum + 4 * ((int64_t) y * W + x);
-        atomicAdd(a + 0, r); atomicAdd(a + 1, g); atomicAdd(a + 2, b); atomicAdd(a + 3, 1.f);
-        return;
-    }
-    SplatWeights w = gaussian_window(px, py);
-    if (!live) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) w.wx[j] = w.wy[j] = 0.f;
-    }
-    // largest aligned group size whose lanes all sit in one pixel, the same for the whole wave
-    const int lane = threadIdx.x & 63;
-    const int X8 = __shfl(w.X, lane & ~7), Y8 = __shfl(w.Y, lane & ~7);
-    const int X16 = __shfl(w.X, lane & ~15), Y16 = __shfl(w.Y, lane & ~15);
-    const int X64 = __builtin_amdgcn_readfirstlane(w.X), Y64 = __builtin_amdgcn_readfirstlane(w.Y);
-    if (__ballot(w.X != X64 || w.Y != Y64) == 0ull) { splat_groups<64>(w, r, g, b, W, H, accum); return; }
-    if (__ballot(w.X != X16 || w.Y != Y16) == 0ull) { splat_groups<16>(w, r, g, b, W, H, accum); return; }
-    if (__ballot(w.X != X8 || w.Y != Y8) == 0ull) { splat_groups<8>(w, r, g, b, W, H, accum); return; }
-#pragma unroll
-    for (int jy = 0; jy < 5; ++jy) {
-        const int y = w.Y + jy - 2;
-        if (y < 0 || y >= H) continue;
-#pragma unroll
-        for (int jx = 0; jx < 5; ++jx) {
-            const int x = w.X + jx - 2;
-            const float wt = w.wy[jy] * w.wx[jx];
-            if (x < 0 || x >= W || wt == 0.f) continue;
-            float *a = accum + 4 * ((int64_t) y * W + x);
-            atomicAdd(a + 0, r * wt); atomicAdd(a + 1, g * wt); atomicAdd(a + 2, b * wt); atomicAdd(a + 3, wt);
-        }
-    }
-}
-// Adjoint of the gaussian splat + weight division w.r.t. a sample's radiance, its FILM POSITION and the determinant of the
-// reparameterisation that multiplies both its value and its weight (common.py:880-920; prb_reparam's pass between its two
-// traces):   image[p] = sum_i w_ip L_i det_i / sum_i w_ip det_i,   w_ip = f(p - pos_i).
-// One lane per sample, its 5 x 5 window of pixels: dL = sum_p w_ip grad_p / W_p;  A_p = grad_p . (L_i - image_p) / W_p;
-// d/d pos.x = sum_p A_p wy dwx,  d/d pos.y = sum_p A_p dwy wx,  d/d det = sum_p A_p w.  (Round 3 ran this as ~40 small torch
-// kernels per tile: integrators.film_adjoint_reparam, kept as the checker.)
-__global__ __launch_bounds__(256) void epsm_film_adjoint_reparam_kernel(int64_t N, const float *pos, const float *rad, const float *grad,
-                                                                        int grad_stride, const float *accum, int W, int H,
-                                                                        float *dL, float *adj) {
-    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const float px = pos[2 * i], py = pos[2 * i + 1];
-    const float r = rad[3 * i], g = rad[3 * i + 1], b = rad[3 * i + 2];
-    const float radius = 2.f, alpha = -1.f / (2.f * 0.5f * 0.5f), bias = expf(alpha * radius * radius);
-    const int X = (int) floorf(px), Y = (int) floorf(py);
-    float wx[5], wy[5], dwx[5], dwy[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int x = X + j - 2, y = Y + j - 2;
-        const float dx = (x + 0.5f) - px, dy = (y + 0.5f) - py;
-        const float ex = expf(alpha * dx * dx), ey = expf(alpha * dy * dy);
-        const bool lx = fabsf(dx) <= radius && x >= 0 && x < W && ex - bias > 0.f;
-        const bool ly = fabsf(dy) <= radius && y >= 0 && y < H && ey - bias > 0.f;
-        wx[j] = lx ? ex - bias : 0.f; dwx[j] = lx ? -2.f * alpha * dx * ex : 0.f;      // d w / d pos (dx = pixel centre - pos)
-        wy[j] = ly ? ey - bias : 0.f; dwy[j] = ly ? -2.f * alpha * dy * ey : 0.f;
-    }
-    float lr = 0.f, lg = 0.f, lb = 0.f, ax = 0.f, ay = 0.f, ad = 0.f;
-#pragma unroll
-    for (int jy = 0; jy < 5; ++jy) {
-        const int y = min(max(Y + jy - 2, 0), H - 1);
-#pragma unroll
-        for (int jx = 0; jx < 5; ++jx) {
-            const int x = min(max(X + jx - 2, 0), W - 1);
-            const float w2 = wy[jy] * wx[jx], wdx = wy[jy] * dwx[jx], wdy = dwy[jy] * wx[jx];
-            if (w2 == 0.f && wdx == 0.f && wdy == 0.f) continue;
-            const int64_t p = (int64_t) y * W + x;
-            const float Wp = accum[4 * p + 3];
-            const float inv = Wp > 0.f ? 1.f / fmaxf(Wp, 1e-30f) : 0.f;
-            const float *gp = grad + p * grad_stride;
-            const float gr = gp[0] * inv, gg = gp[1] * inv, gb = gp[2] * inv;             // grad / W_p
-            const float gi = (gr * accum[4 * p] + gg * accum[4 * p + 1] + gb * accum[4 * p + 2]) * inv;   // (grad . image) / W_p
-            const float A = gr * r + gg * g + gb * b - gi;
-            lr += gr * w2; lg += gg * w2; lb += gb * w2;
-            ax += A * wdx; ay += A * wdy; ad += A * w2;
-        }
-    }
-    dL[3 * i] = lr; dL[3 * i + 1] = lg; dL[3 * i + 2] = lb;
-    adj[3 * i] = ax; adj[3 * i + 1] = ay; adj[3 * i + 2] = ad;
-}
-// Forward mode of the splat + weight division (common.py:880-920), the transpose of epsm_film_adjoint_reparam_kernel: one lane per
-// sample, its 5 x 5 window (the box filter: the pixel under it).  Per pixel p, with w_ip = f(p - pos_i) and its gradient,
-//   dA_p += (grad w . dpos_i + w ddet_i) L_i + w dL_i,    dW_p += grad w . dpos_i + w ddet_i
-// into d_accum (H,W,4); the image's tangent is (dA - image dW) / W with the primal film.  d_film may be NULL (colour tangents:
-// the samples do not move).  Lanes whose samples share a pixel sum over the group before the atomics, as epsm_film_splat_kernel
-// does (one atomic per lane and pixel: 10.9 ms at 4.26 M samples, against 0.73 ms for the primal splat).
-struct TangentWindow { float wx[5], wy[5], dwx[5], dwy[5]; int X, Y; };
-template <int G> __device__ __forceinline__ float group_total_or_own(float v) {
-    if constexpr (G == 1) return v;
-    else return group_total<G>(v);
-}
-template <int G>
-__device__ __forceinline__ void splat_tangent_groups(const TangentWindow &w, const float *L, const float *T, const float *F, int W, int H,
-                                                     float *d_accum) {
-    const bool carrier = (threadIdx.x & (G - 1)) == G - 1;
-#pragma unroll
-    for (int jy = 0; jy < 5; ++jy) {
-        const int y = w.Y + jy - 2;
-#pragma unroll
-        for (int jx = 0; jx < 5; ++jx) {
-            const int x = w.X + jx - 2;
-            const float w2 = w.wy[jy] * w.wx[jx];
-            const float dw = w.wy[jy] * w.dwx[jx] * F[0] + w.dwy[jy] * w.wx[jx] * F[1] + w2 * F[2];      // d (w det)
-            const float sr = group_total_or_own<G>(dw * L[0] + w2 * T[0]), sg = group_total_or_own<G>(dw * L[1] + w2 * T[1]),
-                        sb = group_total_or_own<G>(dw * L[2] + w2 * T[2]), sw = group_total_or_own<G>(dw);
-            if (carrier && x >= 0 && y >= 0 && x < W && y < H && (sr != 0.f || sg != 0.f || sb != 0.f || sw != 0.f)) {
-                float *a = d_accum + 4 * ((int64_t) y * W + x);
-                atomicAdd(a + 0, sr); atomicAdd(a + 1, sg); atomicAdd(a + 2, sb);
-                if (sw != 0.f) atomicAdd(a + 3, sw);
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void epsm_film_splat_tangent_kernel(int64_t N, const float *pos, const float *rad, const float *d_rad,
-                                                                      const float *d_film, int W, int H, int rfilter, float *d_accum) {
-    const int64_t i0 = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    const bool live = i0 < N;
-    const int64_t i = live ? i0 : N - 1;                // lanes past the end take part in the sums with weight 0
-    const float px = pos[2 * i], py = pos[2 * i + 1];
-    const float T[3] = {d_rad[3 * i], d_rad[3 * i + 1], d_rad[3 * i + 2]};
-    if (rfilter == EPSM_RFILTER_BOX) {                                    // (a box weight does not move with the sample)
-        const int x = (int) floorf(px), y = (int) floorf(py);
-        if (!live || x < 0 || y < 0 || x >= W || y >= H) return;
-        float *a = d_accum + 4 * ((int64_t) y * W + x);
-        atomicAdd(a + 0, T[0]); atomicAdd(a + 1, T[1]); atomicAdd(a + 2, T[2]);
-        return;
-    }
-    const float L[3] = {rad[3 * i], rad[3 * i + 1], rad[3 * i + 2]};
-    const float F[3] = {d_film ? d_film[3 * i] : 0.f, d_film ? d_film[3 * i + 1] : 0.f, d_film ? d_film[3 * i + 2] : 0.f};
-    const float radius = 2.f, alpha = -1.f / (2.f * 0.5f * 0.5f), bias = expf(alpha * radius * radius);
-    TangentWindow w;
-    w.X = (int) floorf(px); w.Y = (int) floorf(py);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int x = w.X + j - 2, y = w.Y + j - 2;
-        const float dx = (x + 0.5f) - px, dy = (y + 0.5f) - py;
-        const float ex = expf(alpha * dx * dx), ey = expf(alpha * dy * dy);
-        const bool lx = live && fabsf(dx) <= radius && x >= 0 && x < W && ex - bias > 0.f;
-        const bool ly = live && fabsf(dy) <= radius && y >= 0 && y < H && ey - bias > 0.f;
-        w.wx[j] = lx ? ex - bias : 0.f; w.dwx[j] = lx ? -2.f * alpha * dx * ex : 0.f;
-        w.wy[j] = ly ? ey - bias : 0.f; w.dwy[j] = ly ? -2.f * alpha * dy * ey : 0.f;
-    }
-    // largest aligned group size whose lanes all sit in one pixel, the same for the whole wave (epsm_film_splat_kernel)
-    const int lane = threadIdx.x & 63;
-    const int X8 = __shfl(w.X, lane & ~7), Y8 = __shfl(w.Y, lane & ~7);
-    const int X16 = __shfl(w.X, lane & ~15), Y16 = __shfl(w.Y, lane & ~15);
-    const int X64 = __builtin_amdgcn_readfirstlane(w.X), Y64 = __builtin_amdgcn_readfirstlane(w.Y);
-    if (__ballot(w.X != X64 || w.Y != Y64) == 0ull) { splat_tangent_groups<64>(w, L, T, F, W, H, d_accum); return; }
-    if (__ballot(w.X != X16 || w.Y != Y16) == 0ull) { splat_tangent_groups<16>(w, L, T, F, W, H, d_accum); return; }
-    if (__ballot(w.X != X8 || w.Y != Y8) == 0ull) { splat_tangent_groups<8>(w, L, T, F, W, H, d_accum); return; }
-    splat_tangent_groups<1>(w, L, T, F, W, H, d_accum);
-}
-__global__ __launch_bounds__(256) void epsm_film_develop_kernel(int64_t n, const float *accum, float *image) {
-    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float w = accum[4 * i + 3], iw = w != 0.f ? 1.f / w : 0.f;
-    image[3 * i] = accum[4 * i] * iw; image[3 * i + 1] = accum[4 * i + 1] * iw; image[3 * i + 2] = accum[4 * i + 2] * iw;
-}
-
 }  // namespace
 
 // Validates the arguments of the tracer entry points and fills the kernel argument block (the common prefix: replay_args_fill).
@@ -626,10 +399,7 @@ extern "C" int epsm_trace_paths(const EpsmScene *scene, const EpsmSensor *sensor
     const int rc = fill_trace_args(A, "epsm_trace_paths", scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log,
                                    ray_o, ray_d, ray_dx, ray_dy, film_pos, radiance, valid, recs, flags);
     if (rc != EPSM_OK) return rc;
-    hipLaunchKernelGGL(epsm_trace_kernel, dim3((unsigned) ((N + 127) / 128)), dim3(128), 0, (hipStream_t) stream, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths", e);
-    return EPSM_OK;
+    return launch_checked("epsm_trace_paths", epsm_trace_kernel, (N + 127) / 128, 128, stream, A);
 }
 
 extern "C" int epsm_trace_paths_color(const EpsmScene *scene, const EpsmSensor *sensor,
@@ -648,12 +418,9 @@ extern "C" int epsm_trace_paths_color(const EpsmScene *scene, const EpsmSensor *
     if (rc != EPSM_OK) return rc;
     A.ray_o = A.ray_d = A.ray_dx = A.ray_dy = nullptr;
     A.color_sum = color_sum; A.n_color = n_color;
-    hipError_t e = hipMemsetAsync(color_sum, 0, (size_t) N * n_color * 3 * sizeof(float), (hipStream_t) stream);
+    const hipError_t e = hipMemsetAsync(color_sum, 0, (size_t) N * n_color * 3 * sizeof(float), (hipStream_t) stream);
     if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_color", e);
-    hipLaunchKernelGGL(epsm_trace_kernel, dim3((unsigned) ((N + 127) / 128)), dim3(128), 0, (hipStream_t) stream, A);
-    e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_color", e);
-    return EPSM_OK;
+    return launch_checked("epsm_trace_paths_color", epsm_trace_kernel, (N + 127) / 128, 128, stream, A);
 }
 
 extern "C" size_t epsm_trace_workspace_bytes(int64_t N) { return N > 0 ? wf_workspace_bytes(N) : 0; }
@@ -714,55 +481,5 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
         hipLaunchKernelGGL(epsm_wf_finish_kernel, blocks(256), dim3(256), 0, s, A, W);
     e = hipGetLastError();
     if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_wavefront", e);
-    return EPSM_OK;
-}
-
-extern "C" int epsm_film_splat(int64_t N, const float *film_pos, const float *radiance, int width, int height,
-                               int rfilter, float *accum, void *stream) {
-    epsm_host::err_buf()[0] = 0;
-    if (N == 0) return EPSM_OK;
-    if (N < 0 || !film_pos || !radiance || !accum || width < 1 || height < 1)
-        return fail(EPSM_EINVAL, "epsm_film_splat: bad argument");
-    hipLaunchKernelGGL(epsm_film_splat_kernel, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
-                       N, film_pos, radiance, width, height, rfilter, accum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_splat", e);
-    return EPSM_OK;
-}
-extern "C" int epsm_film_adjoint_reparam(int64_t N, const float *film_pos, const float *radiance, const float *grad_img,
-                                         int grad_channels, const float *accum, int width, int height, float *dL, float *adj,
-                                         void *stream) {
-    epsm_host::err_buf()[0] = 0;
-    if (N == 0) return EPSM_OK;
-    if (N < 0 || !film_pos || !radiance || !grad_img || !accum || !dL || !adj || width < 1 || height < 1 || grad_channels < 3)
-        return fail(EPSM_EINVAL, "epsm_film_adjoint_reparam: bad argument");
-    hipLaunchKernelGGL(epsm_film_adjoint_reparam_kernel, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
-                       N, film_pos, radiance, grad_img, grad_channels, accum, width, height, dL, adj);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_adjoint_reparam", e);
-    return EPSM_OK;
-}
-extern "C" int epsm_film_develop(int width, int height, const float *accum, float *image, void *stream) {
-    epsm_host::err_buf()[0] = 0;
-    if (!accum || !image || width < 1 || height < 1) return fail(EPSM_EINVAL, "epsm_film_develop: bad argument");
-    const int64_t n = (int64_t) width * height;
-    hipLaunchKernelGGL(epsm_film_develop_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
-                       n, accum, image);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_develop", e);
-    return EPSM_OK;
-}
-extern "C" int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radiance, const float *d_radiance,
-                                       const float *d_film, int width, int height, int rfilter, float *d_accum, void *stream) {
-    epsm_host::err_buf()[0] = 0;
-    if (N == 0) return EPSM_OK;
-    if (N < 0 || !film_pos || !radiance || !d_radiance || !d_accum || width < 1 || height < 1)
-        return fail(EPSM_EINVAL, "epsm_film_splat_tangent: bad argument");
-    if (rfilter == EPSM_RFILTER_BOX && d_film)
-        return fail(EPSM_EINVAL, "epsm_film_splat_tangent: a box filter has no derivative in the film position (d_film must be NULL)");
-    hipLaunchKernelGGL(epsm_film_splat_tangent_kernel, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, (hipStream_t) stream,
-                       N, film_pos, radiance, d_radiance, d_film, width, height, rfilter, d_accum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail("epsm_film_splat_tangent", e);
     return EPSM_OK;
 }

@@ -1,8 +1,8 @@
 // epsm_trace_adjoint.h -- the device frame of the colour adjoint's replay passes ("the replay frame"): what the units
 // epsm_trace_{texture,bsdf,material,alphamap}.hip share beyond the per-path code.  The lane prologue (replay_lane), the two
 // ways a backward pass gets rid of its sums -- the atomic-free row reduction (SumSink, block_row_reduce, epsm_rows_sum_kernel)
-// and the merged scatter into texel footprints (FootprintScatter) -- and the host side of an entry point (workspace_ok,
-// launch_adjoint, launch_reduced).  Device only: hipcc, never the host harness.
+// and the merged scatter into texel footprints (FootprintScatter) -- and the reducing pass's pair of launches (launch_reduced,
+// on the checked launch of epsm_trace_launch.h).  Device only: hipcc, never the host harness.
 //
 // A unit describes its pass by a struct P:
 //     Args                       the argument block (`A`, `adj`, what its sinks read)
@@ -13,6 +13,7 @@
 
 #include "epsm_common.h"
 #include "epsm_trace_alphamap.h"         // tx::Item, am::NoItem: what a footprint sink is handed
+#include "epsm_trace_launch.h"
 #include "epsm_trace_packet.h"
 #include "epsm_wave_scatter.h"           // make_runs / seg_sum: the merge before the atomics
 
@@ -139,24 +140,12 @@ struct FootprintScatter {
     __device__ __forceinline__ void finish() {}
 };
 
-// ---- the host side of an entry point ----
-// a backward pass's workspace: there, 16-byte aligned and of `need` bytes at least
-inline bool workspace_ok(const void *workspace, size_t bytes, size_t need) {
-    return workspace && bytes >= need && !((uintptr_t) workspace & 15u);
-}
-
-template <class Kernel, class... Params>
-int launch_adjoint(const char *what, Kernel kernel, int64_t blocks, unsigned threads, void *stream, Params... params) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, (hipStream_t) stream, params...);
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? epsm_host::hip_fail(what, e) : EPSM_OK;
-}
-
+// ---- the host side of an entry point (workspace_ok, launch_checked: epsm_trace_launch.h) ----
 // a reducing pass's backward kernel over `rows` workgroups, then the rows' sum into out[0 .. n_live)
 template <int ROW, class Kernel, class Args>
 int launch_reduced(const char *what, Kernel kernel, const Args &T, int64_t rows, int n_live, float *out, void *stream) {
-    if (const int rc = launch_adjoint(what, kernel, rows, 128, stream, T)) return rc;
-    return launch_adjoint(what, epsm_rows_sum_kernel<ROW>, n_live, 256, stream, (const float *) T.partial, rows, out);
+    if (const int rc = launch_checked(what, kernel, rows, 128, stream, T)) return rc;
+    return launch_checked(what, epsm_rows_sum_kernel<ROW>, n_live, 256, stream, (const float *) T.partial, rows, out);
 }
 
 }  // namespace epsm

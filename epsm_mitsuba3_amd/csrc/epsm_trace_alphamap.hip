@@ -44,7 +44,7 @@ extern "C" int epsm_trace_paths_alpha_texture_backward(const EpsmScene *scene, c
     if (!adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
     if (T.n_buf == 0) return EPSM_OK;
     T.adj = adj_radiance;
-    return launch_adjoint(what, epsm_alphamap_kernel<true>, (N + 127) / 128, 128, stream, T);
+    return launch_checked(what, epsm_alphamap_kernel<true>, (N + 127) / 128, 128, stream, T);
 }
 
 extern "C" int epsm_trace_paths_alpha_texture_forward(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp,
@@ -61,5 +61,5 @@ extern "C" int epsm_trace_paths_alpha_texture_forward(const EpsmScene *scene, co
     if (N == 0) return EPSM_OK;
     if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     T.d_radiance = d_radiance;
-    return launch_adjoint(what, epsm_alphamap_kernel<false>, (N + 127) / 128, 128, stream, T);
+    return launch_checked(what, epsm_alphamap_kernel<false>, (N + 127) / 128, 128, stream, T);
 }

@@ -65,5 +65,5 @@ extern "C" int epsm_trace_paths_bsdf_forward(const EpsmScene *scene, const EpsmS
     if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     if (B > 0 && !tangent_alpha) return fail(EPSM_EINVAL, what, "NULL tangent_alpha");
     T.tangent = tangent_alpha; T.d_radiance = d_radiance;
-    return launch_adjoint(what, epsm_bsdf_kernel<false>, ba::partial_rows(N), 128, stream, T);
+    return launch_checked(what, epsm_bsdf_kernel<false>, ba::partial_rows(N), 128, stream, T);
 }

@@ -876,6 +876,14 @@ EPSM_HD float gaussian_rfilter(float x) {
     const float bias = expf(kGaussAlpha * kGaussRadius * kGaussRadius);
     return fabsf(x) <= kGaussRadius ? fmaxf(0.f, expf(kGaussAlpha * x * x) - bias) : 0.f;
 }
+// The same weight with its derivative in the sample's position (x = pixel centre - position): d w / d pos = -2 alpha x e where
+// the weight is positive, 0 elsewhere (film.py, _gaussian_window); one exponential serves both.
+EPSM_HD float gaussian_rfilter_d(float x, float &dw) {
+    const float bias = expf(kGaussAlpha * kGaussRadius * kGaussRadius), e = expf(kGaussAlpha * x * x);
+    const bool live = fabsf(x) <= kGaussRadius && e - bias > 0.f;
+    dw = live ? -2.f * kGaussAlpha * x * e : 0.f;
+    return live ? e - bias : 0.f;
+}
 
 // ---------------------------------------------------------------------------
 // the path (epsm.py:503-742)

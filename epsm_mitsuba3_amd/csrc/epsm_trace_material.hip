@@ -65,5 +65,5 @@ extern "C" int epsm_trace_paths_material_forward(const EpsmScene *scene, const E
     if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     if (M > 0 && !tangent_material) return fail(EPSM_EINVAL, what, "NULL tangent_material");
     T.tangent = tangent_material; T.d_radiance = d_radiance;
-    return launch_adjoint(what, epsm_material_kernel<false>, ma::partial_rows(N), 128, stream, T);
+    return launch_checked(what, epsm_material_kernel<false>, ma::partial_rows(N), 128, stream, T);
 }

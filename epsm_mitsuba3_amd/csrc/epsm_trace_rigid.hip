@@ -5,7 +5,10 @@
 #include <stdint.h>
 
 #include "epsm_common.h"
+#include "epsm_trace_launch.h"
 
+using epsm::launch_checked;
+using epsm::workspace_ok;
 using epsm_host::fail;
 
 namespace {
@@ -147,18 +150,13 @@ extern "C" int epsm_rigid_reduce(const float *positions, const float *normals, c
     if (V > 0 && n_slots > 0 && (!positions || !g_pos)) return fail(EPSM_EINVAL, what, "NULL positions or g_pos");
     if (g_nrm && !normals) return fail(EPSM_EINVAL, what, "g_nrm without normals");
     if (V == 0 || n_slots == 0) return EPSM_OK;
-    if (!workspace || workspace_bytes < epsm_rigid_workspace_bytes(V, n_slots) || ((uintptr_t) workspace & 15u))
+    if (!workspace_ok(workspace, workspace_bytes, epsm_rigid_workspace_bytes(V, n_slots)))
         return fail(EPSM_EINVAL, what, "workspace NULL, misaligned or smaller than epsm_rigid_workspace_bytes(V, n_slots)");
     const int64_t mc = max_chunks_of(V);
-    hipLaunchKernelGGL(epsm_rigid_partial_kernel, dim3((unsigned) mc, (unsigned) n_slots), dim3(256), 0, (hipStream_t) stream, positions,
-                       normals, g_pos, g_nrm, V, ranges, pivots, mc, (double *) workspace);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    hipLaunchKernelGGL(epsm_rigid_sum_kernel, dim3((unsigned) n_slots), dim3(64), 0, (hipStream_t) stream, (const double *) workspace, V,
-                       ranges, mc, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    return EPSM_OK;
+    if (const int rc = launch_checked(what, epsm_rigid_partial_kernel, dim3((unsigned) mc, (unsigned) n_slots), 256, stream, positions,
+                                      normals, g_pos, g_nrm, V, ranges, pivots, mc, (double *) workspace))
+        return rc;
+    return launch_checked(what, epsm_rigid_sum_kernel, n_slots, 64, stream, (const double *) workspace, V, ranges, mc, out);
 }
 
 extern "C" int epsm_rigid_expand(const float *positions, const float *normals, int64_t V, const int64_t *ranges, const float *pivots,
@@ -170,9 +168,6 @@ extern "C" int epsm_rigid_expand(const float *positions, const float *normals, i
     if (V > 0 && n_slots > 0 && (!positions || !d_pos)) return fail(EPSM_EINVAL, what, "NULL positions or d_pos");
     if (d_nrm && !normals) return fail(EPSM_EINVAL, what, "d_nrm without normals");
     if (V == 0 || n_slots == 0) return EPSM_OK;
-    hipLaunchKernelGGL(epsm_rigid_expand_kernel, dim3((unsigned) ((V + 255) / 256)), dim3(256), 0, (hipStream_t) stream, positions, normals,
-                       V, ranges, pivots, twists, (int) n_slots, d_pos, d_nrm);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    return EPSM_OK;
+    return launch_checked(what, epsm_rigid_expand_kernel, (V + 255) / 256, 256, stream, positions, normals, V, ranges, pivots, twists,
+                          (int) n_slots, d_pos, d_nrm);
 }

@@ -47,7 +47,7 @@ extern "C" int epsm_trace_paths_texture_backward(const EpsmScene *scene, const E
     if (!adj_radiance) return fail(EPSM_EINVAL, what, "NULL adj_radiance");
     if (T.n_buf == 0 && !grad_env) return EPSM_OK;
     T.adj = adj_radiance;
-    return launch_adjoint(what, epsm_texture_kernel<true>, (N + 127) / 128, 128, stream, T);
+    return launch_checked(what, epsm_texture_kernel<true>, (N + 127) / 128, 128, stream, T);
 }
 
 extern "C" int epsm_trace_paths_texture_forward(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
@@ -63,5 +63,5 @@ extern "C" int epsm_trace_paths_texture_forward(const EpsmScene *scene, const Ep
     if (N == 0) return EPSM_OK;
     if (!d_radiance) return fail(EPSM_EINVAL, what, "NULL d_radiance");
     T.d_radiance = d_radiance;
-    return launch_adjoint(what, epsm_texture_kernel<false>, (N + 127) / 128, 128, stream, T);
+    return launch_checked(what, epsm_texture_kernel<false>, (N + 127) / 128, 128, stream, T);
 }

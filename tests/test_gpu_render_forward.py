@@ -102,6 +102,104 @@ def test_film_splat_tangent_kernel_equals_its_torch_form(rfilter, moving):
     assert float((got.cpu() - ref).abs().max()) <= 1e-4 * scale
 
 
+def _pixel_major(res, spp, n_cut, gen):
+    """Film positions of a pixel-major wavefront without its last ``n_cut`` samples: pixel + uniform jitter."""
+    n = res * res * spp - n_cut
+    pix = torch.arange(res * res * spp)[:n] // spp
+    return torch.stack([(pix % res).float(), (pix // res).float()], dim=1) + torch.rand((n, 2), generator=gen)
+
+
+@pytest.mark.parametrize("rfilter,res,spp,n_cut,moving", [
+    (1, 9, 64, 0, True), (1, 9, 128, 0, True), (1, 12, 16, 0, True), (1, 12, 8, 0, True), (1, 11, 5, 0, True), (1, 9, 64, 37, True),
+    (1, 9, 64, 0, False), (1, 9, 128, 0, False), (1, 12, 16, 0, False), (1, 12, 8, 0, False), (1, 11, 5, 0, False), (1, 9, 64, 37, False),
+    (0, 12, 16, 0, False)])
+def test_film_splat_tangent_kernel_through_every_group_size(rfilter, res, spp, n_cut, moving):
+    """epsm_film_splat_tangent against its torch form on pixel-major wavefronts: 64 / 128, 16 and 8 spp take the sums over
+    groups of 64, 16 and 8 lanes, 5 spp the lane-by-lane form; a ragged tail puts lanes past the end (weight 0) into a
+    group of 64.  Films of 9 to 12 pixels: most 5 x 5 windows are clipped at an edge.  The bound is the one of
+    test_film_splat_tangent_kernel_equals_its_torch_form (the same kernel against the same reference): on these cases the
+    worst error of the build before the film unit was 9.6e-7 of max|ref| (MEASUREMENTS.md 24), far below a third of it."""
+    gen = torch.Generator().manual_seed(res * 1000 + spp + n_cut)
+    pos = _pixel_major(res, spp, n_cut, gen)
+    n = pos.shape[0]
+    L, dL = torch.rand((n, 3), generator=gen), torch.randn((n, 3), generator=gen)
+    dpos = torch.randn((n, 3), generator=gen) if moving else None
+    ref = film_splat_tangent_torch(pos, L, dL, dpos, res, res, rfilter)
+    got = torch.zeros((res, res, 4), device="cuda")
+    film_splat_tangent(got, pos.cuda(), L.cuda(), dL.cuda(), None if dpos is None else dpos.cuda(), rfilter)
+    torch.cuda.synchronize()
+    scale = float(ref.abs().max())
+    err = float((got.cpu() - ref).abs().max())
+    print("film_splat_tangent", (rfilter, res, spp, n_cut, moving), "err / max|ref| = %.3g" % (err / scale))
+    assert scale > 0
+    assert err <= 1e-4 * scale
+
+
+def _one_wave(name, gen):
+    """64 film positions -- one wave -- whose 5 x 5 windows overlap only inside an aligned group of lanes in one pixel, so that
+    every word of the film receives one atomic add at the most: -> (W, H, pos (n,2))."""
+    jitter = torch.rand((64, 2), generator=gen)
+    if name in ("64 lanes in one pixel", "40 lanes in one pixel"):
+        W = H = 14
+        px = torch.tensor([[1.0, 12.0]]).expand(64, 2)                      # (clipped at two edges)
+    elif name == "four pixels":                                             # four groups of 16 lanes, 7 pixels apart
+        W = H = 14
+        g = torch.arange(64) // 16
+        px = torch.stack([3.0 + 7 * (g % 2), 3.0 + 7 * (g // 2)], dim=1)
+    elif name == "eight pixels":                                            # eight groups of 8 lanes, 6 pixels apart
+        W, H = 23, 11
+        g = torch.arange(64) // 8
+        px = torch.stack([2.0 + 6 * (g % 4), 2.0 + 6 * (g // 4)], dim=1)
+    else:                                                                   # 64 pixels 5 apart, row 0 and column 0 among them
+        W = H = 40
+        g = torch.arange(64)
+        px = torch.stack([5.0 * (g % 8), 5.0 * (g // 8)], dim=1)
+    pos = (px + jitter)[:40 if name.startswith("40") else 64].contiguous()
+    return W, H, pos
+
+
+ONE_WAVE = ["64 lanes in one pixel", "four pixels", "eight pixels", "64 pixels", "40 lanes in one pixel"]
+
+
+@pytest.mark.parametrize("name", ONE_WAVE)
+@pytest.mark.parametrize("which", ["splat", "tangent"])
+def test_film_splats_one_group_size_at_a_time(which, name):
+    """Each group size of the two splats -- 64, 16, 8 lanes and lane by lane -- alone in one wave, and lanes past the end in a
+    group of 64.  No word of the film gets a second add, so the result does not depend on the order of the atomics: two calls
+    into zeroed films agree bit for bit, and the result meets the host twin (test_gpu_tracer.py::test_film_splat_matches_host's
+    bound) / the torch form (test_film_splat_tangent_kernel_equals_its_torch_form's)."""
+    import ctypes as C
+    from _scenes import host_tracer
+    from epsm_mitsuba3_amd import _lib
+    gen = torch.Generator().manual_seed(ONE_WAVE.index(name))
+    W, H, pos = _one_wave(name, gen)
+    n = pos.shape[0]
+    L, dL, dpos = torch.rand((n, 3), generator=gen) * 3.0, torch.randn((n, 3), generator=gen), torch.randn((n, 3), generator=gen)
+    pd, Ld, dLd, dposd = pos.cuda(), L.cuda(), dL.cuda(), dpos.cuda()
+    out = []
+    for _ in range(2):
+        got = torch.zeros((H, W, 4), device="cuda")
+        if which == "splat":
+            assert _lib.lib().epsm_film_splat(C.c_int64(n), C.c_void_p(pd.data_ptr()), C.c_void_p(Ld.data_ptr()), W, H, 1,
+                                              C.c_void_p(got.data_ptr()), C.c_void_p(_lib.stream(got.device))) == 0
+        else:
+            film_splat_tangent(got, pd, Ld, dLd, dposd, 1)
+        torch.cuda.synchronize()
+        out.append(got.cpu())
+    assert torch.equal(out[0], out[1])
+    if which == "splat":
+        want = torch.zeros((H, W, 4))
+        assert host_tracer().epsm_film_splat(C.c_int64(n), C.c_void_p(pos.data_ptr()), C.c_void_p(L.data_ptr()), W, H, 1,
+                                             C.c_void_p(want.data_ptr()), None) == 0
+        assert float(want.abs().max()) > 0
+        assert torch.allclose(out[0], want, rtol=2e-4, atol=2e-4 * float(want.abs().max()))
+    else:
+        ref = film_splat_tangent_torch(pos, L, dL, dpos, H, W, 1)
+        scale = float(ref.abs().max())
+        assert scale > 0
+        assert float((out[0] - ref).abs().max()) <= 1e-4 * scale
+
+
 @pytest.mark.parametrize("name,spp,tol", [
     ("diffuse_sphere_area_light", 4096, 0.15),
     ("textured_plane_constant", 800, 0.1),
