@@ -50,11 +50,24 @@ constexpr int kWfMaxChunkBlocks = 8192;                 // compaction: workgroup
 // it leaves are COMPACTED into a queue before bounce 0's shade stage (a scan + compaction pass numbered bounce -1) -- slot q of bounce 0
 // is then path queue[0][q] of counters[0], not path q of N.
 constexpr uint32_t kWfPreCompact = 0x80000000u;
-__device__ __forceinline__ bool wf_identity(const TraceArgs &A, int b) { return b < 0 || (b == 0 && !(A.flags & kWfPreCompact)); }   // slot == path
-__device__ __forceinline__ int64_t wf_count(const TraceArgs &A, const WfState &W, int b) {
-    return wf_identity(A, b) ? A.N : (int64_t) W.counters[b];
+// The slots a stage walks: `count` of them, slot q holding path queue[q] -- or path q itself (queue NULL).
+struct WfSlots {
+    const uint32_t *queue;
+    int64_t count;
+    __device__ __forceinline__ int64_t path(int64_t q) const { return queue ? (int64_t) queue[q] : q; }
+};
+// the paths alive into bounce b (bounce 0 and the pass numbered -1: every path, unless the survivors were compacted before bounce 0)
+__device__ __forceinline__ WfSlots wf_alive_slots(const TraceArgs &A, const WfState &W, int b) {
+    const bool identity = b < 0 || (b == 0 && !(A.flags & kWfPreCompact));
+    return identity ? WfSlots{nullptr, A.N} : WfSlots{W.queue[b & 1], (int64_t) W.counters[wf_alive_counter(b)]};
 }
-// Traversal kernels: 8 KB of LDS stacks per workgroup, 47-50 registers: 8 waves per SIMD.
+__device__ __forceinline__ WfSlots wf_shadow_slots(const WfState &W, int b) { return WfSlots{W.shadow_queue, (int64_t) W.counters[wf_shadow_counter(b)]}; }
+// every slot, grid-stride over workgroups of THREADS: body(path)
+template <int THREADS, class Body>
+__device__ __forceinline__ void wf_for_each_slot(const WfSlots &Q, Body body) {
+    for (int64_t q = (int64_t) blockIdx.x * THREADS + threadIdx.x; q < Q.count; q += (int64_t) gridDim.x * THREADS) body(Q.path(q));
+}
+// Traversal kernels: 8 KB of LDS stacks per workgroup; extend 62 registers, shadow 67: 8 and 7 waves per SIMD.
 // (Tried and dropped: persistent waves whose idle lanes fetch new rays between two traversal rounds -- from a shared
 // queue head the ~10^5 same-address atomics serialise, from a static share per wave the primary rays lose their
 // coherence: 667 -> 1226 us for bounce 0, -5..10 % for the later bounces, +1.1 ms per 4.2 M paths in all.
@@ -62,25 +75,22 @@ __device__ __forceinline__ int64_t wf_count(const TraceArgs &A, const WfState &W
 // the unfinished lanes (the while-while loops run for the slowest lane: 27 % of the VALU lanes busy).  Same hits;
 // 5.6-5.7 ms against 5.3-5.4 ms at 128 k triangles, 8.7 against 8.9 ms at 512 k: the step-wise traversal state
 // (leaf cursor kept across turns) costs the while-while form 5-7 % where both share it, so it was not kept.)
-// FIRST: bounce 0, whose rays are the primary rays (derived from the path index, nothing read); its own instantiation so
-// that the later bounces keep their 47 registers.
-template <bool FIRST>
+// The closest hits of the bounces >= 1 (the primary rays are the packet kernel's, below).
 __global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_kernel(TraceArgs A, WfState W, int b) {
     __shared__ uint32_t s_stack[kWfStackLds * kWfThreads];
-    const int64_t count = wf_count(A, W, b);
-    if (!FIRST && wf_in_tail(A, b, count)) return;
-    for (int64_t q = (int64_t) blockIdx.x * kWfThreads + threadIdx.x; q < count; q += (int64_t) gridDim.x * kWfThreads)
-        wf_extend(A, W, FIRST ? q : (int64_t) W.queue[b & 1][q], s_stack + threadIdx.x, kWfThreads, FIRST ? 0 : 1);
+    const WfSlots Q = wf_alive_slots(A, W, b);
+    if (wf_in_tail(A, b, Q.count)) return;
+    // (a literal 1 for "a later bounce": with b the compiler keeps bounce 0's ray derivation in this kernel)
+    wf_for_each_slot<kWfThreads>(Q, [&](int64_t i) { wf_extend(A, W, i, s_stack + threadIdx.x, kWfThreads, 1); });
 }
-// The closest-hit stage with the WAVE as the unit (epsm_trace_packet.h).  FIRST: the primary rays -- a wave is the samples of one
-// pixel or of a few neighbours.
-// EPSM_TRACE_FUSE_FIRST_HIT: what the lanes of a wave -- at bounce 0 the samples of one pixel or of a few neighbouring ones -- give the
+// ---- the first-hit stage (EPSM_TRACE_FUSE_FIRST_HIT): wave_sum, first_hit_add, first_hit_scatter and the kernel that finishes it ----
+// What the lanes of a wave -- at bounce 0 the samples of one pixel or of a few neighbouring ones -- give the
 // backward pass: every path's grad_d into the wave's share of -sum grad_d, and the first-vertex rows of the paths retired at their
 // first hit.  Lanes on the same triangle are summed first (butterfly over the wave, in up to four turns of "the first lane still
 // owing and everybody on its triangle"), one lane adds the sum; what is left after four turns adds for itself.
 // sum over the wave by six DPP adds (epsm_wave_scatter.h: the total lands in lane 63) + one readlane: no trip through the LDS crossbar
 __device__ __forceinline__ float wave_sum(float v) { return lane63(wave_total_lane63(v)); }
-__device__ __forceinline__ void first_hit_add(float *p, float v) { if (v != 0.f && fabsf(v) < __builtin_inff()) atomicAdd(p, v); }
+__device__ __forceinline__ void first_hit_add(float *p, float v) { if (first_hit_addend_kept(v)) atomicAdd(p, v); }
 __device__ __forceinline__ void first_hit_scatter(const TraceArgs &A, const WfState &W, const WfFirstHit &fh, unsigned wave_index) {
     const int lane = threadIdx.x & 63;
     if (A.fh.grad_o_sum) {
@@ -124,35 +134,41 @@ __device__ __forceinline__ void first_hit_scatter(const TraceArgs &A, const WfSt
         }
     }
 }
-template <bool FIRST>
-__global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_packet_kernel(TraceArgs A, WfState W, int b) {
+__global__ __launch_bounds__(kWfFirstHitSlots) void epsm_wf_first_hit_finish_kernel(TraceArgs A, WfState W) {
+    __shared__ float s_sum[kWfFirstHitSlots / 64][3];
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = wave_sum(W.fh_partial[4 * threadIdx.x + c]);
+    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = v[0]; s_sum[threadIdx.x >> 6][1] = v[1]; s_sum[threadIdx.x >> 6][2] = v[2]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float t = 0.f;
+        for (int w = 0; w < kWfFirstHitSlots / 64; ++w) t += s_sum[w][threadIdx.x];
+        first_hit_add(A.fh.grad_o_sum + threadIdx.x, -t);
+    }
+}
+// ---- (end of the first-hit stage) ----
+
+// The closest hits of the PRIMARY rays, with the wave as the unit (epsm_trace_packet.h): a wave is the samples of one pixel or of a
+// few neighbours.  Every path, whatever is compacted behind this stage.
+__global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_packet_kernel(TraceArgs A, WfState W) {
     __shared__ uint32_t s_stack[kPacketStack * (kWfThreads / 64)];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t count = FIRST ? A.N : wf_count(A, W, b);     // (the primary rays: every path, whatever is compacted behind this stage)
-    if (!FIRST && wf_in_tail(A, b, count)) return;
-    for (int64_t q0 = (int64_t) blockIdx.x * kWfThreads + wv * 64; q0 < count; q0 += (int64_t) gridDim.x * kWfThreads) {     // wave-uniform
+    for (int64_t q0 = (int64_t) blockIdx.x * kWfThreads + wv * 64; q0 < A.N; q0 += (int64_t) gridDim.x * kWfThreads) {     // wave-uniform
         const int64_t q = q0 + lane;
-        const bool has = q < count;
-        const int64_t i = FIRST ? (has ? q : q0) : (int64_t) W.queue[b & 1][has ? q : q0];
-        Ray r;
+        const bool has = q < A.N;
+        const int64_t i = has ? q : q0;
         // EPSM_TRACE_FUSE_FIRST_HIT: the primary rays' stage has ray and hit in registers -- it retires the paths the rule retires at
         // their first vertex itself (first_hit_retires / first_hit_rows: the backward pass of a path without a chain, every path's
         // share of d / d ray.o) and marks their slots; the shade stage passes them by: of 2^24 paths of the clutter scene it shades 2 M.
-        const bool fuse = FIRST && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT);      // (kernel-uniform)
-        WfFirstHit fh;
-        fh.rows.on = false; fh.rows.key[0] = fh.rows.key[1] = fh.rows.key[2] = kNoIndex;
-        fh.rows.val[0] = fh.rows.val[1] = fh.rows.val[2] = fh.gd = zero3<float>();
-        if (FIRST) {
-            PrimaryRay pr;
-            r = path_begin(A, i, false, &pr).ray;
-            if (fuse && has) {
-                float gx, gy;
-                first_hit_pixel_grad(A, i, gx, gy);
-                fh.gd = (pr.dx - pr.ray.d) * gx + (pr.dy - pr.ray.d) * gy;     // epsm.py:255, as tangent_from forms it
-            }
-        } else {
-            const W4 o = W.ray_o[i], d = W.ray_d[i];
-            r.o = xyz(o); r.maxt = u2f(o.w); r.d = xyz(d);
+        const bool fuse = (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) != 0;          // (kernel-uniform)
+        WfFirstHit fh = wf_no_first_hit();
+        PrimaryRay pr;
+        const Ray r = path_begin(A, i, false, &pr).ray;
+        if (fuse && has) {
+            float gx, gy;
+            first_hit_pixel_grad(A, i, gx, gy);
+            fh.gd = (pr.dx - pr.ray.d) * gx + (pr.dy - pr.ray.d) * gy;         // epsm.py:255, as tangent_from forms it
         }
         const TriHit th = packet_intersect(A.S, r, has, s_stack + wv * kPacketStack);
         bool done = false;
@@ -175,31 +191,31 @@ __global__ __launch_bounds__(kWfThreads) void epsm_wf_extend_packet_kernel(Trace
                 atomicAdd(&W.group_counts[chunk / kWfGroup], (uint32_t) __popcll(ma));
             }
         }
-        if (has && !done) {
-            W4 h; h.x = th.hit ? th.tri : kNoIndex; h.y = f2u(th.t); h.z = f2u(th.u); h.w = f2u(th.v);
-            W.hit[i] = h;
-        }
+        if (has && !done) W.hit[i] = wf_hit_pack(th);
     }
 }
 // The rest of the loop of the paths alive into bounce b, once they are few (wf_tail, epsm_trace_wavefront.h).
 __global__ __launch_bounds__(kWfThreads) void epsm_wf_tail_kernel(TraceArgs A, WfState W, int b) {
     __shared__ uint32_t s_stack[kWfStackLds * kWfThreads];
-    const int64_t count = wf_count(A, W, b);
-    if (!wf_in_tail(A, b, count)) return;
-    for (int64_t q = (int64_t) blockIdx.x * kWfThreads + threadIdx.x; q < count; q += (int64_t) gridDim.x * kWfThreads)
-        wf_tail(A, W, (int64_t) W.queue[b & 1][q], b, s_stack + threadIdx.x, kWfThreads);
+    const WfSlots Q = wf_alive_slots(A, W, b);
+    if (!wf_in_tail(A, b, Q.count)) return;
+    wf_for_each_slot<kWfThreads>(Q, [&](int64_t i) { wf_tail(A, W, i, b, s_stack + threadIdx.x, kWfThreads); });
 }
-__global__ __launch_bounds__(kWfFirstHitSlots) void epsm_wf_first_hit_finish_kernel(TraceArgs A, WfState W) {
-    __shared__ float s_sum[kWfFirstHitSlots / 64][3];
-    float v[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = wave_sum(W.fh_partial[4 * threadIdx.x + c]);
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6][0] = v[0]; s_sum[threadIdx.x >> 6][1] = v[1]; s_sum[threadIdx.x >> 6][2] = v[2]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float t = 0.f;
-        for (int w = 0; w < kWfFirstHitSlots / 64; ++w) t += s_sum[w][threadIdx.x];
-        first_hit_add(A.fh.grad_o_sum + threadIdx.x, -t);
+// Every 256-slot chunk of `count` slots, the workgroups (of kWfChunk lanes) taking chunks in turn: flags(chunk, q) gives slot q's
+// bits (kWfAlive | kWfShadow); the number of each among a wave's slots is left in LDS, n[which][wave], and then
+// use(chunk, f, m, n) runs -- f the lane's bits, m the two ballots of its wave.
+template <class Flags, class Use>
+__device__ __forceinline__ void wf_for_each_chunk(int64_t count, Flags flags, Use use) {
+    __shared__ uint32_t s_n[2][kWfChunk / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll 1
+    for (int64_t chunk = blockIdx.x; chunk * kWfChunk < count; chunk += gridDim.x) {           // workgroup-uniform
+        const uint8_t f = flags(chunk, chunk * kWfChunk + threadIdx.x);
+        const unsigned long long m[2] = {__ballot((f & kWfAlive) != 0), __ballot((f & kWfShadow) != 0)};
+        if (lane == 0) { s_n[0][wv] = (uint32_t) __popcll(m[0]); s_n[1][wv] = (uint32_t) __popcll(m[1]); }
+        __syncthreads();
+        use(chunk, f, m, s_n);
+        __syncthreads();                                             // (the counts of this chunk are read before the next one writes its own)
     }
 }
 // (160 registers, 3 waves per SIMD; capped at 128 for 4 waves it spills 96 B/lane and is no faster.)
@@ -208,39 +224,33 @@ __global__ __launch_bounds__(kWfFirstHitSlots) void epsm_wf_first_hit_finish_ker
 // writes cost nothing, each of the two queues 0.6 ms: 65 536 same-address atomics, ~9 ns apiece at the memory
 // side); it leaves a flag per slot and two counts per chunk instead.
 __global__ __launch_bounds__(kWfChunk) void epsm_wf_shade_kernel(TraceArgs A, WfState W, int b) {
-    const int64_t count = wf_count(A, W, b);
-    if ((int64_t) blockIdx.x * kWfChunk >= count || wf_in_tail(A, b, count)) return;           // workgroup-uniform
+    const WfSlots Q = wf_alive_slots(A, W, b);
+    if (wf_in_tail(A, b, Q.count)) return;
     // (A capped grid whose workgroups take chunks in turn, as the compaction does: the launch of a bounce nobody reaches 15 -> 5 us, but
     // a stage whose every chunk has work 1.08 -> 1.19 ms at 2^24 paths -- the hardware's dispatch order balances better.  So the
     // host caps the grid only where the queue is known to be short: behind the first-hit stage's compaction and from bounce 1 on.)
-    __shared__ uint32_t s_n[2][kWfChunk / 64];
-#pragma unroll 1
-    for (int64_t chunk = blockIdx.x; chunk * kWfChunk < count; chunk += gridDim.x) {           // workgroup-uniform
-    const int64_t q = chunk * kWfChunk + threadIdx.x;
-    bool alive = false, shadow = false;
     // EPSM_TRACE_FUSE_FIRST_HIT: the primary rays' stage (packet kernel) has dealt with the paths that end at their first vertex and
     // the survivors come here compacted (kWfPreCompact); without that stage (the host harness) this one does it, wf_shade's `out`
     const bool fuse = b == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && !(A.flags & kWfPreCompact);     // (kernel-uniform)
-    WfFirstHit fh;
-    fh.rows.on = false; fh.rows.key[0] = fh.rows.key[1] = fh.rows.key[2] = kNoIndex;
-    fh.rows.val[0] = fh.rows.val[1] = fh.rows.val[2] = fh.gd = zero3<float>();
-    if (q < count) {
-        wf_shade(A, W, wf_identity(A, b) ? q : (int64_t) W.queue[b & 1][q], b, alive, shadow, fuse ? &fh : nullptr);
-        W.flags[q] = (uint8_t) ((alive ? kWfAlive : 0) | (shadow ? kWfShadow : 0));
-    }
-    if (fuse) first_hit_scatter(A, W, fh, (unsigned) chunk * (kWfChunk / 64) + (threadIdx.x >> 6));   // (all lanes of the wave: the sums run over it)
-    const unsigned long long ma = __ballot(alive), ms = __ballot(shadow);
-    if ((threadIdx.x & 63) == 0) { s_n[0][threadIdx.x >> 6] = (uint32_t) __popcll(ma); s_n[1][threadIdx.x >> 6] = (uint32_t) __popcll(ms); }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        uint32_t n = 0;
+    wf_for_each_chunk(Q.count,
+        [&](int64_t chunk, int64_t q) {
+            bool alive = false, shadow = false;
+            WfFirstHit fh = wf_no_first_hit();
+            if (q < Q.count) {
+                wf_shade(A, W, Q.path(q), b, alive, shadow, fuse ? &fh : nullptr);
+                W.flags[q] = (uint8_t) ((alive ? kWfAlive : 0) | (shadow ? kWfShadow : 0));
+            }
+            if (fuse) first_hit_scatter(A, W, fh, (unsigned) chunk * (kWfChunk / 64) + (threadIdx.x >> 6));   // (all lanes of the wave: the sums run over it)
+            return (uint8_t) ((alive ? kWfAlive : 0) | (shadow ? kWfShadow : 0));
+        },
+        [&](int64_t chunk, uint8_t, const unsigned long long *, const uint32_t (&n_wave)[2][kWfChunk / 64]) {
+            if (threadIdx.x >= 2) return;
+            uint32_t n = 0;
 #pragma unroll
-        for (int w = 0; w < kWfChunk / 64; ++w) n += s_n[threadIdx.x][w];
-        W.chunk_counts[threadIdx.x * W.chunks + chunk] = n;
-        if (n) atomicAdd(&W.group_counts[threadIdx.x * W.groups + chunk / kWfGroup], n);     // (64 adds per address at most)
-    }
-    __syncthreads();                                                 // (the counts of this chunk are read before the next one writes its own)
-    }
+            for (int w = 0; w < kWfChunk / 64; ++w) n += n_wave[threadIdx.x][w];
+            W.chunk_counts[threadIdx.x * W.chunks + chunk] = n;
+            if (n) atomicAdd(&W.group_counts[threadIdx.x * W.groups + chunk / kWfGroup], n);     // (64 adds per address at most)
+        });
 }
 // Exclusive scan of the chunk counts of both queues (<= 65 536 chunks each at 2^24 paths), one workgroup PER QUEUE, two
 // levels: the counts of the GROUPS of 64 chunks (summed by the shade stage) are scanned over the workgroup -- one coalesced
@@ -248,8 +258,14 @@ __global__ __launch_bounds__(kWfChunk) void epsm_wf_shade_kernel(TraceArgs A, Wf
 // added.  Publishes the queue length of the next stage and leaves the group counts zeroed for the next bounce.
 // (One level -- thread t sums a strip of 64 counts, the strips' sums are scanned, the strip is rewritten -- took 100 us for
 // the first bounce of a 2^24-path tile: two passes of strided, dependent loads by two workgroups.)
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t) __shfl_up((int) v, off); if (lane >= off) v += t; }
+    return v;
+}
 __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState W, int b) {
-    const int64_t count = wf_count(A, W, b), n = (count + kWfChunk - 1) / kWfChunk, groups = (n + kWfGroup - 1) / kWfGroup;
+    const int64_t count = wf_alive_slots(A, W, b).count, n = (count + kWfChunk - 1) / kWfChunk, groups = (n + kWfGroup - 1) / kWfGroup;
     if (wf_in_tail(A, b, count)) return;                          // (the counters of the later bounces stay 0: their stages leave at once)
     __shared__ uint32_t s_w[16];
     __shared__ uint32_t s_carry;
@@ -261,9 +277,7 @@ __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState
         const int64_t g = base + threadIdx.x;
         const uint32_t v = g < groups ? gc[g] : 0u;
         if (g < groups) gc[g] = 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t) __shfl_up((int) inc, off); if (lane >= off) inc += t; }
+        const uint32_t inc = wave_inclusive_scan(v);
         if (lane == 63) s_w[wv] = inc;
         __syncthreads();
         uint32_t before = s_carry, all = 0;
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState
         if (threadIdx.x == 0) s_carry += all;
         __syncthreads();
     }
-    if (threadIdx.x == 0) W.counters[which == 0 ? b + 1 : 8 + b] = s_carry;
+    if (threadIdx.x == 0) W.counters[which == 0 ? wf_alive_counter(b + 1) : wf_shadow_counter(b)] = s_carry;
     if (threadIdx.x == 0 && b < 0 && which == 0 && A.fh.survivor_count) *A.fh.survivor_count = s_carry;   // (the caller's copy: EpsmFirstHitBackward)
     constexpr int kBatch = 4;                                     // groups a wave has in flight
     for (int64_t g0 = (int64_t) wv * kBatch; g0 < groups; g0 += 16 * kBatch) {
@@ -287,9 +301,7 @@ __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState
         }
 #pragma unroll
         for (int j = 0; j < kBatch; ++j) {
-            uint32_t inc = v[j];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t) __shfl_up((int) inc, off); if (lane >= off) inc += t; }
+            const uint32_t inc = wave_inclusive_scan(v[j]);
             const int64_t k = (g0 + j) * kWfGroup + lane;
             if (g0 + j < groups && k < n) c[k] = o[j] + inc - v[j];
         }
@@ -302,89 +314,36 @@ __global__ __launch_bounds__(1024) void epsm_wf_scan_kernel(TraceArgs A, WfState
 // (And in round 4: inside its 256-slot chunk, grouped by the triangle the rays LEAVE -- the pixel neighbourhood kept -- slower
 // again, the shade stage's reads lose their coalescing: MEASUREMENTS.md 9.3, profiles/r04_j_tracer_rekey.txt.  Removed.)
 __global__ __launch_bounds__(kWfChunk) void epsm_wf_compact_kernel(TraceArgs A, WfState W, int b) {
-    const int64_t count = wf_count(A, W, b);
-    if (wf_in_tail(A, b, count)) return;
-    for (int64_t chunk = blockIdx.x; chunk * kWfChunk < count; chunk += gridDim.x) {              // workgroup-uniform
-    const int64_t q = chunk * kWfChunk + threadIdx.x;
-    const uint8_t f = q < count ? W.flags[q] : (uint8_t) 0;
-    const uint32_t i = q < count ? (wf_identity(A, b) ? (uint32_t) q : W.queue[b & 1][q]) : 0u;
-    __shared__ uint32_t s_n[2][kWfChunk / 64];
+    const WfSlots Q = wf_alive_slots(A, W, b);
+    if (wf_in_tail(A, b, Q.count)) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long m[2] = {__ballot((f & kWfAlive) != 0), __ballot((f & kWfShadow) != 0)};
-    if (lane == 0) { s_n[0][wv] = (uint32_t) __popcll(m[0]); s_n[1][wv] = (uint32_t) __popcll(m[1]); }
-    __syncthreads();
+    uint32_t i = 0u;                                                 // the slot's path, read beside its flag
+    wf_for_each_chunk(Q.count,
+        [&](int64_t, int64_t q) {
+            i = q < Q.count ? (uint32_t) Q.path(q) : 0u;
+            return q < Q.count ? W.flags[q] : (uint8_t) 0;
+        },
+        [&](int64_t chunk, uint8_t f, const unsigned long long *m, const uint32_t (&n_wave)[2][kWfChunk / 64]) {
 #pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (!((f >> which) & 1)) continue;
-        uint32_t off = W.chunk_counts[which * W.chunks + chunk];
-        for (int w = 0; w < wv; ++w) off += s_n[which][w];
-        off += (uint32_t) __popcll(m[which] & ((1ull << lane) - 1ull));
-        (which == 0 ? W.queue[(b + 1) & 1] : W.shadow_queue)[off] = i;
-        if (b < 0 && which == 0 && A.fh.survivors) A.fh.survivors[off] = i;      // (the caller's copy: EpsmFirstHitBackward)
-    }
-    __syncthreads();
-    }
+            for (int which = 0; which < 2; ++which) {
+                if (!((f >> which) & 1)) continue;
+                uint32_t off = W.chunk_counts[which * W.chunks + chunk];
+                for (int w = 0; w < wv; ++w) off += n_wave[which][w];
+                off += (uint32_t) __popcll(m[which] & ((1ull << lane) - 1ull));
+                (which == 0 ? W.queue[(b + 1) & 1] : W.shadow_queue)[off] = i;
+                if (b < 0 && which == 0 && A.fh.survivors) A.fh.survivors[off] = i;      // (the caller's copy: EpsmFirstHitBackward)
+            }
+        });
 }
 __global__ __launch_bounds__(kWfThreads) void epsm_wf_shadow_kernel(TraceArgs A, WfState W, int b) {
     __shared__ uint32_t s_stack[kWfStackLds * kWfThreads];
-    const int64_t count = (int64_t) W.counters[8 + b];
-    for (int64_t q = (int64_t) blockIdx.x * kWfThreads + threadIdx.x; q < count; q += (int64_t) gridDim.x * kWfThreads)
-        wf_shadow(A, W, (int64_t) W.shadow_queue[q], b, s_stack + threadIdx.x, kWfThreads);
+    wf_for_each_slot<kWfThreads>(wf_shadow_slots(W, b), [&](int64_t i) { wf_shadow(A, W, i, b, s_stack + threadIdx.x, kWfThreads); });
 }
 __global__ __launch_bounds__(256) void epsm_wf_finish_kernel(TraceArgs A, WfState W) {
-    for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < A.N; i += (int64_t) gridDim.x * 256) wf_finish(A, W, i);
+    wf_for_each_slot<256>(WfSlots{nullptr, A.N}, [&](int64_t i) { wf_finish(A, W, i); });
 }
 
 }  // namespace
-
-// Validates the arguments of the tracer entry points and fills the kernel argument block (the common prefix: replay_args_fill).
-static int fill_trace_args(TraceArgs &A, const char *who, const EpsmScene *scene, const EpsmSensor *sensor,
-                           uint32_t seed, int spp, int max_depth, int rr_depth, int64_t path_offset, int64_t N, int K_log,
-                           float *ray_o, float *ray_d, float *ray_dx, float *ray_dy, float *film_pos, float *radiance,
-                           uint8_t *valid, const EpsmRecordOut *recs, uint32_t flags) {
-    auto bad = [&](const char *what) { return fail(EPSM_EINVAL, who, what); };
-    if (const char *why = replay_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return bad(why);
-    if (K_log < 0 || K_log > EPSM_MAX_VERTICES || K_log > (max_depth < 6 ? max_depth : 6))
-        return bad("K_log must be <= min(max_depth, 5)");
-    const bool packed = (flags & EPSM_TRACE_PACKED_LOG) != 0;
-    if (!ray_o || (!packed && (!ray_d || !ray_dx || !ray_dy)) || (K_log > 0 && !recs)) return bad("NULL output");
-    if (packed && ((((uintptr_t) ray_o) & 15) || (K_log > 0 && (!recs[0].packed || !recs[0].pflags || (((uintptr_t) recs[0].packed) & 15)))))
-        return bad("EPSM_TRACE_PACKED_LOG needs 16-byte aligned ray_o (N,12), recs[0].packed and recs[0].pflags");
-    if (packed && K_log > 0) {
-        const int64_t rs = recs[0].ray_stride, ps = recs[0].packed_stride;
-        if (rs < 0 || ps < 0 || (rs & 3) || (ps & 3) || (rs && rs < 12) || (ps && ps < (int64_t) K_log * 32))
-            return bad("EpsmRecordOut.ray_stride / packed_stride must be 0 or multiples of 4 words >= 12 / 32 K_log");
-    }
-    if (flags & ~(uint32_t) (EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | EPSM_TRACE_GRADIENT_ONLY | EPSM_TRACE_GRADIENT_CAUSTIC | EPSM_TRACE_NO_TAIL |
-                             EPSM_TRACE_FUSE_FIRST_HIT))
-        return bad("unknown flag");
-    if (flags & EPSM_TRACE_FUSE_FIRST_HIT) {
-        if (!(flags & EPSM_TRACE_GRADIENT_ONLY) || !packed || K_log < 1) return bad("EPSM_TRACE_FUSE_FIRST_HIT needs EPSM_TRACE_GRADIENT_ONLY and EPSM_TRACE_PACKED_LOG");
-        const EpsmFirstHitBackward *f = recs[0].first_hit;
-        if (!f || !f->grad_img || !f->grad_pos || (f->T > 0 && !f->tri_table) || f->T < 0 || f->V < 0 || f->res < 1 || f->img_width < f->res ||
-            f->img_channels < 5 || (((uintptr_t) f->tri_table) & 15))
-            return bad("EPSM_TRACE_FUSE_FIRST_HIT: recs[0].first_hit needs grad_img (>= 5 channels, img_width >= res >= 1), grad_pos and a 16-byte aligned tri_table");
-        if (path_offset + N > (int64_t) f->res * f->res * spp) return bad("EPSM_TRACE_FUSE_FIRST_HIT: path range exceeds res * res * spp");
-        if (recs[0].shadow && max_depth <= 3) return bad("EPSM_TRACE_FUSE_FIRST_HIT: not with the occluder record (max_depth <= 3)");
-        if ((f->survivors != nullptr) != (f->survivor_count != nullptr)) return bad("EPSM_TRACE_FUSE_FIRST_HIT: survivors and survivor_count come together");
-    }
-    if ((flags & EPSM_TRACE_GRADIENT_CAUSTIC) && !(flags & EPSM_TRACE_GRADIENT_ONLY)) return bad("EPSM_TRACE_GRADIENT_CAUSTIC modifies EPSM_TRACE_GRADIENT_ONLY");
-    if ((flags & EPSM_TRACE_GRADIENT_ONLY) && K_log < 1) return bad("EPSM_TRACE_GRADIENT_ONLY needs a vertex log (K_log >= 1)");
-    A.flags = flags; A.K_log = K_log;
-    A.ray_o = ray_o; A.ray_d = ray_d; A.ray_dx = ray_dx; A.ray_dy = ray_dy;
-    A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
-    for (int k = 0; k < K_log; ++k) {
-        const EpsmRecordOut &r = recs[k];
-        if (packed) { A.rec[k] = r; continue; }
-        if (!r.p0 || !r.p1 || !r.p2 || !r.n0 || !r.n1 || !r.n2 || !r.b0 || !r.b1 || !r.eta || !r.hf || !r.light ||
-            !r.bsdf || !r.active || !r.active_em || !r.ismesh || !r.tri || !r.aux || !r.emit)
-            return bad("NULL pointer in a record (p / normal may be NULL)");
-        A.rec[k] = r;
-    }
-    trace_args_log_strides(A);
-    if (flags & EPSM_TRACE_FUSE_FIRST_HIT) A.fh = *recs[0].first_hit;
-    return EPSM_OK;
-}
 
 extern "C" int epsm_trace_paths(const EpsmScene *scene, const EpsmSensor *sensor,
                                 uint32_t seed, int spp, int max_depth, int rr_depth,
@@ -396,9 +355,9 @@ extern "C" int epsm_trace_paths(const EpsmScene *scene, const EpsmSensor *sensor
     if (scene && sensor && N == 0) return EPSM_OK;
     TraceArgs A;
     if (flags & EPSM_TRACE_FUSE_FIRST_HIT) return fail(EPSM_EINVAL, "epsm_trace_paths: EPSM_TRACE_FUSE_FIRST_HIT is the wavefront form's (epsm_trace_paths_wavefront)");
-    const int rc = fill_trace_args(A, "epsm_trace_paths", scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log,
-                                   ray_o, ray_d, ray_dx, ray_dy, film_pos, radiance, valid, recs, flags);
-    if (rc != EPSM_OK) return rc;
+    if (const char *why = trace_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log, ray_o, ray_d, ray_dx, ray_dy,
+                                          film_pos, radiance, valid, recs, flags))
+        return fail(EPSM_EINVAL, "epsm_trace_paths", why);
     return launch_checked("epsm_trace_paths", epsm_trace_kernel, (N + 127) / 128, 128, stream, A);
 }
 
@@ -412,10 +371,10 @@ extern "C" int epsm_trace_paths_color(const EpsmScene *scene, const EpsmSensor *
     if (!color_sum || n_color < 1 || n_color > 4 || !radiance)
         return fail(EPSM_EINVAL, "epsm_trace_paths_color: need color_sum, radiance and 1 <= n_color <= 4");
     TraceArgs A;
-    static float dummy_rays[12];                               // (the rays are not wanted: fill_trace_args only checks for NULL)
-    const int rc = fill_trace_args(A, "epsm_trace_paths_color", scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 0,
-                                   dummy_rays, dummy_rays, dummy_rays, dummy_rays, film_pos, radiance, valid, nullptr, 0);
-    if (rc != EPSM_OK) return rc;
+    static float dummy_rays[12];                               // (the rays are not wanted: trace_args_fill only checks for NULL)
+    if (const char *why = trace_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 0, dummy_rays, dummy_rays,
+                                          dummy_rays, dummy_rays, film_pos, radiance, valid, nullptr, 0))
+        return fail(EPSM_EINVAL, "epsm_trace_paths_color", why);
     A.ray_o = A.ray_d = A.ray_dx = A.ray_dy = nullptr;
     A.color_sum = color_sum; A.n_color = n_color;
     const hipError_t e = hipMemsetAsync(color_sum, 0, (size_t) N * n_color * 3 * sizeof(float), (hipStream_t) stream);
@@ -434,9 +393,9 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
     epsm_host::err_buf()[0] = 0;
     if (scene && sensor && N == 0) return EPSM_OK;
     TraceArgs A;
-    const int rc = fill_trace_args(A, "epsm_trace_paths_wavefront", scene, sensor, seed, spp, max_depth, rr_depth, path_offset,
-                                   N, K_log, ray_o, ray_d, ray_dx, ray_dy, film_pos, radiance, valid, recs, flags);
-    if (rc != EPSM_OK) return rc;
+    if (const char *why = trace_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log, ray_o, ray_d, ray_dx, ray_dy,
+                                          film_pos, radiance, valid, recs, flags))
+        return fail(EPSM_EINVAL, "epsm_trace_paths_wavefront", why);
     if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < wf_workspace_bytes(N))
         return fail(EPSM_EINVAL, "epsm_trace_paths_wavefront: workspace NULL, not 16-byte aligned or smaller than epsm_trace_workspace_bytes(N)");
     if (N > 0xFFFFFFF0LL) return fail(EPSM_EINVAL, "epsm_trace_paths_wavefront: N must fit the 32-bit queues");
@@ -449,36 +408,37 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
         e = hipMemsetAsync(W.chunk_counts, 0, (size_t) W.chunks * 8, s);
         if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_wavefront", e);
     }
-    auto blocks = [&](int threads) { const int64_t b = (N + threads - 1) / threads; return dim3((unsigned) (b < kWfMaxBlocks ? b : kWfMaxBlocks)); };
+    // a stage: `kernel` over `grid` workgroups of `threads`, on (A, W) and what else it takes (the bounce)
+    auto stage = [&](auto kernel, int64_t grid, int threads, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned) grid), dim3((unsigned) threads), 0, s, A, W, more...);
+    };
+    auto at_most = [](int64_t n, int64_t cap) { return n < cap ? n : cap; };
+    auto blocks = [&](int threads) { return at_most((N + threads - 1) / threads, kWfMaxBlocks); };
     const int depth = path_max_depth(A);
-    const dim3 shade_short((unsigned) (W.chunks < 16384 ? W.chunks : 16384));
-    const dim3 chunks((unsigned) W.chunks), chunk_blocks((unsigned) (W.chunks < kWfMaxChunkBlocks ? W.chunks : kWfMaxChunkBlocks));
-    const int64_t tail_most = N < kWfTailBelow ? N : kWfTailBelow;
-    const dim3 tail_blocks((unsigned) ((tail_most + kWfThreads - 1) / kWfThreads));
+    const int64_t shade_short = at_most(W.chunks, 16384), chunk_blocks = at_most(W.chunks, kWfMaxChunkBlocks);
+    const int64_t tail_blocks = (at_most(N, kWfTailBelow) + kWfThreads - 1) / kWfThreads;
     for (int b = 0; b < depth; ++b) {
         // the queue lengths of bounce b live on the device: every stage is launched for the worst case and its
         // surplus workgroups leave at once (no host round trip between the bounces)
         // (bounces >= 1: the tail first -- it runs once, when the queue has become short, and the stages behind it leave at once)
-        if (b >= 1 && !(A.flags & EPSM_TRACE_NO_TAIL)) hipLaunchKernelGGL(epsm_wf_tail_kernel, tail_blocks, dim3(kWfThreads), 0, s, A, W, b);
+        if (b >= 1 && !(A.flags & EPSM_TRACE_NO_TAIL)) stage(epsm_wf_tail_kernel, tail_blocks, kWfThreads, b);
         if (b == 0) {
-            hipLaunchKernelGGL(epsm_wf_extend_packet_kernel<true>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
+            stage(epsm_wf_extend_packet_kernel, blocks(kWfThreads), kWfThreads);
             if (A.flags & kWfPreCompact) {                       // the survivors of the primary rays' stage, compacted: "bounce -1"
-                hipLaunchKernelGGL(epsm_wf_scan_kernel, dim3(2), dim3(1024), 0, s, A, W, -1);
-                hipLaunchKernelGGL(epsm_wf_compact_kernel, chunk_blocks, dim3(kWfChunk), 0, s, A, W, -1);
+                stage(epsm_wf_scan_kernel, 2, 1024, -1);
+                stage(epsm_wf_compact_kernel, chunk_blocks, kWfChunk, -1);
             }
         }
-        else hipLaunchKernelGGL(epsm_wf_extend_kernel<false>, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
+        else stage(epsm_wf_extend_kernel, blocks(kWfThreads), kWfThreads, b);
         // (the whole grid where every chunk has work -- bounce 0 of an unfused trace --, a capped one where the queue is short)
-        hipLaunchKernelGGL(epsm_wf_shade_kernel, (b == 0 && !(A.flags & kWfPreCompact)) ? chunks : shade_short, dim3(kWfChunk), 0, s, A, W, b);
-        if (b == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && A.fh.grad_o_sum)
-            hipLaunchKernelGGL(epsm_wf_first_hit_finish_kernel, dim3(1), dim3(kWfFirstHitSlots), 0, s, A, W);
-        hipLaunchKernelGGL(epsm_wf_scan_kernel, dim3(2), dim3(1024), 0, s, A, W, b);
-        hipLaunchKernelGGL(epsm_wf_compact_kernel, chunk_blocks, dim3(kWfChunk), 0, s, A, W, b);
-        hipLaunchKernelGGL(epsm_wf_shadow_kernel, blocks(kWfThreads), dim3(kWfThreads), 0, s, A, W, b);
+        stage(epsm_wf_shade_kernel, (b == 0 && !(A.flags & kWfPreCompact)) ? W.chunks : shade_short, kWfChunk, b);
+        if (b == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT) && A.fh.grad_o_sum) stage(epsm_wf_first_hit_finish_kernel, 1, kWfFirstHitSlots);
+        stage(epsm_wf_scan_kernel, 2, 1024, b);
+        stage(epsm_wf_compact_kernel, chunk_blocks, kWfChunk, b);
+        stage(epsm_wf_shadow_kernel, blocks(kWfThreads), kWfThreads, b);
     }
     // (radiance / valid not asked for and the native log: nothing is left to write -- the gradient-only trace of render_backward)
-    if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))
-        hipLaunchKernelGGL(epsm_wf_finish_kernel, blocks(256), dim3(256), 0, s, A, W);
+    if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG)) stage(epsm_wf_finish_kernel, blocks(256), 256);
     e = hipGetLastError();
     if (e != hipSuccess) return epsm_host::hip_fail("epsm_trace_paths_wavefront", e);
     return EPSM_OK;

@@ -53,6 +53,55 @@ inline const char *replay_args_fill(TraceArgs &A, const EpsmScene *scene, const 
     return nullptr;
 }
 
+// The arguments of the tracer's own entry points (epsm_trace_paths, _color, _wavefront), device library and host twin alike:
+// replay_args_fill, then the log, the outputs and the flags.  NULL = fine and A filled, otherwise what is wrong.
+inline const char *trace_args_fill(TraceArgs &A, const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
+                                   int rr_depth, int64_t path_offset, int64_t N, int K_log, float *ray_o, float *ray_d, float *ray_dx,
+                                   float *ray_dy, float *film_pos, float *radiance, uint8_t *valid, const EpsmRecordOut *recs,
+                                   uint32_t flags) {
+    if (const char *why = replay_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return why;
+    if (K_log < 0 || K_log > EPSM_MAX_VERTICES || K_log > (max_depth < 6 ? max_depth : 6))
+        return "K_log must be <= min(max_depth, 5)";
+    const bool packed = (flags & EPSM_TRACE_PACKED_LOG) != 0;
+    if (!ray_o || (!packed && (!ray_d || !ray_dx || !ray_dy)) || (K_log > 0 && !recs)) return "NULL output";
+    if (packed && ((((uintptr_t) ray_o) & 15) || (K_log > 0 && (!recs[0].packed || !recs[0].pflags || (((uintptr_t) recs[0].packed) & 15)))))
+        return "EPSM_TRACE_PACKED_LOG needs 16-byte aligned ray_o (N,12), recs[0].packed and recs[0].pflags";
+    if (packed && K_log > 0) {
+        const int64_t rs = recs[0].ray_stride, ps = recs[0].packed_stride;
+        if (rs < 0 || ps < 0 || (rs & 3) || (ps & 3) || (rs && rs < 12) || (ps && ps < (int64_t) K_log * 32))
+            return "EpsmRecordOut.ray_stride / packed_stride must be 0 or multiples of 4 words >= 12 / 32 K_log";
+    }
+    if (flags & ~(uint32_t) (EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | EPSM_TRACE_GRADIENT_ONLY | EPSM_TRACE_GRADIENT_CAUSTIC | EPSM_TRACE_NO_TAIL |
+                             EPSM_TRACE_FUSE_FIRST_HIT))
+        return "unknown flag";
+    if (flags & EPSM_TRACE_FUSE_FIRST_HIT) {
+        if (!(flags & EPSM_TRACE_GRADIENT_ONLY) || !packed || K_log < 1) return "EPSM_TRACE_FUSE_FIRST_HIT needs EPSM_TRACE_GRADIENT_ONLY and EPSM_TRACE_PACKED_LOG";
+        const EpsmFirstHitBackward *f = recs[0].first_hit;
+        if (!f || !f->grad_img || !f->grad_pos || (f->T > 0 && !f->tri_table) || f->T < 0 || f->V < 0 || f->res < 1 || f->img_width < f->res ||
+            f->img_channels < 5 || (((uintptr_t) f->tri_table) & 15))
+            return "EPSM_TRACE_FUSE_FIRST_HIT: recs[0].first_hit needs grad_img (>= 5 channels, img_width >= res >= 1), grad_pos and a 16-byte aligned tri_table";
+        if (path_offset + N > (int64_t) f->res * f->res * spp) return "EPSM_TRACE_FUSE_FIRST_HIT: path range exceeds res * res * spp";
+        if (recs[0].shadow && max_depth <= 3) return "EPSM_TRACE_FUSE_FIRST_HIT: not with the occluder record (max_depth <= 3)";
+        if ((f->survivors != nullptr) != (f->survivor_count != nullptr)) return "EPSM_TRACE_FUSE_FIRST_HIT: survivors and survivor_count come together";
+    }
+    if ((flags & EPSM_TRACE_GRADIENT_CAUSTIC) && !(flags & EPSM_TRACE_GRADIENT_ONLY)) return "EPSM_TRACE_GRADIENT_CAUSTIC modifies EPSM_TRACE_GRADIENT_ONLY";
+    if ((flags & EPSM_TRACE_GRADIENT_ONLY) && K_log < 1) return "EPSM_TRACE_GRADIENT_ONLY needs a vertex log (K_log >= 1)";
+    A.flags = flags; A.K_log = K_log;
+    A.ray_o = ray_o; A.ray_d = ray_d; A.ray_dx = ray_dx; A.ray_dy = ray_dy;
+    A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
+    for (int k = 0; k < K_log; ++k) {
+        const EpsmRecordOut &r = recs[k];
+        if (packed) { A.rec[k] = r; continue; }
+        if (!r.p0 || !r.p1 || !r.p2 || !r.n0 || !r.n1 || !r.n2 || !r.b0 || !r.b1 || !r.eta || !r.hf || !r.light ||
+            !r.bsdf || !r.active || !r.active_em || !r.ismesh || !r.tri || !r.aux || !r.emit)
+            return "NULL pointer in a record (p / normal may be NULL)";
+        A.rec[k] = r;
+    }
+    trace_args_log_strides(A);
+    if (flags & EPSM_TRACE_FUSE_FIRST_HIT) A.fh = *recs[0].first_hit;
+    return nullptr;
+}
+
 EPSM_HD float finite_or_zero(float x) { return fabsf(x) < __builtin_inff() ? x : 0.f; }   // (a non-finite coefficient adds nothing)
 EPSM_HD F3 finite_or_zero3(F3 v) { return f3(finite_or_zero(v.x), finite_or_zero(v.y), finite_or_zero(v.z)); }
 

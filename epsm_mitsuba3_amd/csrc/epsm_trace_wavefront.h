@@ -34,7 +34,9 @@ EPSM_HD F3 xyz(const W4 &q) { return f3(u2f(q.x), u2f(q.y), u2f(q.z)); }
 constexpr int kWfArrays = 10;                 // 16-byte words per path in the workspace
 constexpr int kWfMaxDepth = 6;                // epsm.py:549
 constexpr int kWfFirstHitSlots = 256;         // EPSM_TRACE_FUSE_FIRST_HIT: partial sums of grad_d, [slot][4] floats behind the counters
-constexpr int kWfCounters = 64;               // uint32 header: [b] = paths alive into bounce b, [8 + b] = shadow rays of bounce b
+constexpr int kWfCounters = 64;               // uint32 header of the workspace: the queue lengths, at
+EPSM_HD int wf_alive_counter(int b) { return b; }          // paths alive into bounce b
+EPSM_HD int wf_shadow_counter(int b) { return 8 + b; }     // visibility rays of bounce b
 constexpr uint32_t kWfOccluder = 1u;          // sh_d.w: the shadow stage also owes the occluder record
 
 struct WfState {                              // device pointers into the workspace
@@ -137,36 +139,23 @@ EPSM_HD PathState wf_load(const WfState &W, int64_t i) {
 //      bounce 0 derive the primary ray from the path index -- sample_rays, ~100 instructions -- instead of one kernel
 //      writing 96 bytes of state per path for the next two to read back: 0.45 ms + 0.2 ms per 2^24 paths)
 
-// ---- stage: extend.  Closest hit of path i's ray, as a resumable job (begin, traversal rounds until done).
-struct WfJob {
-    int64_t i;
-    int phase;                     // shadow stage: 0 = visibility (any hit), 1 = occluder record (closest hit)
-    Traversal T;
-};
-EPSM_HD void wf_extend_begin(const TraceArgs &A, const WfState &W, int64_t i, WfJob &J, int iteration) {
-    Ray r;
-    if (iteration == 0) {
-        r = path_begin(A, i, false).ray;
-    } else {
-        const W4 o = W.ray_o[i], d = W.ray_d[i];
-        r.o = xyz(o); r.maxt = u2f(o.w); r.d = xyz(d);
-    }
-    J.i = i; J.phase = 0;
-    trav_begin(J.T, A.S, r);
-}
-// one round; true when the job is finished (its result is written)
-EPSM_HD bool wf_extend_round(const TraceArgs &A, const WfState &W, WfJob &J, uint32_t *lds, int stride) {
-    if (!trav_done(J.T)) trav_round<false>(J.T, A.S, wf_stack(W, J.i, lds, stride));
-    if (!trav_done(J.T)) return false;
-    const TriHit th = trav_result(J.T, A.S);
+// a ray / a closest hit as the workspace keeps them
+EPSM_HD Ray wf_ray_unpack(const W4 &o, const W4 &d) { Ray r; r.o = xyz(o); r.maxt = u2f(o.w); r.d = xyz(d); return r; }
+EPSM_HD Ray wf_ray(const WfState &W, int64_t i) { return wf_ray_unpack(W.ray_o[i], W.ray_d[i]); }            // path i's next ray
+EPSM_HD Ray wf_shadow_ray(const WfState &W, int64_t i) { return wf_ray_unpack(W.sh_o[i], W.sh_d[i]); }     // its pending visibility ray
+EPSM_HD W4 wf_hit_pack(const TriHit &th) {
     W4 h; h.x = th.hit ? th.tri : kNoIndex; h.y = f2u(th.t); h.z = f2u(th.u); h.w = f2u(th.v);
-    W.hit[J.i] = h;
-    return true;
+    return h;
 }
+EPSM_HD TriHit wf_hit_unpack(const W4 &h) {
+    TriHit th; th.hit = h.x != kNoIndex; th.tri = th.hit ? h.x : 0u; th.t = u2f(h.y); th.u = u2f(h.z); th.v = u2f(h.w);
+    return th;
+}
+
+// ---- stage: extend.  Closest hit of path i's ray at bounce `iteration` (bounce 0: the ray derived from the path index).
 EPSM_HD void wf_extend(const TraceArgs &A, const WfState &W, int64_t i, uint32_t *lds, int stride, int iteration) {
-    WfJob J;
-    wf_extend_begin(A, W, i, J, iteration);
-    while (!wf_extend_round(A, W, J, lds, stride)) {}
+    const Ray r = iteration == 0 ? path_begin(A, i, false).ray : wf_ray(W, i);
+    W.hit[i] = wf_hit_pack(intersect<false>(A.S, r, wf_stack(W, i, lds, stride)));
 }
 
 // Visibility policy of the shade stage: nothing is traced, the questions are written down for the shadow stage.
@@ -193,15 +182,31 @@ struct DeferredVis {
     }
 };
 
-// ---- stage: shade.  Returns through `alive` / `shadow` whether path i goes on to bounce `iteration + 1` / has a
-//      visibility ray pending; the caller compacts.
 // what path i gives the backward pass at its first hit (EPSM_TRACE_FUSE_FIRST_HIT; the caller sums it over the wave and adds it)
 struct WfFirstHit { FirstHitRows rows; F3 gd; };
+EPSM_HD WfFirstHit wf_no_first_hit() {                                   // ... and a path that gives nothing
+    WfFirstHit fh;
+    fh.rows.on = false; fh.rows.key[0] = fh.rows.key[1] = fh.rows.key[2] = kNoIndex;
+    fh.rows.val[0] = fh.rows.val[1] = fh.rows.val[2] = fh.gd = zero3<float>();
+    return fh;
+}
+// an addend of the first-hit sums is kept when it is neither zero nor non-finite (the device's atomics and the host twin's plain sums)
+EPSM_HD bool first_hit_addend_kept(float v) { return v != 0.f && fabsf(v) < __builtin_inff(); }
+
+// A path that ends leaves what finish reads: L, depth, the bounces done (nothing when nobody asked for radiance / valid and the
+// log is the native one: the gradient-only trace)
+EPSM_HD void wf_retire(const TraceArgs &A, const WfState &W, int64_t i, const PathState &s, int done) {
+    if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))
+        W.L[i] = pack4u(s.L, (uint32_t) s.depth | ((uint32_t) done << 16));
+}
+
+// ---- stage: shade.  Returns through `alive` / `shadow` whether path i goes on to bounce `iteration + 1` / has a
+//      visibility ray pending; the caller compacts.
 EPSM_HD void wf_shade(const TraceArgs &A, const WfState &W, int64_t i, int iteration, bool &alive, bool &shadow, WfFirstHit *out = nullptr) {
     DeferredVis vis; vis.pending = false; vis.want_occluder = false; vis.Lr = zero3<float>();
     vis.sr.o = vis.sr.d = zero3<float>(); vis.sr.maxt = 0.f;
-    vis.gd = zero3<float>(); vis.fh_taken = false; vis.fh_enabled = out != nullptr; vis.fh.on = false; vis.fh.key[0] = vis.fh.key[1] = vis.fh.key[2] = kNoIndex;
-    vis.fh.val[0] = vis.fh.val[1] = vis.fh.val[2] = zero3<float>();
+    const WfFirstHit none = wf_no_first_hit();
+    vis.gd = none.gd; vis.fh = none.rows; vis.fh_taken = false; vis.fh_enabled = out != nullptr;
     PathState s;
     const bool fuse = iteration == 0 && (A.flags & EPSM_TRACE_FUSE_FIRST_HIT);
     if (fuse) {
@@ -215,9 +220,7 @@ EPSM_HD void wf_shade(const TraceArgs &A, const WfState &W, int64_t i, int itera
     } else {
         s = iteration == 0 ? path_begin(A, i) : wf_load(W, i);
     }
-    const W4 h = W.hit[i];
-    TriHit th; th.hit = h.x != kNoIndex; th.tri = th.hit ? h.x : 0u; th.t = u2f(h.y); th.u = u2f(h.z); th.v = u2f(h.w);
-    path_bounce(A, i, iteration, s, th, vis);
+    path_bounce(A, i, iteration, s, wf_hit_unpack(W.hit[i]), vis);
     if (out) { out->rows = vis.fh; out->gd = vis.gd; }
     // a path the first-hit stage has dealt with leaves nothing in the log, its rays included (48 bytes x 94 % of the paths of the
     // clutter scene); the others get theirs now -- derived again rather than carried through the bounce in twelve registers
@@ -226,9 +229,7 @@ EPSM_HD void wf_shade(const TraceArgs &A, const WfState &W, int64_t i, int itera
     if (alive) {
         wf_store(W, i, s, iteration + 1);
     } else {                                                             // a path that ends here: only what finish / shadow read
-        // (nothing when nobody asked for radiance / valid and the log is the native one: the gradient-only trace)
-        if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))
-            W.L[i] = pack4u(s.L, (uint32_t) s.depth | ((uint32_t) (iteration + 1) << 16));
+        wf_retire(A, W, i, s, iteration + 1);
         if (vis.want_occluder) W.prev_p[i] = pack4(s.prev_p, 0.f);
     }
     if (vis.pending) {
@@ -240,13 +241,7 @@ EPSM_HD void wf_shade(const TraceArgs &A, const WfState &W, int64_t i, int itera
 }
 
 // ---- stage: shadow.  The visibility ray of path i's emitter sample at bounce `iteration` (any hit), then -- when the
-//      shade stage asked for it -- the occluder record of the first vertex (closest hit); a resumable job like extend.
-EPSM_HD void wf_shadow_begin(const TraceArgs &A, const WfState &W, int64_t i, WfJob &J) {
-    const W4 o = W.sh_o[i], d = W.sh_d[i];
-    Ray sr; sr.o = xyz(o); sr.maxt = u2f(o.w); sr.d = xyz(d);
-    J.i = i; J.phase = 0;
-    trav_begin(J.T, A.S, sr);
-}
+//      shade stage asked for it -- the occluder record of the first vertex (closest hit).
 // ds.p of the first bounce, as logged (per-field array or packed record)
 EPSM_HD F3 wf_logged_light0(const TraceArgs &A, int64_t i) {
     if (A.flags & EPSM_TRACE_PACKED_LOG) {                                 // light = words 22, 23, 28 (include/epsm.h, EpsmPackedLog)
@@ -278,28 +273,13 @@ EPSM_HD Ray wf_occluder_ray(const TraceArgs &A, const WfState &W, int64_t i, F3 
     Ray r2; r2.o = xyz(W.sh_o[i]); r2.d = dd * (1.f / dist); r2.maxt = kInf;
     return r2;
 }
-EPSM_HD bool wf_shadow_round(const TraceArgs &A, const WfState &W, int iteration, WfJob &J, uint32_t *lds, int stride) {
-    const BvhStack st = wf_stack(W, J.i, lds, stride);
-    const int64_t i = J.i;
-    F3 sip, esp;
-    if (J.phase == 0) {
-        if (!trav_done(J.T)) trav_round<true>(J.T, A.S, st);
-        if (!trav_done(J.T)) return false;
-        if (!wf_shadow_resolve(A, W, i, iteration, J.T.best.hit)) return true;
-        J.phase = 1;
-        trav_begin(J.T, A.S, wf_occluder_ray(A, W, i, sip, esp));
-        return false;
-    }
-    if (!trav_done(J.T)) trav_round<false>(J.T, A.S, st);
-    if (!trav_done(J.T)) return false;
-    const Ray r2 = wf_occluder_ray(A, W, i, sip, esp);
-    write_occluder(A.S, A.rec[0].shadow + 4 * i, r2, trav_result(J.T, A.S), sip, esp);
-    return true;
-}
 EPSM_HD void wf_shadow(const TraceArgs &A, const WfState &W, int64_t i, int iteration, uint32_t *lds, int stride) {
-    WfJob J;
-    wf_shadow_begin(A, W, i, J);
-    while (!wf_shadow_round(A, W, iteration, J, lds, stride)) {}
+    const BvhStack st = wf_stack(W, i, lds, stride);
+    const bool occluded = intersect<true>(A.S, wf_shadow_ray(W, i), st).hit;
+    if (!wf_shadow_resolve(A, W, i, iteration, occluded)) return;
+    F3 sip, esp;
+    const Ray r2 = wf_occluder_ray(A, W, i, sip, esp);
+    write_occluder(A.S, A.rec[0].shadow + 4 * i, r2, intersect<false>(A.S, r2, st), sip, esp);
 }
 
 // ---- the tail.  A stage's time has a floor of one traversal's dependent misses (~0.1 ms: every launch starts with cold
@@ -323,9 +303,7 @@ EPSM_HD void wf_tail(const TraceArgs &A, const WfState &W, int64_t i, int b, uin
         const TriHit th = intersect<false>(A.S, s.ray, st);
         path_bounce(A, i, iteration, s, th, vis);
     }
-    // as the shade stage leaves a path that ends: what finish reads
-    if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))
-        W.L[i] = pack4u(s.L, (uint32_t) s.depth | ((uint32_t) iteration << 16));
+    wf_retire(A, W, i, s, iteration);
 }
 
 // A bounce the path never reached: what path_bounce logs for a masked lane (epsm.py:551: inactive zeros).

@@ -51,6 +51,8 @@ EPSM_TRACE_GRADIENT_ONLY = 0x4
 EPSM_TRACE_GRADIENT_CAUSTIC = 0x8
 EPSM_TRACE_NO_TAIL = 0x10
 EPSM_TRACE_FUSE_FIRST_HIT = 0x20
+# the wavefront workspace's header words (csrc/epsm_trace_wavefront.h: wf_alive_counter(b) = b, wf_shadow_counter(b) = 8 + b)
+WF_ALIVE_COUNTER, WF_SHADOW_COUNTER = 0, 8
 
 
 class EpsmMesh(C.Structure):
@@ -1809,7 +1811,7 @@ class Scene:
         if ws is None:
             return None
         c = ws[:64].view(torch.int32).cpu().tolist()
-        return {"alive": c[0:6], "shadow": c[8:14]}
+        return {"alive": c[WF_ALIVE_COUNTER:WF_ALIVE_COUNTER + 6], "shadow": c[WF_SHADOW_COUNTER:WF_SHADOW_COUNTER + 6]}
 
     def _launch_trace(self, sensor: Sensor, seed: int, spp: int, max_depth: int, K: int, lo: int, n: int, rays, film_pos, radiance,
                       valid, recs, flags: int, gradient_only) -> None:

@@ -30,16 +30,11 @@ extern "C" int epsm_trace_paths(const EpsmScene *scene, const EpsmSensor *sensor
                                 int rr_depth, int64_t path_offset, int64_t N, int K_log, float *ray_o, float *ray_d,
                                 float *ray_dx, float *ray_dy, float *film_pos, float *radiance, uint8_t *valid,
                                 const EpsmRecordOut *recs, uint32_t flags, void *) {
+    if (scene && sensor && N == 0) return 0;
     TraceArgs A;
-    memset(&A, 0, sizeof(A));
-    A.flags = flags;
-    A.S = *scene; A.C = *sensor;
-    A.seed = seed; A.spp = spp; A.max_depth = max_depth; A.rr_depth = rr_depth; A.K_log = K_log;
-    A.path_offset = path_offset; A.N = N;
-    A.ray_o = ray_o; A.ray_d = ray_d; A.ray_dx = ray_dx; A.ray_dy = ray_dy;
-    A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
-    for (int k = 0; k < K_log; ++k) A.rec[k] = recs[k];
-    trace_args_log_strides(A);
+    if ((flags & EPSM_TRACE_FUSE_FIRST_HIT) || trace_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log, ray_o, ray_d,
+                                                               ray_dx, ray_dy, film_pos, radiance, valid, recs, flags))
+        return -22;                                                        // (refused as the device library refuses it)
 #pragma omp parallel for schedule(dynamic, 256)
     for (int64_t i = 0; i < N; ++i) {
         uint32_t stack[kBvhStack];
@@ -147,32 +142,28 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
                                           int rr_depth, int64_t path_offset, int64_t N, int K_log, float *ray_o, float *ray_d,
                                           float *ray_dx, float *ray_dy, float *film_pos, float *radiance, uint8_t *valid,
                                           const EpsmRecordOut *recs, uint32_t flags, void *workspace, size_t workspace_bytes, void *) {
-    if (!workspace || workspace_bytes < wf_workspace_bytes(N)) return -22;
+    if (scene && sensor && N == 0) return 0;
     TraceArgs A;
-    memset(&A, 0, sizeof(A));
-    A.flags = flags;
-    A.S = *scene; A.C = *sensor;
-    A.seed = seed; A.spp = spp; A.max_depth = max_depth; A.rr_depth = rr_depth; A.K_log = K_log;
-    A.path_offset = path_offset; A.N = N;
-    A.ray_o = ray_o; A.ray_d = ray_d; A.ray_dx = ray_dx; A.ray_dy = ray_dy;
-    A.film_pos = film_pos; A.radiance = radiance; A.valid = valid;
-    for (int k = 0; k < K_log; ++k) A.rec[k] = recs[k];
-    trace_args_log_strides(A);
-    if (flags & EPSM_TRACE_FUSE_FIRST_HIT) { if (K_log < 1 || !recs[0].first_hit) return -22; A.fh = *recs[0].first_hit; }
+    if (trace_args_fill(A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, K_log, ray_o, ray_d, ray_dx, ray_dy, film_pos,
+                        radiance, valid, recs, flags))
+        return -22;                                                        // (refused as the device library refuses it)
+    if (!workspace || workspace_bytes < wf_workspace_bytes(N)) return -22;
     const WfState W = wf_carve(workspace, N);
     memset(W.counters, 0, kWfCounters * sizeof(uint32_t));
     uint32_t stack[kWfStackLds];
     for (int b = 0; b < path_max_depth(A); ++b) {
-        const int64_t count = b == 0 ? N : (int64_t) W.counters[b];
-        for (int64_t q = 0; q < count; ++q) wf_extend(A, W, b == 0 ? q : (int64_t) W.queue[b & 1][q], stack, 1, b);
+        const int64_t count = b == 0 ? N : (int64_t) W.counters[wf_alive_counter(b)];
+        const auto path = [&](int64_t q) { return b == 0 ? q : (int64_t) W.queue[b & 1][q]; };
+        uint32_t &n_alive = W.counters[wf_alive_counter(b + 1)], &n_shadow = W.counters[wf_shadow_counter(b)];
+        for (int64_t q = 0; q < count; ++q) wf_extend(A, W, path(q), stack, 1, b);
         for (int64_t q = 0; q < count; ++q) {
-            const int64_t i = b == 0 ? q : (int64_t) W.queue[b & 1][q];
+            const int64_t i = path(q);
             bool alive, shadow;
             WfFirstHit fh;
             const bool fuse = b == 0 && (flags & EPSM_TRACE_FUSE_FIRST_HIT);
             wf_shade(A, W, i, b, alive, shadow, fuse ? &fh : nullptr);
             if (fuse) {                                                     // (the device sums over the wave first: epsm_trace.hip, first_hit_scatter)
-                auto add = [](float *p, float v) { if (v != 0.f && fabsf(v) < INFINITY) *p += v; };
+                auto add = [](float *p, float v) { if (first_hit_addend_kept(v)) *p += v; };
                 if (A.fh.grad_o_sum) { add(A.fh.grad_o_sum, -fh.gd.x); add(A.fh.grad_o_sum + 1, -fh.gd.y); add(A.fh.grad_o_sum + 2, -fh.gd.z); }
                 if (fh.rows.on)
                     for (int j = 0; j < 3; ++j) {
@@ -180,10 +171,10 @@ extern "C" int epsm_trace_paths_wavefront(const EpsmScene *scene, const EpsmSens
                         add(p, fh.rows.val[j].x); add(p + 1, fh.rows.val[j].y); add(p + 2, fh.rows.val[j].z);
                     }
             }
-            if (alive) W.queue[(b + 1) & 1][W.counters[b + 1]++] = (uint32_t) i;
-            if (shadow) W.shadow_queue[W.counters[8 + b]++] = (uint32_t) i;
+            if (alive) W.queue[(b + 1) & 1][n_alive++] = (uint32_t) i;
+            if (shadow) W.shadow_queue[n_shadow++] = (uint32_t) i;
         }
-        for (int64_t q = 0; q < (int64_t) W.counters[8 + b]; ++q) wf_shadow(A, W, (int64_t) W.shadow_queue[q], b, stack, 1);
+        for (int64_t q = 0; q < (int64_t) n_shadow; ++q) wf_shadow(A, W, (int64_t) W.shadow_queue[q], b, stack, 1);
     }
     if (A.radiance || A.valid || !(A.flags & EPSM_TRACE_PACKED_LOG))           // as the device entry point
         for (int64_t i = 0; i < N; ++i) wf_finish(A, W, i);

@@ -185,6 +185,42 @@ def test_gpu_wavefront_tracer_equals_one_launch(max_depth, K, tail):
     assert torch.allclose(a.radiance.mean(0), b.radiance.mean(0), rtol=1e-3)
 
 
+def test_gpu_wavefront_walks_take_many_turns():
+    """The capped grids of the wavefront stages at a size where their workgroups come round again: the traversal kernels and the
+    compaction above 2^21 slots (16 384 workgroups of 128, 8 192 of 256), the shade stage of the bounces >= 1 above 16 384 x 256 =
+    4 194 304.  The camera sits inside a closed diffuse box under a small light, so every one of the 512 x 512 x 18 = 4 718 592 paths
+    lives on into bounce 1 and bounce 2; no vertex log (K = 0).  Both forms as in the test above, same thresholds, with the three
+    stages for every bounce and with the tail allowed; the queue lengths show that the second turn was taken."""
+    from _scenes import quad, sensor
+    from epsm_mitsuba3_amd import scene as S
+    dev = torch.device("cuda", 0)
+    res, spp = 512, 18
+    n = res * res * spp
+    h = 2.0
+    bv = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], float)
+    bf = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]])
+    lv, lf = quad(1.9, 0.1, up=False)
+    d = {"type": "scene", "cam": sensor([0.0, -1.5, 0.5], [0.0, 1.0, -0.5], up=(0, 0, 1), res=res, spp=spp),
+         "box": {"type": "mesh", "vertices": bv, "faces": bf, "face_normals": True, "bsdf": {"type": "twosided", "bsdf": {"type": "diffuse"}}},
+         "light": {"type": "mesh", "vertices": lv, "faces": lf, "face_normals": True,
+                   "emitter": {"type": "area", "radiance": {"type": "rgb", "value": 200.0}}}}
+    sc = S.Scene.from_dict(d, device=dev)
+    sc.tracer = "mega"
+    a = sc._trace(0, seed=7, spp=spp, max_depth=3, K=0, lo=0, hi=n)
+    sc.tracer = "wavefront"
+    for tail in (False, True):
+        sc.wavefront_tail = tail
+        b = sc._trace(0, seed=7, spp=spp, max_depth=3, K=0, lo=0, hi=n)
+        torch.cuda.synchronize()
+        if not tail:
+            lengths = sc.wavefront_queue_lengths()
+            print("queue lengths of", n, "paths:", lengths)
+            assert lengths["alive"][1] > 4_194_304, lengths
+        _forms_agree(a, b, n, dev)
+        del b
+    assert float(a.radiance.max()) > 0
+
+
 def test_gpu_wavefront_edge_sizes_and_empty_scene():
     """One path, a ragged handful, and a scene without a single triangle: the queues, chunk counts and the scan of
     the wavefront form at their smallest."""

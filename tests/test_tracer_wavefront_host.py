@@ -259,6 +259,38 @@ def test_packed_record_words_are_where_the_header_says():
     assert seen > n
 
 
+def test_host_twin_refuses_what_the_device_refuses():
+    """Both host entry points check their arguments with the device library's own rule (csrc/epsm_trace_replay.h,
+    trace_args_fill): a K_log above the limit, an unknown flag bit and EPSM_TRACE_GRADIENT_CAUSTIC without
+    EPSM_TRACE_GRADIENT_ONLY are refused; the same call without the fault is traced."""
+    import ctypes as C
+    res, spp, depth = 8, 4, 6
+    sc = _rich_scene(res, spp)
+    lib, n = sc._backend, res * res * spp
+    rays = [torch.empty((n, 3)) for _ in range(4)]
+    film_pos, radiance, valid = torch.empty((n, 2)), torch.full((n, 3), float("nan")), torch.empty((n,), dtype=torch.uint8)
+    recs = (S.EpsmRecordOut * 8)()
+    ws = torch.empty(int(lib.epsm_trace_workspace_bytes(C.c_int64(n))), dtype=torch.uint8)
+    cs = sc.sensors[0].c_struct()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+
+    def call(wavefront, K, flags):
+        args = [C.byref(sc.c_scene), C.byref(cs), C.c_uint32(1), spp, depth, int(sc.rr_depth), C.c_int64(0), C.c_int64(n), K,
+                *map(ptr, rays), ptr(film_pos), ptr(radiance), ptr(valid), C.c_void_p(C.addressof(recs)), C.c_uint32(flags)]
+        if wavefront:
+            return lib.epsm_trace_paths_wavefront(*args, ptr(ws), C.c_size_t(ws.numel()), None)
+        return lib.epsm_trace_paths(*args, None)
+
+    for wavefront in (False, True):
+        assert call(wavefront, depth + 1, 0) != 0                                   # K_log > min(max_depth, 6)
+        assert call(wavefront, 0, 0x40) != 0                                        # no such flag
+        assert call(wavefront, 0, S.EPSM_TRACE_GRADIENT_CAUSTIC) != 0               # modifies a flag that is not set
+        assert bool(torch.isnan(radiance).all())                                    # nothing was traced
+        assert call(wavefront, 0, 0) == 0
+        assert bool(torch.isfinite(radiance).all()) and float(radiance.max()) > 0
+        radiance.fill_(float("nan"))
+
+
 @pytest.mark.parametrize("lo,hi", [(0, 16 * 16 * 8), (100, 1001)])
 def test_wavefront_equals_one_launch_on_the_deep_chain(lo, hi):
     """The tree whose walk fills the traversal stack (tests/_scenes.py chain_scene: peak 47 of 48 entries): the one-launch form
