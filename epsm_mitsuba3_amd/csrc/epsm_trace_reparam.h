@@ -185,6 +185,18 @@ struct Warp {
     Aux a[kMaxAux];
 };
 struct ReparamCfg { int max_depth, rays; float kappa, exponent; uint32_t flags; };      // flags: EPSM_REPARAM_* (epsm_trace.h)
+// The pass's own arguments behind replay_args_fill, device library and host twin alike: NULL = fine and cfg filled, otherwise
+// what is wrong.
+inline const char *reparam_cfg_fill(ReparamCfg &cfg, const EpsmScene *scene, int reparam_max_depth, int reparam_rays, float kappa,
+                                    float exponent, uint32_t flags) {
+    if (reparam_rays < 1 || reparam_rays > kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
+        return "need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0";
+    if (flags & ~EPSM_REPARAM_ANTITHETIC) return "unknown flag";
+    // (this pass's own rule: there is nothing to move, and its kernels have not been tried on a scene without geometry)
+    if (scene->n_triangles <= 0) return "the scene has no triangles";
+    cfg.max_depth = reparam_max_depth; cfg.rays = reparam_rays; cfg.kappa = kappa; cfg.exponent = exponent; cfg.flags = flags;
+    return nullptr;
+}
 
 // Boundary term of a hit (mesh.cpp:832-887; rectangle.cpp:320-321 for the tessellated rectangles)
 EPSM_HD float boundary_test(const EpsmScene &S, const TriHit &th, F3 ray_d) {
@@ -425,6 +437,18 @@ struct Vertex {
 };
 EPSM_HD void vertex_clear(Vertex &v) { v.valid = false; v.escaped = false; v.L_in = v.L_after = v.Le = v.Lr_dir = zero3<float>(); v.active_em = false; v.bs_valid = false; v.depth = 0; }
 
+// Which rays get a warp beside the ray into a valid vertex and the camera ray -- asked by both passes, so that request n of
+// path i is the same warp in both.
+EPSM_HD bool nonzero3(F3 a) { return a.x != 0.f || a.y != 0.f || a.z != 0.f; }
+// a ray that left the scene towards an environment emitter carries that emitter's radiance: its warp's divergence multiplies it
+// and its direction moves the lookup (prb_reparam.py:341-358 reparameterises every ray before it is known to hit).  (The camera
+// ray has its own warp: prev == nullptr.)
+EPSM_HD bool escaped_warp(const EpsmScene &S, const ReparamCfg &cfg, const Vertex *prev, const Vertex &cur) {
+    return cur.escaped && prev && has_environment(S) && cur.depth < cfg.max_depth && nonzero3(cur.Le);
+}
+// the emitter ray of a vertex whose emitter sample added something (prb_reparam.py:394-411)
+EPSM_HD bool emitter_warp(const ReparamCfg &cfg, const Vertex &cur) { return cur.active_em && cur.depth + 1 < cfg.max_depth && nonzero3(cur.Lr_dir); }
+
 // path_bounce observer: copies what the bounce computed
 struct Capture {
     Vertex *out;
@@ -439,6 +463,45 @@ struct Capture {
         v.wo_world = to_world(si, bs.wo);
     }
 };
+
+// The vertex walk of both passes: path i replays under the primal seed through path_bounce, three Vertex records go round,
+// and vertex j - 1's step runs when vertex j is known -- visit(prev, cur, next, j) for j = 1 .. max_depth with cur = vertex
+// j - 1 (slots (j - 2, j - 1, j) mod 3; prev == nullptr at the first vertex, *next cleared behind the last bounce).  cur may be
+// invalid (a dead path, or a ray that left the scene: cur.escaped).  `radiance_i`: L of the primal pass, from which the
+// radiance still to come before / after a vertex's own terms is counted down (L_in, L_after: prb_reparam.py:435-436).
+// `pr`: the camera ray, there before the first visit.  Returns whether the camera ray reached a vertex.
+template <class Visit>
+EPSM_HD bool walk_vertices(const TraceArgs &A, int64_t i, const BvhStack &st, const float *radiance_i, PrimaryRay &pr, Visit &&visit) {
+    PathState s = path_begin(A, i, false, &pr);
+    InlineVis vis{st};
+    Vertex v[3];
+    for (int k = 0; k < 3; ++k) vertex_clear(v[k]);
+    F3 L_run = ld3(radiance_i);
+    const int max_depth = path_max_depth(A);
+    bool first_valid = false;
+    for (int j = 0; j <= max_depth; ++j) {
+        Vertex &nx = v[j % 3];
+        vertex_clear(nx);
+        if (j < max_depth) {
+            TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
+            const bool was_active = s.active;
+            if (s.active) th = intersect<false>(A.S, s.ray, st);
+            nx.ray = s.ray; nx.th = th; nx.beta = s.beta; nx.depth = s.depth;
+            Capture cap{&nx};
+            path_bounce(A, i, j, s, th, vis, cap);
+            nx.valid = nx.valid && was_active;
+            nx.escaped = was_active && !th.hit;
+            nx.L_in = L_run;
+            L_run = L_run - nx.Le - nx.Lr_dir;
+            nx.L_after = L_run;
+        }
+        if (j == 0) continue;
+        const Vertex &cur = v[(j - 1) % 3];
+        if (j == 1) first_valid = cur.valid;
+        visit(j >= 2 ? &v[(j - 2) % 3] : nullptr, cur, &nx, j);
+    }
+    return first_valid;
+}
 
 // The inputs of one dual evaluation of eval_lo, by index: d', d_em', P0, P1, P2, N0, N1, N2
 enum { kInD = 0, kInDem = 1, kInP = 2, kInN = 5, kInputs = 8 };
@@ -591,37 +654,40 @@ struct ReparamArgs {
     GradOut G;
 };
 
-// d loss / d film position -> d loss / d reparameterised primary direction (common.py:405-418: the position is the
-// projection of ray.o + d' by sensor.sample_direction; perspective.cpp's near plane is affine in the film position)
-EPSM_HD F3 film_to_direction(const EpsmSensor &C, const PrimaryRay &pr, float gx, float gy) {
+// The film position as a function of the primary direction (common.py:405-418: the position is the projection of ray.o + d' by
+// sensor.sample_direction; perspective.cpp's near plane is affine in the film position): what its derivative needs, both ways
+struct CameraFrame {
+    F3 c0, c1, c2;               // the camera axes in world space (the columns of to_world)
+    F3 q;                        // ray.o + d in camera space (orthonormal to_world)
+    float s;                     // [u, v] = q.xy * s = base.xy + px * dx.xy + py * dy.xy on the near plane
+    float a, b, c, d, idet;      // A = [dx.xy dy.xy] = [a b; c d] and 1 / det A
+};
+EPSM_HD CameraFrame camera_frame(const EpsmSensor &C, const PrimaryRay &pr) {
+    CameraFrame f;
     const float *W = C.to_world;
-    const F3 c0 = f3(W[0], W[4], W[8]), c1 = f3(W[1], W[5], W[9]), c2 = f3(W[2], W[6], W[10]);    // columns = camera axes in world space
+    f.c0 = f3(W[0], W[4], W[8]); f.c1 = f3(W[1], W[5], W[9]); f.c2 = f3(W[2], W[6], W[10]);
     const F3 origin = f3(W[3], W[7], W[11]);
     const F3 r = (pr.ray.o - origin) + pr.ray.d;
-    const F3 q = f3(dot(c0, r), dot(c1, r), dot(c2, r));                    // camera space (orthonormal to_world)
+    f.q = f3(dot(f.c0, r), dot(f.c1, r), dot(f.c2, r));
     const F3 base = xform_point(C.sample_to_camera, f3(0.f, 0.f, 0.f));
-    const float s = base.z / q.z;
-    // [u, v] = q.xy * s = base.xy + px * dx.xy + py * dy.xy   ->   h = A^-T g with A = [dx.xy dy.xy]
-    const float a = C.dx[0], b = C.dy[0], c = C.dx[1], d = C.dy[1], idet = 1.f / (a * d - b * c);
-    const float hx = (d * gx - c * gy) * idet, hy = (-b * gx + a * gy) * idet;
-    const F3 gq = f3(s * hx, s * hy, -(q.x * hx + q.y * hy) * s / q.z);
-    return c0 * gq.x + c1 * gq.y + c2 * gq.z;
+    f.s = base.z / f.q.z;
+    f.a = C.dx[0]; f.b = C.dy[0]; f.c = C.dx[1]; f.d = C.dy[1]; f.idet = 1.f / (f.a * f.d - f.b * f.c);
+    return f;
 }
-
+// d loss / d film position -> d loss / d reparameterised primary direction: h = A^-T g, then through q.xy * s
+EPSM_HD F3 film_to_direction(const EpsmSensor &C, const PrimaryRay &pr, float gx, float gy) {
+    const CameraFrame f = camera_frame(C, pr);
+    const float hx = (f.d * gx - f.c * gy) * f.idet, hy = (-f.b * gx + f.a * gy) * f.idet;
+    const F3 gq = f3(f.s * hx, f.s * hy, -(f.q.x * hx + f.q.y * hy) * f.s / f.q.z);
+    return f.c0 * gq.x + f.c1 * gq.y + f.c2 * gq.z;
+}
 // Transpose of film_to_direction: the tangent of the reparameterised primary direction -> that of the film position (pixels)
 EPSM_HD void direction_to_film(const EpsmSensor &C, const PrimaryRay &pr, F3 td, float &fx, float &fy) {
-    const float *W = C.to_world;
-    const F3 c0 = f3(W[0], W[4], W[8]), c1 = f3(W[1], W[5], W[9]), c2 = f3(W[2], W[6], W[10]);
-    const F3 origin = f3(W[3], W[7], W[11]);
-    const F3 r = (pr.ray.o - origin) + pr.ray.d;
-    const F3 q = f3(dot(c0, r), dot(c1, r), dot(c2, r));
-    const F3 base = xform_point(C.sample_to_camera, f3(0.f, 0.f, 0.f));
-    const float s = base.z / q.z;
-    const float a = C.dx[0], b = C.dy[0], c = C.dx[1], d = C.dy[1], idet = 1.f / (a * d - b * c);
-    const F3 tq = f3(dot(c0, td), dot(c1, td), dot(c2, td));
-    const float th = tq.z * s / q.z;
-    const float hx = s * tq.x - q.x * th, hy = s * tq.y - q.y * th;
-    fx = (d * hx - b * hy) * idet; fy = (-c * hx + a * hy) * idet;
+    const CameraFrame f = camera_frame(C, pr);
+    const F3 tq = f3(dot(f.c0, td), dot(f.c1, td), dot(f.c2, td));
+    const float th = tq.z * f.s / f.q.z;
+    const float hx = f.s * tq.x - f.q.x * th, hy = f.s * tq.y - f.q.y * th;
+    fx = (f.d * hx - f.b * hy) * f.idet; fy = (-f.c * hx + f.a * hy) * f.idet;
 }
 
 // What happens to a warp once its ray and the adjoints of its direction / divergence are known.
@@ -640,18 +706,32 @@ struct InlineSink {
         if (ftri != kNoIndex) add_follow_point(S, G, ftri, fb1, fb2, g_o);
     }
 };
-// QueueSink: the request is written for the second stage (epsm_trace_reparam.hip), the n-th of path i at req[n * N + i].
+// On the device a warp is a REQUEST for the second stage (epsm_trace_reparam.hip): the same eight things; gdir / gdiv hold the
+// adjoints on the way in (backward pass) or the tangents d', div' on the way back (forward pass).
 struct alignas(16) WarpReq { float o[3], gdiv, d[3], em_inv_dist, gdir[3], fb1; uint32_t ftri; float fb2, pad0, pad1; };
 constexpr int kMaxReq = 1 + 2 * 6;           // the camera ray + two warps per vertex (epsm.py:549: at most six vertices)
-struct QueueSink {
+EPSM_HD WarpReq make_request(F3 o, F3 d, F3 g_dir, float g_div, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
+    WarpReq q;
+    q.o[0] = o.x; q.o[1] = o.y; q.o[2] = o.z; q.gdiv = g_div; q.d[0] = d.x; q.d[1] = d.y; q.d[2] = d.z; q.em_inv_dist = em_inv_dist;
+    q.gdir[0] = g_dir.x; q.gdir[1] = g_dir.y; q.gdir[2] = g_dir.z; q.fb1 = fb1; q.ftri = ftri; q.fb2 = fb2; q.pad0 = q.pad1 = 0.f;
+    return q;
+}
+// the n-th request of path i of a tile of N paths: n-major, so that neighbouring lanes hold the same call of neighbouring paths
+template <class Req> EPSM_HD Req &request_slot(Req *req, int64_t N, int n, int64_t i) { return req[(int64_t) n * N + i]; }
+// The requests of path i in the order its walk asks for them (what the three device sinks are): next() is the slot of the
+// following one, nullptr past kMaxReq -- such a warp is dropped (backward) or the identity (forward).
+struct RequestCursor {
     WarpReq *req; int64_t N, i; int n;
-    EPSM_HD void warp(F3 o, F3 d, F3 g_dir, float g_div, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
-        if (n >= kMaxReq) return;
-        WarpReq q;
-        q.o[0] = o.x; q.o[1] = o.y; q.o[2] = o.z; q.gdiv = g_div; q.d[0] = d.x; q.d[1] = d.y; q.d[2] = d.z; q.em_inv_dist = em_inv_dist;
-        q.gdir[0] = g_dir.x; q.gdir[1] = g_dir.y; q.gdir[2] = g_dir.z; q.fb1 = fb1; q.ftri = ftri; q.fb2 = fb2; q.pad0 = q.pad1 = 0.f;
-        req[(int64_t) n * N + i] = q;
+    EPSM_HD WarpReq *next() {
+        if (n >= kMaxReq) return nullptr;
         n += 1;
+        return &request_slot(req, N, n - 1, i);
+    }
+};
+// QueueSink: the request is written with the adjoints of its direction / divergence
+struct QueueSink : RequestCursor {
+    EPSM_HD void warp(F3 o, F3 d, F3 g_dir, float g_div, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
+        if (WarpReq *q = next()) *q = make_request(o, d, g_dir, g_div, ftri, fb1, fb2, em_inv_dist);
     }
 };
 
@@ -693,7 +773,7 @@ EPSM_HD void differential(const ReparamArgs &R, Sink &sink, const Vertex *prev, 
         sink.warp(cur.ray.o, cur.ray.d, g_dir, dot(dL, cur.L_in) /* (Le + Lr_dir + Lr_ind) has the value L_in */, prev->th.tri, prev->th.u, prev->th.v, 0.f);
     // ---- the emitter ray (prb_reparam.py:394-411): em_ray.d = normalize(ds.p - o) with o glued to this triangle
     //      (si_cur_follow.spawn_ray_to)
-    if (cur.active_em && cur.depth + 1 < R.cfg.max_depth && (cur.Lr_dir.x != 0.f || cur.Lr_dir.y != 0.f || cur.Lr_dir.z != 0.f)) {
+    if (emitter_warp(R.cfg, cur)) {
         float dist;
         const Ray er = spawn_ray_to(c, cur.es.p, dist);
         sink.warp(er.o, er.d, f3(g[3], g[4], g[5]), dot(dL, cur.Lr_dir), cur.th.tri, cur.th.u, cur.th.v, 1.f / dist);
@@ -704,60 +784,30 @@ EPSM_HD void differential(const ReparamArgs &R, Sink &sink, const Vertex *prev, 
 template <class Sink>
 EPSM_HD void reparam_one_path(const ReparamArgs &R, int64_t i, const BvhStack &st, Sink &sink) {
     const TraceArgs &A = R.A;
-    const int64_t widx = A.path_offset + i;
-    PathState s = path_begin(A, i, false);
     const F3 dL = ld3(R.adj_radiance + 3 * i);
-    // ---- the camera ray: one warp serves sample_rays (film position + det, common.py:405-418) and the first vertex
     PrimaryRay pr;
-    { Pcg32 r2 = seed_sampler(A.seed, (uint32_t) widx); pr = sample_primary_ray(A.C, widx, A.spp, r2); }
-    const F3 g_film = film_to_direction(A.C, pr, R.adj_film[3 * i], R.adj_film[3 * i + 1]);
+    // ---- the camera ray: one warp serves sample_rays (film position + det, common.py:405-418) and the first vertex, whose
+    //      direction adjoint it adds (g_first; the environment's where the ray hit nothing).  g_film is formed at the first
+    //      visit (there is one: max_depth >= 1), once, for whichever of the two places asks for that warp; formed in both,
+    //      the path kernel's scratch grows by 96 bytes per lane (MEASUREMENTS.md 26).
+    F3 g_film = zero3<float>();
     const float g_det_film = R.adj_film[3 * i + 2];
-    F3 g_first = zero3<float>();
-    InlineVis vis{st};
-    Vertex v[3];
-    for (int k = 0; k < 3; ++k) vertex_clear(v[k]);
-    F3 L_run = ld3(R.radiance + 3 * i);
-    const int max_depth = path_max_depth(A);
-    bool primary_done = false;
-    // vertex j's step runs when vertex j+1 is known: slots (j-1, j, j+1) mod 3
-    for (int j = 0; j <= max_depth; ++j) {
-        Vertex &nx = v[j % 3];
-        vertex_clear(nx);
-        if (j < max_depth) {
-            TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
-            const bool was_active = s.active;
-            if (s.active) th = intersect<false>(A.S, s.ray, st);
-            nx.ray = s.ray; nx.th = th; nx.beta = s.beta; nx.depth = s.depth;
-            Capture cap{&nx};
-            path_bounce(A, i, j, s, th, vis, cap);
-            nx.valid = nx.valid && was_active;
-            nx.escaped = was_active && !th.hit;
-            nx.L_in = L_run;
-            L_run = L_run - nx.Le - nx.Lr_dir;
-            nx.L_after = L_run;
-        }
-        if (j == 0) continue;
-        const Vertex &cur = v[(j - 1) % 3];
-        const Vertex *prev = j >= 2 ? &v[(j - 2) % 3] : nullptr;
-        if (!cur.valid) {
-            // a dead path: every term is zero.  A ray that left the scene towards an environment emitter carries that emitter's
-            // radiance: its warp's divergence multiplies it and its direction moves the lookup (prb_reparam.py:341-358
-            // reparameterises every ray before it is known to hit).  (The camera ray: below.)
-            if (cur.escaped && prev && has_environment(A.S) && cur.depth < R.cfg.max_depth && (cur.Le.x != 0.f || cur.Le.y != 0.f || cur.Le.z != 0.f)) {
+    const bool hit = walk_vertices(A, i, st, R.radiance + 3 * i, pr, [&](const Vertex *prev, const Vertex &cur, const Vertex *next, int j) EPSM_LAMBDA {
+        if (j == 1) g_film = film_to_direction(A.C, pr, R.adj_film[3 * i], R.adj_film[3 * i + 1]);
+        if (!cur.valid) {                                                  // a dead path: every term is zero but an escaped ray's
+            if (escaped_warp(A.S, R.cfg, prev, cur)) {
                 F3 g[3];
                 const F3 L0 = env_eval_grad(A.S, cur.ray.d, g);            // Le = beta mis L(d): d Le / d d = Le / L * grad L, per channel
                 const F3 w = f3(L0.x > 0.f ? dL.x * cur.Le.x / L0.x : 0.f, L0.y > 0.f ? dL.y * cur.Le.y / L0.y : 0.f, L0.z > 0.f ? dL.z * cur.Le.z / L0.z : 0.f);
                 sink.warp(cur.ray.o, cur.ray.d, g[0] * w.x + g[1] * w.y + g[2] * w.z, dot(dL, cur.L_in), prev->th.tri, prev->th.u, prev->th.v, 0.f);
             }
-            continue;
+            return;
         }
-        differential(R, sink, prev, cur, &nx, dL, &g_first);
-        if (j == 1 && R.cfg.max_depth > 0) {
-            sink.warp(pr.ray.o, pr.ray.d, g_film + g_first, g_det_film, kNoIndex, 0.f, 0.f, 0.f);
-            primary_done = true;
-        }
-    }
-    if (!primary_done && R.cfg.max_depth > 0) {                            // the camera ray hit nothing: the film's term, and the
+        F3 g_first = zero3<float>();
+        differential(R, sink, prev, cur, next, dL, &g_first);
+        if (j == 1 && R.cfg.max_depth > 0) sink.warp(pr.ray.o, pr.ray.d, g_film + g_first, g_det_film, kNoIndex, 0.f, 0.f, 0.f);
+    });
+    if (!hit && R.cfg.max_depth > 0) {                                     // the camera ray hit nothing: the film's term, and the
         F3 g_env = zero3<float>();                                         // environment's radiance along the reparameterised ray
         if (has_environment(A.S)) {
             F3 g[3];
@@ -774,7 +824,8 @@ EPSM_HD void reparam_one_path(const ReparamArgs &R, int64_t i, const BvhStack &s
 //   InlineFwdSink  traced and evaluated on the spot (the host build)
 //   RecordSink     stage 1 of the device: the request is written (ray, glued origin, em_inv_dist), nothing is evaluated
 //   ReadSink       stage 3 of the device: the tangents stage 2 left in the request (gdir, gdiv) are read back
-// Requests are numbered as QueueSink numbers them, so every warp draws the auxiliary rays the backward pass draws.
+// Both passes ride walk_vertices and ask for a vertex's warps under the same predicates in the same order, and the device sinks
+// are one RequestCursor: request n of path i is the same warp in both, so every warp draws the auxiliary rays the backward draws.
 // ---------------------------------------------------------------------------
 struct ReparamFwdArgs {
     TraceArgs A;
@@ -794,29 +845,19 @@ struct InlineFwdSink {
         return warp_forward(S, T, W, t_o, em_inv_dist);
     }
 };
-struct RecordSink {
+EPSM_HD WarpTan identity_warp() { WarpTan r; r.dir = zero3<float>(); r.div = 0.f; return r; }     // no reparameterisation: nothing moves
+struct RecordSink : RequestCursor {
     static constexpr bool kEval = false;
-    WarpReq *req; int64_t N, i; int n;
     EPSM_HD WarpTan warp(F3 o, F3 d, uint32_t ftri, float fb1, float fb2, float em_inv_dist) {
-        WarpTan r; r.dir = zero3<float>(); r.div = 0.f;
-        if (n >= kMaxReq) return r;
-        WarpReq q;
-        q.o[0] = o.x; q.o[1] = o.y; q.o[2] = o.z; q.gdiv = 0.f; q.d[0] = d.x; q.d[1] = d.y; q.d[2] = d.z; q.em_inv_dist = em_inv_dist;
-        q.gdir[0] = q.gdir[1] = q.gdir[2] = 0.f; q.fb1 = fb1; q.ftri = ftri; q.fb2 = fb2; q.pad0 = q.pad1 = 0.f;
-        req[(int64_t) n * N + i] = q;
-        n += 1;
-        return r;
+        if (WarpReq *q = next()) *q = make_request(o, d, zero3<float>(), 0.f, ftri, fb1, fb2, em_inv_dist);
+        return identity_warp();
     }
 };
-struct ReadSink {
+struct ReadSink : RequestCursor {
     static constexpr bool kEval = true;
-    const WarpReq *req; int64_t N, i; int n;
     EPSM_HD WarpTan warp(F3, F3, uint32_t, float, float, float) {
-        WarpTan r; r.dir = zero3<float>(); r.div = 0.f;
-        if (n >= kMaxReq) return r;
-        const WarpReq &q = req[(int64_t) n * N + i];
-        r.dir = f3(q.gdir[0], q.gdir[1], q.gdir[2]); r.div = q.gdiv;
-        n += 1;
+        WarpTan r = identity_warp();
+        if (const WarpReq *q = next()) { r.dir = f3(q->gdir[0], q->gdir[1], q->gdir[2]); r.div = q->gdiv; }
         return r;
     }
 };
@@ -835,13 +876,12 @@ EPSM_HD void differential_forward(const ReparamFwdArgs &R, Sink &sink, const Ver
     const EpsmMesh m = S.meshes[c.mesh];
     TanSeeds sd;
     for (int k = 0; k < kInputs; ++k) { sd.on[k] = false; sd.t[k] = zero3<float>(); }
-    WarpTan tin; tin.dir = zero3<float>(); tin.div = 0.f;
-    WarpTan tem = tin;
+    WarpTan tin = identity_warp(), tem = identity_warp();
     if (!first && cur.depth < R.cfg.max_depth) {
         tin = sink.warp(cur.ray.o, cur.ray.d, prev->th.tri, prev->th.u, prev->th.v, 0.f);
         sd.on[kInD] = true;
     }
-    const bool em = cur.active_em && cur.depth + 1 < R.cfg.max_depth && (cur.Lr_dir.x != 0.f || cur.Lr_dir.y != 0.f || cur.Lr_dir.z != 0.f);
+    const bool em = emitter_warp(R.cfg, cur);
     if (em) {
         float dist;
         const Ray er = spawn_ray_to(c, cur.es.p, dist);
@@ -878,40 +918,13 @@ EPSM_HD void differential_forward(const ReparamFwdArgs &R, Sink &sink, const Ver
 template <class Sink>
 EPSM_HD void reparam_forward_one_path(const ReparamFwdArgs &R, int64_t i, const BvhStack &st, Sink &sink) {
     const TraceArgs &A = R.A;
-    const int64_t widx = A.path_offset + i;
-    PathState s = path_begin(A, i, false);
     PrimaryRay pr;
-    { Pcg32 r2 = seed_sampler(A.seed, (uint32_t) widx); pr = sample_primary_ray(A.C, widx, A.spp, r2); }
     F3 dLo = zero3<float>();
-    WarpTan cam; cam.dir = zero3<float>(); cam.div = 0.f;
-    InlineVis vis{st};
-    Vertex v[3];
-    for (int k = 0; k < 3; ++k) vertex_clear(v[k]);
-    F3 L_run = ld3(R.radiance + 3 * i);
-    const int max_depth = path_max_depth(A);
-    bool primary_done = false;
-    for (int j = 0; j <= max_depth; ++j) {
-        Vertex &nx = v[j % 3];
-        vertex_clear(nx);
-        if (j < max_depth) {
-            TriHit th; th.hit = false; th.tri = 0; th.t = kInf; th.u = th.v = 0.f;
-            const bool was_active = s.active;
-            if (s.active) th = intersect<false>(A.S, s.ray, st);
-            nx.ray = s.ray; nx.th = th; nx.beta = s.beta; nx.depth = s.depth;
-            Capture cap{&nx};
-            path_bounce(A, i, j, s, th, vis, cap);
-            nx.valid = nx.valid && was_active;
-            nx.escaped = was_active && !th.hit;
-            nx.L_in = L_run;
-            L_run = L_run - nx.Le - nx.Lr_dir;
-            nx.L_after = L_run;
-        }
-        if (j == 0) continue;
-        const Vertex &cur = v[(j - 1) % 3];
-        const Vertex *prev = j >= 2 ? &v[(j - 2) % 3] : nullptr;
+    WarpTan cam = identity_warp();
+    const bool hit = walk_vertices(A, i, st, R.radiance + 3 * i, pr, [&](const Vertex *prev, const Vertex &cur, const Vertex *next, int) EPSM_LAMBDA {
         if (!cur.valid) {
             // an escaped ray towards an environment emitter: its warp's direction moves the lookup, its divergence multiplies L_in
-            if (cur.escaped && prev && has_environment(A.S) && cur.depth < R.cfg.max_depth && (cur.Le.x != 0.f || cur.Le.y != 0.f || cur.Le.z != 0.f)) {
+            if (escaped_warp(A.S, R.cfg, prev, cur)) {
                 const WarpTan t = sink.warp(cur.ray.o, cur.ray.d, prev->th.tri, prev->th.u, prev->th.v, 0.f);
                 if (Sink::kEval) {
                     F3 g[3];
@@ -920,12 +933,11 @@ EPSM_HD void reparam_forward_one_path(const ReparamFwdArgs &R, int64_t i, const 
                                    L0.z > 0.f ? dot(g[2], t.dir) * cur.Le.z / L0.z : 0.f) + cur.L_in * t.div;
                 }
             }
-            continue;
+            return;
         }
-        differential_forward(R, sink, prev, cur, &nx, pr, dLo, &cam);
-        if (j == 1 && R.cfg.max_depth > 0) primary_done = true;
-    }
-    if (!primary_done && R.cfg.max_depth > 0) {                            // the camera ray hit nothing: the film's term, and the
+        differential_forward(R, sink, prev, cur, next, pr, dLo, &cam);
+    });
+    if (!hit && R.cfg.max_depth > 0) {                                     // the camera ray hit nothing: the film's term, and the
         cam = sink.warp(pr.ray.o, pr.ray.d, kNoIndex, 0.f, 0.f, 0.f);      // environment's radiance along the reparameterised ray
         if (Sink::kEval && has_environment(A.S)) {
             F3 g[3];

@@ -8,6 +8,7 @@
 #include "epsm_trace_reparam.h"
 #include "epsm_trace_replay.h"
 #include "epsm_trace_packet.h"
+#include "epsm_trace_launch.h"
 
 using namespace epsm;
 using epsm_host::fail;
@@ -20,19 +21,28 @@ namespace {
 #ifndef EPSM_RP_OCC
 #define EPSM_RP_OCC 2                   // 256 registers: 3.4 KB of scratch per lane instead of 4.0 at four waves; render_backward 47.4 -> 44.9 ms (3: 46.5, 1: 45.2)
 #endif
-// Stage 1: one lane = one path, replayed; every vertex differentiated (dual numbers, scratch: three vertex records);
-// its warps are left as requests.  (First version, auxiliary rays traced by the same lane: 182 ms per render_backward
-// at 4.26 M paths / 128 k triangles / 16 rays with one wave per SIMD, 99 ms with four.)
-__global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_path_kernel(rp::ReparamArgs R, rp::WarpReq *req, int *count) {
+// What a lane of the three path kernels starts with: its path i of the tile and its traversal stack (an LDS column, the rest
+// private); lanes past N leave.  body(i, st).
+template <class Body>
+__device__ __forceinline__ void path_lane(int64_t N, Body body) {
     __shared__ uint32_t s_stack[kLaneStackLds * EPSM_RP_THREADS];
     uint32_t deep[kBvhStack - kLaneStackLds];
     const int64_t i = (int64_t) blockIdx.x * EPSM_RP_THREADS + threadIdx.x;
     const BvhStack st = lane_stack(s_stack, deep, EPSM_RP_THREADS);
-    if (i >= R.A.N) return;
-    rp::QueueSink sink{req, R.A.N, i, 0};
-    // (the camera rays of a wave walked together first, as the tracers do: 41.6 -> 42.3 ms per call; not kept)
-    rp::reparam_one_path(R, i, st, sink);
-    count[i] = sink.n;
+    if (i >= N) return;
+    body(i, st);
+}
+
+// Stage 1: one lane = one path, replayed; every vertex differentiated (dual numbers, scratch: three vertex records);
+// its warps are left as requests.  (First version, auxiliary rays traced by the same lane: 182 ms per render_backward
+// at 4.26 M paths / 128 k triangles / 16 rays with one wave per SIMD, 99 ms with four.)
+__global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_path_kernel(rp::ReparamArgs R, rp::WarpReq *req, int *count) {
+    path_lane(R.A.N, [&](int64_t i, const BvhStack &st) {
+        rp::QueueSink sink{{req, R.A.N, i, 0}};
+        // (the camera rays of a wave walked together first, as the tracers do: 41.6 -> 42.3 ms per call; not kept)
+        rp::reparam_one_path(R, i, st, sink);
+        count[i] = sink.n;
+    });
 }
 
 // Stage 2: one lane = one auxiliary ray, a group of G lanes (G = 16, 32 or 64 >= reparam_rays) = one request.  The rays of a wave
@@ -42,7 +52,19 @@ __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_pat
 // groups hold the same call of neighbouring paths: rays that start next to each other and point the same way -- and works
 // through the list 256 / G requests at a time.  (Round 3 launched one group per (n, path) slot and let the empty ones leave:
 // 29 % of the slots exist -- 2.06 requests per path of 7 at max_depth 3 -- and the waves that held any were 75 % full.)
-// Z, dZ and the origin's adjoint are reduced over the group with xor shuffles.
+// Z, dZ and the origin's adjoint are reduced over the group with xor shuffles: masks 1, 2, .., G / 2 in that order -- the order of
+// the additions is part of what the passes compute.
+template <int G> __device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+template <int G> __device__ __forceinline__ F3 group_sum(F3 v) { return f3(group_sum<G>(v.x), group_sum<G>(v.y), group_sum<G>(v.z)); }
+template <int G> __device__ __forceinline__ uint32_t group_min(uint32_t t) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) { const uint32_t u = (uint32_t) __shfl_xor((int) t, m); t = u < t ? u : t; }
+    return t;
+}
 struct WarpLds {
     uint32_t pstack[kPacketStack * 4];                                     // one column per wave (epsm_trace_packet.h)
     uint16_t list[256 * rp::kMaxReq];                                      // (n << 8) | path of the block
@@ -96,7 +118,7 @@ __device__ __forceinline__ void for_each_warp_group(const Args &R, const rp::War
         const int e = lds.list[g.live ? b : 0];
         g.n = e >> 8;
         g.i = p0 + (e & 255);
-        g.q = req[(int64_t) g.n * N + g.i];
+        g.q = rp::request_slot(req, N, g.n, g.i);
         const F3 o = f3(g.q.o[0], g.q.o[1], g.q.o[2]);
         g.d = f3(g.q.d[0], g.q.d[1], g.q.d[2]);
         F3 fs, ft;
@@ -109,11 +131,8 @@ __device__ __forceinline__ void for_each_warp_group(const Args &R, const rp::War
         if (g.mine) D = rp::aux_begin(R.cfg, rp::WarpId{0xffffffffu ^ R.A.seed, (uint32_t) (R.A.path_offset + g.i), g.n}, g.r, o, g.d, fs, ft);
         const TriHit ath = packet_intersect(R.A.S, D.ray, g.mine, lds.pstack + wv * kPacketStack);
         if (g.mine) g.A = rp::aux_finish(R.A.S, R.cfg, D, ath, o, g.d);
-        float Z = g.A.w;
-        g.dZ = g.A.dw;
-#pragma unroll
-        for (int m = 1; m < G; m <<= 1) { Z += __shfl_xor(Z, m); g.dZ.x += __shfl_xor(g.dZ.x, m); g.dZ.y += __shfl_xor(g.dZ.y, m); g.dZ.z += __shfl_xor(g.dZ.z, m); }
-        g.iZ = 1.f / fmaxf(Z, 1e-8f);
+        g.dZ = group_sum<G>(g.A.dw);
+        g.iZ = 1.f / fmaxf(group_sum<G>(g.A.w), 1e-8f);
         body(g);
     }
 }
@@ -146,29 +165,18 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
         // is 10^5 times a single share, which then falls under half an ulp of it -- 2 % of a four-vertex wall's gradient at
         // 256 spp.)
         for (int round = 0; round < G; ++round) {
-            uint32_t t = pending;
-#pragma unroll
-            for (int m = 1; m < G; m <<= 1) { const uint32_t u = (uint32_t) __shfl_xor((int) t, m); t = u < t ? u : t; }
+            const uint32_t t = group_min<G>(pending);
             if (t == 0xFFFFFFFFu) break;                                   // (uniform over the group)
             const bool sel = pending == t;
             const float b1 = sel ? A.b1 : 0.f, b2 = sel ? A.b2 : 0.f, b0 = sel ? 1.f - A.b1 - A.b2 : 0.f;
-            float acc[9] = {g_p.x * b0, g_p.y * b0, g_p.z * b0, g_p.x * b1, g_p.y * b1, g_p.z * b1, g_p.x * b2, g_p.y * b2, g_p.z * b2};
-#pragma unroll
-            for (int m = 1; m < G; m <<= 1)
-#pragma unroll
-                for (int k = 0; k < 9; ++k) acc[k] += __shfl_xor(acc[k], m);
+            const F3 acc0 = group_sum<G>(g_p * b0), acc1 = group_sum<G>(g_p * b1), acc2 = group_sum<G>(g_p * b2);
             if (r == 0) {
                 const uint32_t *iv = R.A.S.tri + 3 * (int64_t) t;
-                rp::add_vertex(R.G.pos, iv[0], f3(acc[0], acc[1], acc[2])); rp::add_vertex(R.G.pos, iv[1], f3(acc[3], acc[4], acc[5]));
-                rp::add_vertex(R.G.pos, iv[2], f3(acc[6], acc[7], acc[8]));
+                rp::add_vertex(R.G.pos, iv[0], acc0); rp::add_vertex(R.G.pos, iv[1], acc1); rp::add_vertex(R.G.pos, iv[2], acc2);
             }
             if (sel) pending = 0xFFFFFFFFu;
         }
-#pragma unroll
-        for (int m = 1; m < G; m <<= 1) {
-            g_o.x += __shfl_xor(g_o.x, m); g_o.y += __shfl_xor(g_o.y, m); g_o.z += __shfl_xor(g_o.z, m);
-            g_d.x += __shfl_xor(g_d.x, m); g_d.y += __shfl_xor(g_d.y, m); g_d.z += __shfl_xor(g_d.z, m);
-        }
+        g_o = group_sum<G>(g_o); g_d = group_sum<G>(g_d);
         if (live && r == 0 && q.ftri != kNoIndex) {
             if (q.em_inv_dist != 0.f) g_o = g_o - (g_d - d * dot(d, g_d)) * q.em_inv_dist;
             rp::add_follow_point(R.A.S, R.G, q.ftri, q.fb1, q.fb2, g_o);
@@ -183,14 +191,11 @@ __global__ __launch_bounds__(256) void epsm_reparam_warp_kernel(rp::ReparamArgs 
 // (ReadSink) reads each request's tangents back, does the dual evaluations and writes the path's d_radiance / d_film.
 template <class Sink>
 __global__ __launch_bounds__(EPSM_RP_THREADS, EPSM_RP_OCC) void epsm_reparam_fwd_path_kernel(rp::ReparamFwdArgs R, rp::WarpReq *req, int *count) {
-    __shared__ uint32_t s_stack[kLaneStackLds * EPSM_RP_THREADS];
-    uint32_t deep[kBvhStack - kLaneStackLds];
-    const int64_t i = (int64_t) blockIdx.x * EPSM_RP_THREADS + threadIdx.x;
-    const BvhStack st = lane_stack(s_stack, deep, EPSM_RP_THREADS);
-    if (i >= R.A.N) return;
-    Sink sink{req, R.A.N, i, 0};
-    rp::reparam_forward_one_path(R, i, st, sink);
-    if (!Sink::kEval) count[i] = sink.n;
+    path_lane(R.A.N, [&](int64_t i, const BvhStack &st) {
+        Sink sink{{req, R.A.N, i, 0}};
+        rp::reparam_forward_one_path(R, i, st, sink);
+        if (!Sink::kEval) count[i] = sink.n;
+    });
 }
 
 // Stage 2: one lane = one auxiliary ray, a group of G lanes = one request, listed and walked as in epsm_reparam_warp_kernel (the
@@ -210,14 +215,10 @@ __global__ __launch_bounds__(256) void epsm_reparam_fwd_warp_kernel(rp::ReparamF
             wv3 = tv * g.A.w;
             dv = dot(g.A.dw - g.dZ * (g.iZ * g.A.w), tv);
         }
-#pragma unroll
-        for (int m = 1; m < G; m <<= 1) {
-            wv3.x += __shfl_xor(wv3.x, m); wv3.y += __shfl_xor(wv3.y, m); wv3.z += __shfl_xor(wv3.z, m);
-            dv += __shfl_xor(dv, m);
-        }
+        wv3 = group_sum<G>(wv3); dv = group_sum<G>(dv);
         if (g.live && g.r == 0) {
             const F3 td = (wv3 - d * dot(d, wv3)) * g.iZ;
-            rp::WarpReq &w = req[(int64_t) g.n * R.A.N + g.i];
+            rp::WarpReq &w = rp::request_slot(req, R.A.N, g.n, g.i);
             w.gdir[0] = td.x; w.gdir[1] = td.y; w.gdir[2] = td.z; w.gdiv = dv * g.iZ;
         }
     });
@@ -225,37 +226,47 @@ __global__ __launch_bounds__(256) void epsm_reparam_fwd_warp_kernel(rp::ReparamF
 
 size_t req_bytes(int64_t N) { return ((size_t) N * rp::kMaxReq * sizeof(rp::WarpReq) + 255) & ~(size_t) 255; }
 
-// What both entry points check behind replay_args_fill: NULL = fine and cfg filled, otherwise what is wrong.
-const char *reparam_args_invalid(rp::ReparamCfg &cfg, const EpsmScene *scene, int64_t N, int reparam_max_depth, int reparam_rays,
-                                 float kappa, float exponent, uint32_t flags, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || (((uintptr_t) workspace) & 15) || workspace_bytes < epsm_trace_reparam_workspace_bytes(N))
-        return "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
-    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux || reparam_max_depth < 0 || !(kappa > 0.f) || !(exponent > 0.f))
-        return "need 1 <= reparam_rays <= 64, reparam_max_depth >= 0, kappa > 0, exponent > 0";
-    if (flags & ~EPSM_REPARAM_ANTITHETIC) return "unknown flag";
-    // (this pass's own rule: there is nothing to move, and its kernels have not been tried on a scene without geometry)
-    if (scene->n_triangles <= 0) return "the scene has no triangles";
-    cfg.max_depth = reparam_max_depth; cfg.rays = reparam_rays; cfg.kappa = kappa; cfg.exponent = exponent; cfg.flags = flags;
-    return nullptr;
+size_t workspace_bytes_for(int64_t N) { return N > 0 ? req_bytes(N) + (size_t) N * sizeof(int) : 0; }
+
+// What an entry point launches on: the two halves of its workspace and the grid of the path kernels
+struct Stages { rp::WarpReq *req; int *count; dim3 path_grid; };
+
+// What both entry points do before their first launch: the common arguments (replay_args_fill), N == 0, the entry point's own
+// NULL check (`null_why`: its finding, made by the caller), the workspace, the pass's cfg.  True: R.A, R.cfg and L are filled and
+// there is something to launch; false: rc is what the entry point returns.
+template <class Args>
+bool reparam_begin(const char *what, Args &R, Stages &L, int &rc, const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp,
+                   int max_depth, int rr_depth, int64_t path_offset, int64_t N, const char *null_why, int reparam_max_depth, int reparam_rays,
+                   float kappa, float exponent, uint32_t flags, void *workspace, size_t workspace_bytes) {
+    epsm_host::err_buf()[0] = 0;
+    rc = EPSM_OK;
+    const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1);
+    if (!why && N == 0) return false;
+    if (!why) why = null_why;
+    if (!why && !workspace_ok(workspace, workspace_bytes, workspace_bytes_for(N))) why = "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
+    if (!why) why = rp::reparam_cfg_fill(R.cfg, scene, reparam_max_depth, reparam_rays, kappa, exponent, flags);
+    if (why) { rc = fail(EPSM_EINVAL, what, why); return false; }
+    L.req = (rp::WarpReq *) workspace;
+    L.count = (int *) ((char *) workspace + req_bytes(N));
+    L.path_grid = dim3((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS));
+    return true;
 }
 
 // Stage 2 of either pass: launch(G, grid, n_max) starts its warp kernel for groups of G = 16, 32 or 64 >= reparam_rays lanes.
 template <class Launch>
-int launch_warp_stage(const char *what, const TraceArgs &A, int reparam_rays, Launch launch) {
+int launch_warp_stage(const TraceArgs &A, int reparam_rays, Launch launch) {
     // the n-th requests of all paths, n = 0 .. n_max - 1: the camera ray + two warps per vertex the depths allow
     const int depth = path_max_depth(A);
     const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
     const dim3 grid((unsigned) ((A.N + 255) / 256));                       // one workgroup per 256 paths (N < 2^32: checked)
-    if (reparam_rays <= 16) launch(std::integral_constant<int, 16>(), grid, n_max);
-    else if (reparam_rays <= 32) launch(std::integral_constant<int, 32>(), grid, n_max);
-    else launch(std::integral_constant<int, 64>(), grid, n_max);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? EPSM_OK : epsm_host::hip_fail(what, e);
+    if (reparam_rays <= 16) return launch(std::integral_constant<int, 16>(), grid, n_max);
+    if (reparam_rays <= 32) return launch(std::integral_constant<int, 32>(), grid, n_max);
+    return launch(std::integral_constant<int, 64>(), grid, n_max);
 }
 
 }  // namespace
 
-extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t N) { return N > 0 ? req_bytes(N) + (size_t) N * sizeof(int) : 0; }
+extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t N) { return workspace_bytes_for(N); }
 
 extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor *sensor,
                                         uint32_t seed, int spp, int max_depth, int rr_depth,
@@ -263,25 +274,20 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
                                         const float *radiance, const float *adj_radiance, const float *adj_film,
                                         int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                                         float *grad_pos, float *grad_nrm, void *workspace, size_t workspace_bytes, void *stream) {
-    epsm_host::err_buf()[0] = 0;
     static const char *what = "epsm_trace_paths_reparam";
     rp::ReparamArgs R = {};
-    if (const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return fail(EPSM_EINVAL, what, why);
-    if (N == 0) return EPSM_OK;
-    if (!radiance || !adj_radiance || !adj_film || !grad_pos) return fail(EPSM_EINVAL, what, "NULL per-path input or grad_pos");
-    if (const char *why = reparam_args_invalid(R.cfg, scene, N, reparam_max_depth, reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
-        return fail(EPSM_EINVAL, what, why);
+    Stages L;
+    int rc;
+    if (!reparam_begin(what, R, L, rc, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N,
+                       !radiance || !adj_radiance || !adj_film || !grad_pos ? "NULL per-path input or grad_pos" : nullptr, reparam_max_depth,
+                       reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
+        return rc;
     R.radiance = radiance; R.adj_radiance = adj_radiance; R.adj_film = adj_film;
     R.G.pos = grad_pos; R.G.nrm = grad_nrm;
-    rp::WarpReq *req = (rp::WarpReq *) workspace;
-    int *count = (int *) ((char *) workspace + req_bytes(N));
-    hipLaunchKernelGGL(epsm_reparam_path_kernel, dim3((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS)), dim3(EPSM_RP_THREADS), 0,
-                       (hipStream_t) stream, R, req, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    if (reparam_max_depth == 0) return EPSM_OK;
-    return launch_warp_stage(what, R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
-        hipLaunchKernelGGL(epsm_reparam_warp_kernel<decltype(G)::value>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+    rc = launch_checked(what, epsm_reparam_path_kernel, L.path_grid, EPSM_RP_THREADS, stream, R, L.req, L.count);
+    if (rc != EPSM_OK || reparam_max_depth == 0) return rc;
+    return launch_warp_stage(R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+        return launch_checked(what, epsm_reparam_warp_kernel<decltype(G)::value>, grid, 256, stream, R, L.req, L.count, n_max);
     });
 }
 
@@ -293,29 +299,22 @@ extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const Ep
                                                 const float *tan_pos, const float *tan_nrm,
                                                 int reparam_max_depth, int reparam_rays, float kappa, float exponent, uint32_t flags,
                                                 float *d_radiance, float *d_film, void *workspace, size_t workspace_bytes, void *stream) {
-    epsm_host::err_buf()[0] = 0;
     static const char *what = "epsm_trace_paths_reparam_forward";
     rp::ReparamFwdArgs R = {};
-    if (const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return fail(EPSM_EINVAL, what, why);
-    if (N == 0) return EPSM_OK;
-    if (!radiance || !tan_pos || !d_radiance || !d_film) return fail(EPSM_EINVAL, what, "NULL per-path input / output or tan_pos");
-    if (const char *why = reparam_args_invalid(R.cfg, scene, N, reparam_max_depth, reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
-        return fail(EPSM_EINVAL, what, why);
+    Stages L;
+    int rc;
+    if (!reparam_begin(what, R, L, rc, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N,
+                       !radiance || !tan_pos || !d_radiance || !d_film ? "NULL per-path input / output or tan_pos" : nullptr, reparam_max_depth,
+                       reparam_rays, kappa, exponent, flags, workspace, workspace_bytes))
+        return rc;
     R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
-    rp::WarpReq *req = (rp::WarpReq *) workspace;
-    int *count = (int *) ((char *) workspace + req_bytes(N));
-    const dim3 path_grid((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS));
     if (reparam_max_depth > 0) {                                           // (no warp at depth 0: stage 3 alone)
-        hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::RecordSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-        const int rc = launch_warp_stage(what, R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
-            hipLaunchKernelGGL(epsm_reparam_fwd_warp_kernel<decltype(G)::value>, grid, dim3(256), 0, (hipStream_t) stream, R, req, count, n_max);
+        rc = launch_checked(what, epsm_reparam_fwd_path_kernel<rp::RecordSink>, L.path_grid, EPSM_RP_THREADS, stream, R, L.req, L.count);
+        if (rc != EPSM_OK) return rc;
+        rc = launch_warp_stage(R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+            return launch_checked(what, epsm_reparam_fwd_warp_kernel<decltype(G)::value>, grid, 256, stream, R, L.req, L.count, n_max);
         });
         if (rc != EPSM_OK) return rc;
     }
-    hipLaunchKernelGGL(epsm_reparam_fwd_path_kernel<rp::ReadSink>, path_grid, dim3(EPSM_RP_THREADS), 0, (hipStream_t) stream, R, req, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return epsm_host::hip_fail(what, e);
-    return EPSM_OK;
+    return launch_checked(what, epsm_reparam_fwd_path_kernel<rp::ReadSink>, L.path_grid, EPSM_RP_THREADS, stream, R, L.req, L.count);
 }

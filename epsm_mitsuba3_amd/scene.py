@@ -1594,6 +1594,14 @@ class Scene:
             ws = self._reparam_ws = torch.empty(max(need, 16), device=device, dtype=torch.uint8)
         return ws
 
+    def _reparam_tail(self, bytes_entry: str, n: int, device, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float,
+                      antithetic: bool):
+        """What both reparameterised entry points take behind their per-path arrays: ``(cfg_args, ws, ws_size)`` -- the five
+        ``cfg`` arguments in ctypes form, the workspace of ``bytes_entry(n)`` bytes and its size."""
+        ws = self._reparam_workspace(int(getattr(self._runtime()[0], bytes_entry)(C.c_int64(n))), device)
+        cfg_args = (int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent), C.c_uint32(1 if antithetic else 0))
+        return cfg_args, ws, C.c_size_t(ws.numel())
+
     def trace_color(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int):
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
         dev = self.device
@@ -1747,10 +1755,10 @@ class Scene:
             self._rows(t_, n, 3)
         for t_ in (grad_pos, grad_nrm):
             self._rows(t_, self.V, 3)
-        ws = self._reparam_workspace(int(self._runtime()[0].epsm_trace_reparam_workspace_bytes(C.c_int64(n))), radiance.device)
-        self._replay("epsm_trace_paths_reparam", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, adj_film,
-                     int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent), C.c_uint32(1 if antithetic else 0),
-                     grad_pos, grad_nrm, ws, C.c_size_t(ws.numel()))
+        cfg_args, ws, ws_size = self._reparam_tail("epsm_trace_reparam_workspace_bytes", n, radiance.device, reparam_max_depth, reparam_rays,
+                                                   kappa, exponent, antithetic)
+        self._replay("epsm_trace_paths_reparam", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, adj_film, *cfg_args,
+                     grad_pos, grad_nrm, ws, ws_size)
 
     def trace_reparam_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tan_pos,
                               tan_nrm, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float, antithetic: bool = False):
@@ -1765,10 +1773,10 @@ class Scene:
             self._rows(t_, self.V, 3)
         d_radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
         d_film = torch.empty((n, 3), device=dev, dtype=torch.float32)
-        ws = self._reparam_workspace(int(self._runtime()[0].epsm_trace_reparam_forward_workspace_bytes(C.c_int64(n))), radiance.device)
-        self._replay("epsm_trace_paths_reparam_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tan_pos, tan_nrm,
-                     int(reparam_max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent), C.c_uint32(1 if antithetic else 0),
-                     d_radiance, d_film, ws, C.c_size_t(ws.numel()))
+        cfg_args, ws, ws_size = self._reparam_tail("epsm_trace_reparam_forward_workspace_bytes", n, radiance.device, reparam_max_depth,
+                                                   reparam_rays, kappa, exponent, antithetic)
+        self._replay("epsm_trace_paths_reparam_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tan_pos, tan_nrm, *cfg_args,
+                     d_radiance, d_film, ws, ws_size)
         return d_radiance, d_film
 
     def film_splat(self, accum: torch.Tensor, sensor: Sensor, film_pos: torch.Tensor, radiance: torch.Tensor) -> None:

@@ -14,17 +14,12 @@ extern "C" int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const Ep
     rp::ReparamFwdArgs R = {};
     if (replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return -22;
     if (N == 0) return 0;
-    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux) return -22;
     if (!radiance || !tan_pos || !d_radiance || !d_film) return -22;
-    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    if (rp::reparam_cfg_fill(R.cfg, scene, reparam_max_depth, reparam_rays, kappa, exponent, flags)) return -22;   // (as the device library)
     R.radiance = radiance; R.T.pos = tan_pos; R.T.nrm = tan_nrm; R.d_radiance = d_radiance; R.d_film = d_film;
-#pragma omp parallel for schedule(dynamic, 64)
-    for (int64_t i = 0; i < N; ++i) {
-        uint32_t stack[kBvhStack];
-        rp::Warp W;
-        const BvhStack st{stack, 1};
-        rp::InlineFwdSink sink{R.A.S, R.cfg, R.T, st, W, rp::WarpId{0xffffffffu ^ seed, (uint32_t) (path_offset + i), 0}};
+    for_each_reparam_path(R.A, [&](int64_t i, const BvhStack &st, rp::Warp &W, const rp::WarpId &id) {
+        rp::InlineFwdSink sink{R.A.S, R.cfg, R.T, st, W, id};
         rp::reparam_forward_one_path(R, i, st, sink);
-    }
+    });
     return 0;
 }

@@ -60,6 +60,18 @@ extern "C" int epsm_trace_paths_color(const EpsmScene *scene, const EpsmSensor *
     return 0;
 }
 
+// The paths of a reparameterised pass (backward here, forward in trace_fwd_host.cpp), OpenMP over them: body(i, st, W, id) with
+// the path's stack, the Warp its inline sink collects the auxiliary rays in, and the id of its first warp -- path
+// path_offset + i under the reparameterisation's own seed, call 0 (rp::WarpId).
+template <class Body> void for_each_reparam_path(const TraceArgs &A, Body body) {
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < A.N; ++i) {
+        uint32_t stack[kBvhStack];
+        rp::Warp W;
+        body(i, BvhStack{stack, 1}, W, rp::WarpId{0xffffffffu ^ A.seed, (uint32_t) (A.path_offset + i), 0});
+    }
+}
+
 extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor *sensor, uint32_t seed, int spp, int max_depth,
                                         int rr_depth, int64_t path_offset, int64_t N, const float *radiance,
                                         const float *adj_radiance, const float *adj_film, int reparam_max_depth, int reparam_rays,
@@ -68,18 +80,13 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
     rp::ReparamArgs R = {};
     if (replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1)) return -22;
     if (N == 0) return 0;
-    if (reparam_rays < 1 || reparam_rays > rp::kMaxAux) return -22;
-    R.cfg.max_depth = reparam_max_depth; R.cfg.rays = reparam_rays; R.cfg.kappa = kappa; R.cfg.exponent = exponent; R.cfg.flags = flags;
+    if (rp::reparam_cfg_fill(R.cfg, scene, reparam_max_depth, reparam_rays, kappa, exponent, flags)) return -22;   // (as the device library)
     R.radiance = radiance; R.adj_radiance = adj_radiance; R.adj_film = adj_film;
     R.G.pos = grad_pos; R.G.nrm = grad_nrm;
-#pragma omp parallel for schedule(dynamic, 64)
-    for (int64_t i = 0; i < N; ++i) {
-        uint32_t stack[kBvhStack];
-        rp::Warp W;
-        const BvhStack st{stack, 1};
-        rp::InlineSink sink{R.A.S, R.cfg, R.G, st, W, rp::WarpId{0xffffffffu ^ seed, (uint32_t) (path_offset + i), 0}};
+    for_each_reparam_path(R.A, [&](int64_t i, const BvhStack &st, rp::Warp &W, const rp::WarpId &id) {
+        rp::InlineSink sink{R.A.S, R.cfg, R.G, st, W, id};
         rp::reparam_one_path(R, i, st, sink);
-    }
+    });
     return 0;
 }
 extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t) { return 0; }

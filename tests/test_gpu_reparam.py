@@ -50,6 +50,118 @@ def test_device_pass_equals_the_host_build(name, rays, antithetic):
         assert abs(float(a.sum() - b.sum())) < 2e-2 * float(a.abs().sum()), (name, what)
 
 
+_MAX_REQ, _REQ_WORDS = 13, 16            # rp::kMaxReq requests per path of sizeof(rp::WarpReq) / 4 words (csrc/epsm_trace_reparam.h)
+
+
+def _attached(name, res, spp, device="cuda"):
+    sc = build(name, 0.0, res, spp, device)
+    for m in CONFIGS[name]["moving"]:
+        sc.attach(m, positions=True, normals=True)
+    return sc
+
+
+def _cfg_kw(name, rays=16):
+    return dict(reparam_max_depth=CONFIGS[name]["max_depth"], reparam_rays=rays, kappa=CONFIGS[name].get("kappa", 1e5), exponent=3.0)
+
+
+def _workspace_tables(sc, n):
+    """The workspace a reparameterised pass left for n paths, as (kMaxReq, n, 16) request words and n counts: the requests,
+    rounded up to 256 bytes, then the counts (epsm_trace_reparam_workspace_bytes)."""
+    import ctypes as C
+    req_bytes = (n * _MAX_REQ * _REQ_WORDS * 4 + 255) & ~255
+    assert int(sc._runtime()[0].epsm_trace_reparam_workspace_bytes(C.c_int64(n))) == req_bytes + 4 * n
+    ws = sc._reparam_ws.clone()
+    req = ws[: n * _MAX_REQ * _REQ_WORDS * 4].view(torch.int32).view(_MAX_REQ, n, _REQ_WORDS)
+    count = ws[req_bytes: req_bytes + 4 * n].view(torch.int32)
+    return req.cpu(), count.cpu()
+
+
+@pytest.mark.parametrize("name", ["sphere_on_glossy_floor", "diffuse_sphere_envmap"])
+def test_both_passes_number_their_requests_alike(name):
+    """Request n of path i is the same warp in the backward and in the forward pass -- the forward pass draws the backward's
+    auxiliary rays only because of that.  Both passes leave their requests in the same workspace layout: the counts are equal
+    and, below a path's count, the ray (o, d), em_inv_dist and the glued origin (ftri, fb1, fb2) are the same bits; gdir / gdiv
+    hold adjoints in one and tangents in the other, and slots at or past the count are not written.  The glossy floor has warps
+    of the ray into a vertex and of emitter rays at several depths, the envmap escaped rays and camera rays that hit nothing."""
+    res, spp, seed = 16, 4, 3
+    sc = _attached(name, res, spp)
+    depth, n = CONFIGS[name]["max_depth"], sc.sensors[0].wavefront_size(spp)
+    gen = torch.Generator().manual_seed(11)
+    rnd = lambda *shape: torch.randn(shape, generator=gen).to(sc.device)
+    radiance = sc._trace(0, seed, spp, depth, 0, 0, n).radiance.contiguous()
+    p = sc.param_grads()
+    sc.trace_reparam(0, seed, spp, depth, 0, n, radiance, rnd(n, 3), rnd(n, 3), p.pos, p.nrm, **_cfg_kw(name))
+    torch.cuda.synchronize()
+    req_b, count_b = _workspace_tables(sc, n)
+    sc.trace_reparam_forward(0, seed, spp, depth, 0, n, radiance, rnd(sc.V, 3), rnd(sc.V, 3), **_cfg_kw(name))
+    torch.cuda.synchronize()
+    req_f, count_f = _workspace_tables(sc, n)
+    assert torch.equal(count_b, count_f)
+    assert int(count_b.min()) >= 1 and int(count_b.max()) <= min(_MAX_REQ, 1 + 2 * depth)
+    live = torch.arange(_MAX_REQ)[:, None] < count_b[None, :]                       # (kMaxReq, n)
+    for what, words in (("o", [0, 1, 2]), ("d", [4, 5, 6]), ("em_inv_dist", [7]), ("fb1", [11]), ("ftri", [12]), ("fb2", [13])):
+        assert torch.equal(req_b[:, :, words][live], req_f[:, :, words][live]), what
+    # not vacuous: paths with the camera ray's warp alone, paths with three and more, three different counts at least
+    hist = torch.bincount(count_b, minlength=_MAX_REQ + 1)
+    print(f"{name}: {n} paths, requests per path {hist.tolist()}")
+    assert int(hist[1]) > 0 and int(hist[3:].sum()) > 0 and int((hist > 0).sum()) >= 3, hist
+
+
+_RAGGED = [(37, 1037), (1000, 1001)]      # 1 000 paths -- no multiple of 64 or 256 -- from a non-zero offset, and a single path
+
+
+def test_forward_pass_on_ragged_ranges_gives_the_rows_of_the_whole_call():
+    """``trace_reparam_forward`` on a tile that starts off a workgroup's boundary and ends off another: the rows of the call on
+    [0, 2048), bit for bit -- no atomics, a path's streams are keyed by its wavefront index, and the wave-packet walk of stage 2
+    gives every ray its own closest hit whoever its neighbours are (measured on the library before the passes shared their
+    frame: MEASUREMENTS.md 26)."""
+    name, res, spp, seed = "diffuse_sphere_area_light", 16, 8, 5
+    sc = _attached(name, res, spp)
+    depth = CONFIGS[name]["max_depth"]
+    assert sc.sensors[0].wavefront_size(spp) >= 2048
+    gen = torch.Generator().manual_seed(2)
+    tan_pos, tan_nrm = (torch.randn((sc.V, 3), generator=gen).to(sc.device) for _ in range(2))
+    radiance = sc._trace(0, seed, spp, depth, 0, 0, 2048).radiance.contiguous()
+    whole = sc.trace_reparam_forward(0, seed, spp, depth, 0, 2048, radiance, tan_pos, tan_nrm, **_cfg_kw(name))
+    assert float(whole[0].abs().max()) > 0 and float(whole[1].abs().max()) > 0
+    for lo, hi in _RAGGED:
+        part = sc.trace_reparam_forward(0, seed, spp, depth, lo, hi, radiance[lo:hi].contiguous(), tan_pos, tan_nrm, **_cfg_kw(name))
+        for a, b, what in zip(part, whole, ("d_radiance", "d_film")):
+            differ = int((a != b[lo:hi]).any(dim=1).sum())
+            print(f"[{lo}, {hi}) {what}: {differ} of {hi - lo} rows differ")
+            assert torch.equal(a, b[lo:hi]), (lo, hi, what, differ)
+
+
+def test_backward_pass_on_ragged_ranges_equals_the_host_build():
+    """The same ranges through ``trace_reparam`` against the host build's inline warps, under the bound of
+    test_device_pass_equals_the_host_build."""
+    name, res, spp, seed = "diffuse_sphere_area_light", 16, 8, 5
+    depth = CONFIGS[name]["max_depth"]
+    gen = torch.Generator().manual_seed(6)
+    adj_radiance, adj_film = torch.randn((2048, 3), generator=gen), torch.randn((2048, 3), generator=gen)
+    radiance, out = None, []
+    for dev in ("cpu", "cuda"):
+        sc = _attached(name, res, spp, dev)
+        if radiance is None:
+            radiance = sc._trace(0, seed, spp, depth, 0, 0, 2048).radiance.contiguous()
+        grads = []
+        for lo, hi in _RAGGED:
+            p = sc.param_grads()
+            sc.trace_reparam(0, seed, spp, depth, lo, hi, *(t[lo:hi].contiguous().to(sc.device) for t in (radiance, adj_radiance, adj_film)),
+                             p.pos, p.nrm, **_cfg_kw(name))
+            grads.append((p.pos.cpu().clone(), p.nrm.cpu().clone()))
+        out.append(grads)
+    for k, (lo, hi) in enumerate(_RAGGED):
+        for a, b, what in zip(out[0][k], out[1][k], ("pos", "nrm")):
+            scale = float(a.abs().max())
+            bad = float(((a - b).abs() > 2e-2 * scale).float().mean())
+            print(f"[{lo}, {hi}) {what}: scale {scale:.3e}, share beyond 2e-2 of it {bad:.4f}, sums {float(a.sum()):.4e} {float(b.sum()):.4e}")
+            if hi - lo > 1:
+                assert scale > 0, what
+            assert bad < 0.02, (lo, hi, what, bad, scale)
+            assert abs(float(a.sum() - b.sum())) <= 2e-2 * float(a.abs().sum()), (lo, hi, what)
+
+
 @pytest.mark.parametrize("name,spp,tol", [
     ("scale_sphere_emitter_on_black", 2048, 0.1),    # :438-460
     ("self_shadow_point_light", 4096, 0.35),         # :551-596 (all-ones weights, as there: the ramp's answer is ~0)

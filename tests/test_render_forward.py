@@ -185,6 +185,51 @@ def test_refusals_are_those_of_the_backward_pass():
         integ.render_forward(sc, sc.param_grads(), spp=2)
 
 
+def test_host_twins_refuse_what_the_device_refuses():
+    """Both reparameterised host entry points fill their ``cfg`` through the device library's own rule
+    (csrc/epsm_trace_reparam.h, reparam_cfg_fill), as the tracer's twins do with trace_args_fill
+    (tests/test_tracer_wavefront_host.py::test_host_twin_refuses_what_the_device_refuses): a ray count outside 1..64, a kappa
+    or exponent that is not positive, a negative reparam_max_depth and an unknown flag bit are refused and nothing is written;
+    N == 0 with a scene and a sensor is fine whatever else is passed; the same call without the fault runs."""
+    import ctypes as C
+    res, spp, depth = 8, 2, 3
+    sc = _scene("diffuse_sphere_area_light", res, spp)
+    lib, n = sc._backend, sc.sensors[0].wavefront_size(spp)
+    radiance = sc._trace(0, 1, spp, depth, 0, 0, n).radiance.contiguous()
+    gen = torch.Generator().manual_seed(1)
+    adj, adj_film = torch.randn((n, 3), generator=gen), torch.randn((n, 3), generator=gen)
+    tan_pos, tan_nrm = torch.randn((sc.V, 3), generator=gen), torch.randn((sc.V, 3), generator=gen)
+    grad_pos, grad_nrm = torch.zeros((sc.V, 3)), torch.zeros((sc.V, 3))
+    d_radiance, d_film = torch.full((n, 3), float("nan")), torch.full((n, 3), float("nan"))
+    cs = sc.sensors[0].c_struct()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    good = dict(rmd=depth, rays=4, kappa=1e5, exponent=3.0, flags=0)
+
+    def call(forward, N=n, spp_=spp, **kw):
+        c = dict(good, **kw)
+        head = [C.byref(sc.c_scene), C.byref(cs), C.c_uint32(1), spp_, depth, int(sc.rr_depth), C.c_int64(0), C.c_int64(N)]
+        cfg = [c["rmd"], c["rays"], C.c_float(c["kappa"]), C.c_float(c["exponent"]), C.c_uint32(c["flags"])]
+        if N == 0:                                                                       # garbage beside scene and sensor
+            return getattr(lib, "epsm_trace_paths_reparam_forward" if forward else "epsm_trace_paths_reparam")(
+                *head, None, None, None, *cfg, None, None, None, C.c_size_t(0), None)
+        if forward:
+            return lib.epsm_trace_paths_reparam_forward(*head, ptr(radiance), ptr(tan_pos), ptr(tan_nrm), *cfg, ptr(d_radiance), ptr(d_film),
+                                                        None, C.c_size_t(0), None)
+        return lib.epsm_trace_paths_reparam(*head, ptr(radiance), ptr(adj), ptr(adj_film), *cfg, ptr(grad_pos), ptr(grad_nrm), None,
+                                            C.c_size_t(0), None)
+
+    for forward in (False, True):
+        for bad in (dict(rays=0), dict(rays=65), dict(kappa=0.0), dict(exponent=0.0), dict(rmd=-1), dict(flags=2)):
+            assert call(forward, **bad) != 0, (forward, bad)
+        assert call(forward, N=0, spp_=-3, rays=0, kappa=-1.0, exponent=0.0, rmd=-7, flags=0xF0) == 0
+        if forward:                                                                      # nothing ran
+            assert bool(torch.isnan(d_radiance).all()) and bool(torch.isnan(d_film).all())
+        else:
+            assert float(grad_pos.abs().max()) == 0
+        assert call(forward) == 0
+    assert float(grad_pos.abs().max()) > 0 and bool(torch.isfinite(d_radiance).all()) and float(d_radiance.abs().max()) > 0
+
+
 def test_unattached_slots_do_not_change_the_image():
     sc = _scene("diffuse_sphere_area_light", 10, 4)
     integ = epsm.load_dict({"type": "prb_reparam", "max_depth": 3, "reparam_rays": 8})
