@@ -38,17 +38,18 @@ namespace {
 // Shape (round 4): workgroups of four waves, THREE of them per CU = three waves per SIMD.  That takes <= 168 registers (the
 // kernel has 168, no scratch access inside the round loop: csrc/build/asm, tools/cp_regs.sh) and <= 53 248 bytes of LDS per
 // workgroup -- a CU hands out 159 744 bytes (2 x 79 872 fitted in round 3, 3 x 53 872 does not, 3 x 53 120 does): the wave
-// queues went from 384 to 192 items (one push of three rows from every lane), the table from 1504 to 960 fixed-point rows.
+// queues went from 384 to 192 items (one push of three rows from every lane), the table from 1504 to 960 fixed-point rows --
+// 1104 since a window keeps ONE 32-bit slot word per path in LDS instead of a plan word and a 16-bit sorted index.
 // (384-thread workgroups, two per CU: the second one is never co-resident -- 1485 waves in flight of 3072, 3.40 ms; 768
 // threads, one per CU: 2.53 ms -- twelve waves meet at every barrier of a window; 192 threads, four per CU: 2.83 ms.)
 #ifndef EPSM_CP_OCC
 #define EPSM_CP_OCC 3                   // waves per SIMD the register budget is set for
 #endif
 #ifndef EPSM_CP_ROWS_FLOAT
-#define EPSM_CP_ROWS_FLOAT 2064
+#define EPSM_CP_ROWS_FLOAT 2192           // rows of the table with windows of 1024 paths (larger windows: kRowsFloat / kRowsFixed)
 #endif
 #ifndef EPSM_CP_ROWS_FIXED
-#define EPSM_CP_ROWS_FIXED 1184
+#define EPSM_CP_ROWS_FIXED 1256
 #endif
 #ifndef EPSM_CP_QUEUE
 #define EPSM_CP_QUEUE 192               // >= 3 rows x 64 lanes, the largest push
@@ -238,11 +239,10 @@ template <typename Table> struct Emitter {
 };
 
 // ---- who a lane is in round r of the current window
-struct LaneId { int q, c, k; uint32_t plan; int loc; };      // plan == 0: no path on this lane
+struct LaneId { int q, c, k; uint32_t word; int loc; };      // word: the path's slot word (epsm_cp_core.h); 0: no path on this lane
 struct Rounds {
     int cls[kKeys + 1], rb[kKeys + 1];
-    const uint16_t *perm;            // LDS: the window's paths sorted by m
-    const uint32_t *plan;            // LDS
+    const uint32_t *slot;            // LDS: the slot words of the window's paths, sorted by m
     __device__ __forceinline__ LaneId lane_of(int r, int lane) const {
         LaneId L;
         int q = 0;
@@ -255,9 +255,10 @@ struct Rounds {
         const int j = div_small(lane, c), k = lane - j * c + 1;
         const int idx = (r - rb_q) * ppr + j;
         const bool lane_on = r >= 0 && r < rb[kKeys] && j < ppr && idx < n_q;      // (r < 0: past the last round handed out)
-        const int loc = lane_on ? (int) perm[cls_q + idx] : 0;
-        L.q = q; L.c = c; L.k = k; L.loc = loc;
-        L.plan = lane_on ? plan[loc] : 0u;               // (paths beyond the end of the wavefront have plan 0)
+        // ONE LDS word per lane and round: what the round needs of the plan and the path's slot in the window (paths beyond the
+        // end of the wavefront have word 0, and slot 0 with it)
+        const uint32_t word = lane_on ? slot[cls_q + idx] : 0u;
+        L.q = q; L.c = c; L.k = k; L.word = word; L.loc = cp::slot_of(word);
         return L;
     }
 };
@@ -338,12 +339,12 @@ struct LaneRole { bool ok, first, live, end_next, d1, act1; uint32_t loc; const 
 template <bool LIST>
 __device__ __forceinline__ LaneRole role_of(const FusedArgs &F, const LaneId &L, const WinBase &B) {
     LaneRole R;
-    R.ok = L.plan != 0u;
+    R.ok = L.word != 0u;
     R.first = L.k == 1;
     R.live = R.ok && L.q > 0;
-    R.end_next = R.live && L.k == L.c && L.k + 1 <= cp::plan_nv(L.plan);      // vertex k+1 exists and has no lane
-    R.d1 = R.ok && R.first && cp::plan_diffuse1(L.plan);
-    R.act1 = (L.plan & cp::kPlanActive1) != 0;
+    R.end_next = R.live && L.k == L.c && L.k + 1 <= cp::plan_nv(L.word);      // vertex k+1 exists and has no lane
+    R.d1 = R.ok && R.first && cp::slot_diffuse1(L.word);
+    R.act1 = cp::slot_active1(L.word);
     // A lane without a path stands in for the window's FIRST path (loc 0): its rays and its pixel are addresses that a lane of this
     // window may read, so geo_issue_rest loads them without a guard
     R.loc = R.ok ? (uint32_t) L.loc : 0u;
@@ -405,7 +406,7 @@ template <int VARIANT, bool LIST>
 __device__ __forceinline__ void addr_issue(AddrFetch &A, const FusedArgs &F, const LaneId &L, const WinBase &B) {
     const LaneRole R = role_of<LIST>(F, L, B);
     if (R.live) {
-        const bool wN = VARIANT == EPSM_VARIANT_MANIFOLD && cp::plan_a(L.plan, L.k);
+        const bool wN = VARIANT == EPSM_VARIANT_MANIFOLD && cp::plan_a(L.word, L.k);
         if (F.galpha || wN) A.q7 = ldq(R.rec, 7);                  // d hf / d alpha, and light.z of the emitter sample
         if (wN) A.q6 = ldq(R.rec, 6);
     }
@@ -443,21 +444,50 @@ __device__ __forceinline__ void fetch_zero(GeoFetch &X, AddrFetch &A) {
 // pool slab 3.54 -> 3.31 (3072: 2.39 / 2.82 / 3.62 and 4096: 2.12 / 2.78 / 3.46 -- the 6 bytes of LDS per path are taken from
 // the table; with ONE partly filled round per window -- paths on 8 / 4 / 2 / 1 lanes, widest first, classes mixed inside a
 // round -- 2.56: the mixed rounds run the longest chain's recursion for everybody).  Small wavefronts keep <= 1024.
+// (Those figures date from 6 bytes per path; a window now costs 4 -- its slot word.)  With slots > 0 (EPSM_OPT_WORKGROUP_SLOTS, off
+// by default) the LAST windows of a large wavefront are shorter -- half, then a quarter of `bulk_window`, cp::window_schedule -- so
+// that `slots` resident workgroups finish within a quarter of a window's time of each other; slots == 0: every window is
+// `bulk_window` paths, the last one ragged.
 #ifndef EPSM_CP_WINDOW
 #define EPSM_CP_WINDOW 2048
 #endif
 
+// The launch's windows (cp::window_schedule) for the kernel, out of line; what they return is workgroup-uniform, which the
+// compiler cannot see through a call: uniform64.
+struct WindowRange { int64_t first, count; };
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    const uint32_t lo = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) v), hi = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) ((uint64_t) v >> 32));
+    return (int64_t) (((uint64_t) hi << 32) | lo);
+}
+// {windows of the launch, consecutive windows per workgroup}
+__device__ __attribute__((noinline)) WindowRange launch_windows(int64_t n, int slots, int bulk_window, int64_t workgroups) {
+    const cp::WindowSchedule s = cp::window_schedule(n, (int64_t) slots, bulk_window);
+    return WindowRange{s.windows, cp::windows_per_workgroup(s.windows, workgroups)};
+}
+// {first path, paths} of window `win`
+__device__ __attribute__((noinline)) WindowRange window_range(int64_t n, int slots, int bulk_window, int64_t win) {
+    int64_t first;
+    int size;
+    cp::window_at(cp::window_schedule(n, (int64_t) slots, bulk_window), win, first, size);
+    return WindowRange{first, (int64_t) size};
+}
+
 // DROP: paths without any term take no lane (see kSortKeys below)
 template <int VARIANT, int DMODE, bool PACKED, bool FLOAT_ROWS, int kWindow, bool DROP>
-__global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel(FusedArgs F, int dcols, int64_t windows_per_block, int window) {
+__global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel(FusedArgs F, int dcols, int slots, int bulk_window) {
     // float rows where the window's distinct rows need the larger table (epsm_wave_scatter.h, AccFixed64)
     // Rows of the accumulator table: 64-bit fixed point (epsm_wave_scatter.h, AccFixed64: the LDS integer atomic inserts an
     // order of magnitude faster than ds_add_f32, and same-address lanes do not serialise as badly) unless the caller disabled
     // the outlier clamp -- then the terms are unbounded and the sums stay in float.
     constexpr bool kFloatRows = FLOAT_ROWS;
-    // (a window costs 6 bytes of LDS per path: the larger one leaves 224 fixed-point / 384 float rows fewer)
-    constexpr int kRowsFixed = kWindow > 1024 ? EPSM_CP_ROWS_FIXED - 224 * ((kWindow - 1024) / 1024) : EPSM_CP_ROWS_FIXED;
-    constexpr int kRowsFloat = kWindow > 1024 ? EPSM_CP_ROWS_FLOAT - 384 * ((kWindow - 1024) / 1024) : EPSM_CP_ROWS_FLOAT;
+    // (a window costs 4 bytes of LDS per path -- its slot word: 1024 more paths leave 152 fixed-point rows of 28 bytes / 256 float
+    // rows of 16 bytes fewer.  Windows of 2048 paths: 1104 / 1936 rows, 52 376 bytes of LDS in all -- 52 248 with the camera-origin
+    // sum -- of the 53 120 that let three workgroups share a CU.)
+    constexpr int kRowsFixed = kWindow > 1024 ? EPSM_CP_ROWS_FIXED - 152 * ((kWindow - 1024) / 1024) : EPSM_CP_ROWS_FIXED;
+    constexpr int kRowsFloat = kWindow > 1024 ? EPSM_CP_ROWS_FLOAT - 256 * ((kWindow - 1024) / 1024) : EPSM_CP_ROWS_FLOAT;
+    static_assert(kWindow % 256 == 0 && kWindow <= 4096 && kWindow <= cp::kMaxWindowSlots, "a slot below 4096 (WinBase::small), quarter windows on multiples of 64");
+    // the fixed-point rows cannot wrap (epsm_wave_scatter.h, AccFixed64): paths per flush x 16 terms x kLimit <= 2^19
+    static_assert(kFloatRows || (double) kWindow * 16.0 * (double) AccFixed64::kLimit <= 524288.0, "AccFixed64: a window's terms may wrap a row");
     typedef LdsTable<kFloatRows ? kRowsFloat : kRowsFixed, typename std::conditional<kFloatRows, AccFloat, AccFixed64>::type> Table;
     constexpr int kTableSize = Table::kTableSize;
     __shared__ uint32_t s_keys[kTableSize];
@@ -487,14 +517,20 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
     // 12 % of a traced wavefront, half of them with a term) instead of over all N: slot p of the launch is path list[p]
     constexpr bool kList = DROP && PACKED;
     constexpr int kStride = kPer * kWaves, kEntries = kSortKeys * kStride;
-    __shared__ uint32_t s_plan[kWindow];
-    __shared__ uint16_t s_perm[kWindow];
+    __shared__ uint32_t s_slot[kWindow];                             // the window's slot words (epsm_cp_core.h), sorted by m
     __shared__ int s_cnt[kEntries];                                  // [m][j][wave]: histogram, then offsets
     __shared__ int s_cls[kKeys + 2];                                 // first sorted position of class m; [kKeys]: of the paths without a term
     V3<float> gd_acc = zero3<float>();                               // kTangentsInKernel: sum of grad_d over this lane's paths
-    const int64_t n_slots = (kList && F.pk_list) ? (int64_t) lds_(F.pk_list_count, (int64_t) 0) : F.g.N;      // paths the windows run over
-    const int64_t n_windows = (n_slots + window - 1) / window;
-    // (workgroup-uniform: a launch sized for all N).  Under EPSM_OPT_ONE_LAUNCH every workgroup of the grid is a member of its
+    int64_t n_slots = F.g.N;                                         // paths the windows run over
+    if (kList && F.pk_list) { const int64_t cnt = (int64_t) lds_(F.pk_list_count, (int64_t) 0); n_slots = cnt < F.g.N ? cnt : F.g.N; }
+    // The schedule of the launch's windows, and the consecutive ones this workgroup walks: dealt HERE, from n_slots (the host sized
+    // the grid for all N with the same functions; a list's count is known on the device only, and the number of windows is not
+    // monotone in it).
+    // (Out of line, like pixel_offset_large, and once per window: the schedule is a dozen 64-bit scalars that the round loop would
+    // otherwise carry -- inline they cost it 20 spilled vector registers.)
+    const WindowRange WL = launch_windows(n_slots, slots, bulk_window, (int64_t) gridDim.x);
+    const int64_t n_windows = uniform64(WL.first), windows_per_block = uniform64(WL.count);
+    // (workgroup-uniform.)  Under EPSM_OPT_ONE_LAUNCH every workgroup of the grid is a member of its
     // replica (`members` below): one without a window goes on -- through an empty window loop and an empty flush -- to be counted
     if (kList && !F.rep_done && (int64_t) blockIdx.x * windows_per_block >= n_windows) return;
     T.clear();                                                       // ends with a barrier: the table of pointers is visible too
@@ -503,14 +539,20 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
         // a workgroup walks a CONTIGUOUS range of windows: neighbouring pixels keep hitting the rows its table holds
         const int64_t win = (int64_t) blockIdx.x * windows_per_block + wi;
         if (win >= n_windows) break;                                 // workgroup-uniform
-        const int64_t base = win * window;
+        const WindowRange WR = window_range(n_slots, slots, bulk_window, win);
+        const int64_t base = uniform64(WR.first);
+        const int window = __builtin_amdgcn_readfirstlane((int) WR.count);      // <= kWindow; a multiple of 64 except in the launch's last window
         const WinBase WB = win_base<kList>(F, base);
         // ---- plan + histogram of m: thread t plans paths base + j*kThreads + t.  With the caller's tangents a path WITHOUT ANY
         // TERM -- no constraint vertex, first hit not diffuse: 27 % of the bathroom paths -- gets key kKeys, a class sorted behind
         // the others and handed to no round.  (With in-kernel tangents such a path still owes its share of d/d ray.o = -sum grad_d,
         // epsm.py:260-261; taking that here, from coalesced loads of the rays, and keeping the path out of the rounds measured
         // 2.07 -> 2.15 ms on the headline slab: the planning runs before a barrier, a class-0 round under the other waves.)
-        int key[kPer], rank[kPer];
+        // (The plan words stay in registers across the two barriers of the sort, ONE register per path: the sort key takes the
+        // place of m -- bits 16..18, m or kKeys -- and the rank inside the wave's ballot, < 64, the free bits 22..27; what the rounds
+        // need of a plan goes into LDS once, at the path's sorted position: cp::slot_word reads neither field.)
+        constexpr int kRankShift = 22;
+        uint32_t pw[kPer];
         {
             uint32_t fw[kPer];
 #pragma unroll
@@ -530,8 +572,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                 uint32_t plan = VARIANT == EPSM_VARIANT_MANIFOLD ? cp::manifold_plan(w) : cp::caustic_plan(w);
                 plan = in ? (plan | cp::kPlanInRange | ((w & 4u) ? cp::kPlanActive1 : 0u)) : 0u;
                 const bool none = kSortKeys > kKeys && (!in || (cp::plan_m(plan) == 0 && !cp::plan_diffuse1(plan)));
-                key[j] = none ? kKeys : cp::plan_m(plan);
-                if (loc < window) s_plan[loc] = plan;
+                pw[j] = (plan & ~(7u << 16)) | ((none ? (uint32_t) kKeys : (uint32_t) cp::plan_m(plan)) << 16);
             }
         }
 #pragma unroll
@@ -539,8 +580,9 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             const bool has = j * kThreads + (int) threadIdx.x < window;
 #pragma unroll
             for (int q = 0; q < kSortKeys; ++q) {
-                const unsigned long long m = __ballot(has && key[j] == q);
-                if (key[j] == q) rank[j] = __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u));
+                const bool mine = cp::plan_m(pw[j]) == q;
+                const unsigned long long m = __ballot(has && mine);
+                if (mine) pw[j] |= __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u)) << kRankShift;
                 if (lane == 0) s_cnt[(q * kPer + j) * kWaves + wv] = __popcll(m);
             }
         }
@@ -567,12 +609,13 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
 #pragma unroll
         for (int j = 0; j < kPer; ++j) {
             const int loc = j * kThreads + threadIdx.x;
-            if (loc < window) s_perm[s_cnt[(key[j] * kPer + j) * kWaves + wv] + rank[j]] = (uint16_t) loc;
+            const int key = cp::plan_m(pw[j]), rank = (int) ((pw[j] >> kRankShift) & 63u);
+            if (loc < window) s_slot[s_cnt[(key * kPer + j) * kWaves + wv] + rank] = cp::slot_word(pw[j], (uint32_t) loc);
         }
         __syncthreads();
         // ---- rounds: class q has n_q paths on c = max(q,1) lanes each, 64 / c paths per round
         Rounds RS;
-        RS.perm = s_perm; RS.plan = s_plan;
+        RS.slot = s_slot;
 #pragma unroll
         for (int q = 0; q <= kKeys; ++q) RS.cls[q] = __builtin_amdgcn_readfirstlane(s_cls[q]);
         RS.rb[0] = 0;
@@ -598,15 +641,15 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
 #pragma unroll 1
         for (int r = wv; r < n_rounds; r += kWaves) {
             const int q = L.q, c = L.c, k = L.k;
-            const uint32_t plan = L.plan;
+            const uint32_t plan = L.word;                            // the slot word: its bits 0..15 are the plan's
             const bool ok = plan != 0u, first = k == 1;
             const int64_t i = base + L.loc;                          // lanes without a path touch nothing (every load is guarded)
             const Records<PACKED> R{F, s_ptrs, i};
             const int nv = cp::plan_nv(plan);
             const bool live = ok && q > 0;                           // this lane holds a constraint vertex
             const bool has_next = live && k + 1 <= nv;
-            const bool d1 = ok && first && cp::plan_diffuse1(plan);
-            const bool act1 = (plan & cp::kPlanActive1) != 0;
+            const bool d1 = ok && first && cp::slot_diffuse1(plan);
+            const bool act1 = cp::slot_active1(plan);
 
             asm volatile("; EPSM_MARK round_begin");
             // ---- geometry: own vertex; the two neighbours from the lanes that hold them (or from the words fetched for that)
@@ -939,9 +982,15 @@ hipError_t launch(const FusedArgs &F0, int dcols, hipStream_t s) {
         const int64_t w = ((F.g.N + kSlots - 1) / kSlots + 63) / 64 * 64;       // a multiple of 64 paths
         window = (int) (w < 128 ? 128 : w > kSmall ? kSmall : w);
     }
-    const int64_t windows = (F.g.N + window - 1) / window;
-    const int64_t blocks = windows < EPSM_CP_BLOCKS ? windows : EPSM_CP_BLOCKS;
-    const int64_t per = (windows + blocks - 1) / blocks;
+    // Large wavefronts under EPSM_OPT_WORKGROUP_SLOTS = S > 0: the last windows of the launch are half and a quarter of `window`
+    // (cp::window_schedule), so that S workgroup slots run dry within a quarter of a window's time.  OFF by default: with S = 768,
+    // the slots of an MI355X, the headline slab measured 1.668 against 1.648 ms without the taper -- the shorter windows cost more
+    // than the tail they trim -- while a list of few survivors gains (real scene 0.264 against 0.289 ms): MEASUREMENTS.md 27.
+    // Small wavefronts: windows of `window`, never a taper.
+    const int64_t opt_slots = fused_option(EPSM_OPT_WORKGROUP_SLOTS);
+    const int slots = small ? 0 : (int) (opt_slots < (1 << 20) ? opt_slots : (1 << 20));
+    const int64_t windows = cp::window_schedule(F.g.N, slots, window).windows;
+    const int64_t blocks = windows < EPSM_CP_BLOCKS ? windows : EPSM_CP_BLOCKS;      // (the kernel deals the windows to its workgroups)
     // small wavefronts: replicas of the gradient buffers (epsm_grad_scatter.hip, DESIGN.md section 5 "Small wavefronts")
     F.rep = nullptr; F.replicas = 1; F.rep_stride = 0; F.rep_done = nullptr; F.rep_blocks = 0;
     if (small) {
@@ -966,7 +1015,7 @@ hipError_t launch(const FusedArgs &F0, int dcols, hipStream_t s) {
     const bool drop = DMODE != kTangentsInKernel || F.grad_o_sum == nullptr;      // (paths without a term take no lane: kernel, kSortKeys)
 #define EPSM_CP_LAUNCH(FLOAT_ROWS_, WINDOW_, DROP_) \
     hipLaunchKernelGGL((epsm_backward_cp_kernel<VARIANT, DMODE, PACKED, FLOAT_ROWS_, WINDOW_, (DROP_) || DMODE != kTangentsInKernel>), \
-                       dim3((unsigned) blocks), dim3(kThreads), 0, s, F, dcols, per, window)
+                       dim3((unsigned) blocks), dim3(kThreads), 0, s, F, dcols, slots, window)
     if (float_rows) {
         if (small) { if (drop) EPSM_CP_LAUNCH(true, kSmall, true); else EPSM_CP_LAUNCH(true, kSmall, false); }
         else { if (drop) EPSM_CP_LAUNCH(true, kLarge, true); else EPSM_CP_LAUNCH(true, kLarge, false); }

@@ -55,6 +55,72 @@ EPSM_HD bool plan_a(uint32_t p, int k) { return ((p >> (k - 1)) & 1u) != 0; }   
 EPSM_HD bool plan_b(uint32_t p, int k) { return ((p >> (4 + k)) & 1u) != 0; }        // wC / wD
 EPSM_HD bool plan_diffuse1(uint32_t p) { return ((p >> 19) & 1u) != 0; }
 
+// Slot word: what a ROUND keeps of a path -- one 32-bit word per path of a window, in sorted order (the backward kernel's LDS).
+//   bits 0..15  the plan's bits 0..15: plan_nv / plan_a / plan_b / plan_idstar read a slot word as they read a plan word
+//   bit  16     the plan's bit 19 (first logged vertex is diffuse)
+//   bit  17     the plan's bit 21 (first logged vertex is active)
+//   bit  18     the plan's bit 20 (in range): an occupied entry is never 0, and 0 is "no path on this lane"
+//   bits 19..31 the path's slot inside its window (< 8192)
+// m is not kept: it is the class the path was sorted into, which the round index gives.
+constexpr int kSlotShift = 19, kMaxWindowSlots = 1 << (32 - kSlotShift);
+EPSM_HD uint32_t slot_word(uint32_t plan, uint32_t slot) {
+    if (!(plan & kPlanInRange)) return 0u;
+    return (plan & 0xffffu) | (((plan >> 19) & 1u) << 16) | (((plan >> 21) & 1u) << 17) | (1u << 18) | (slot << kSlotShift);
+}
+EPSM_HD bool slot_diffuse1(uint32_t s) { return ((s >> 16) & 1u) != 0; }
+EPSM_HD bool slot_active1(uint32_t s) { return ((s >> 17) & 1u) != 0; }
+EPSM_HD bool slot_in_range(uint32_t s) { return ((s >> 18) & 1u) != 0; }
+EPSM_HD int slot_of(uint32_t s) { return (int) (s >> kSlotShift); }
+
+// ----------------------------------------------------------------------------
+// window schedule: how the n paths (or list slots) of a launch are cut into windows
+// ----------------------------------------------------------------------------
+// S = 0: windows of W, the last one ragged (small wavefronts, and large ones by default).  S > 0 = workgroup slots of the device
+// (EPSM_OPT_WORKGROUP_SLOTS): the end of a launch is TAPERED, so that the S resident workgroups run dry within a quarter of a
+// bulk window's time instead of a whole one --
+//   the last min(n, S W / 4) paths in windows of W / 4, the min(rest, S W / 2) paths before them in windows of W / 2, everything
+//   before that in windows of W; a segment starts on a multiple of W (its start is rounded DOWN: the taper grows by less than
+//   W paths), so only the very last window of a launch is ragged.  W is a multiple of 256: every window starts on a multiple of 64.
+// (The number of windows is not monotone in n -- a path more can move W paths from the quarter windows to the half ones -- so a
+// kernel that learns n on the device deals the windows to its workgroups itself: windows_per_workgroup.)
+struct WindowSchedule {
+    int64_t n;                          // paths
+    int64_t start_half, start_quarter;  // first path of the W / 2 and of the W / 4 segment
+    int64_t win_half, win_quarter;      // ... and their first windows
+    int64_t windows;
+    int w_bulk, w_half, w_quarter;
+};
+EPSM_HD WindowSchedule window_schedule(int64_t n, int64_t S, int W) {
+    WindowSchedule s;
+    s.n = n < 0 ? 0 : n;
+    s.w_bulk = W; s.w_half = S > 0 ? W / 2 : W; s.w_quarter = S > 0 ? W / 4 : W;
+    s.start_half = s.start_quarter = 0;
+    if (S > 0) {
+        const int64_t cap_q = S * (int64_t) (W / 4), cap_h = S * (int64_t) (W / 2);
+        const int64_t tail_q = s.n < cap_q ? s.n : cap_q;
+        s.start_quarter = (s.n - tail_q) / W * W;
+        const int64_t tail_h = s.start_quarter < cap_h ? s.start_quarter : cap_h;
+        s.start_half = (s.start_quarter - tail_h) / W * W;
+    }
+    s.win_half = s.start_half / s.w_bulk;
+    s.win_quarter = s.win_half + (s.start_quarter - s.start_half) / s.w_half;
+    s.windows = s.win_quarter + (s.n - s.start_quarter + s.w_quarter - 1) / s.w_quarter;
+    return s;
+}
+// window `win` (0 <= win < s.windows): its first path and how many it holds
+EPSM_HD void window_at(const WindowSchedule &s, int64_t win, int64_t &first, int &size) {
+    int w;
+    if (win < s.win_half) { first = win * s.w_bulk; w = s.w_bulk; }
+    else if (win < s.win_quarter) { first = s.start_half + (win - s.win_half) * s.w_half; w = s.w_half; }
+    else { first = s.start_quarter + (win - s.win_quarter) * s.w_quarter; w = s.w_quarter; }
+    const int64_t left = s.n - first;
+    size = left < (int64_t) w ? (int) left : w;
+}
+// consecutive windows a workgroup of a grid of `workgroups` walks
+EPSM_HD int64_t windows_per_workgroup(int64_t windows, int64_t workgroups) {
+    return windows <= workgroups ? 1 : (windows + workgroups - 1) / workgroups;
+}
+
 EPSM_HD bool fbit(uint32_t w, int k, uint32_t bit) { return k >= 1 && k <= 5 && ((w >> (5 * (k - 1))) & bit) != 0; }
 
 // term masks of epsm.py:793-802, 852-855, 916-920 (manifold_path of epsm_path_core.h)

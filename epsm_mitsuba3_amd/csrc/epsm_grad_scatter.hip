@@ -134,9 +134,9 @@ static int fill_args(FusedArgs &F, const char *who, int variant, int64_t N, int 
     return EPSM_OK;
 }
 
-// ---- launch options: three process-wide integers, set from the environment by a static initialiser (never by an entry point)
+// ---- launch options: four process-wide integers, set from the environment by a static initialiser (never by an entry point)
 namespace {
-std::atomic<int64_t> g_options[3];
+std::atomic<int64_t> g_options[EPSM_OPT_WORKGROUP_SLOTS + 1];
 struct OptionsInit {
     OptionsInit() {
         const char *e = getenv("EPSM_SMALL_WAVEFRONT");
@@ -145,6 +145,9 @@ struct OptionsInit {
         g_options[EPSM_OPT_REPLICAS] = (off && off[0] == '1') ? 0 : 1;
         const char *one = getenv("EPSM_ONE_LAUNCH");
         g_options[EPSM_OPT_ONE_LAUNCH] = (one && one[0] == '1') ? 1 : 0;
+        const char *ws = getenv("EPSM_WORKGROUP_SLOTS");
+        const int64_t wsv = ws ? atoll(ws) : 0;
+        g_options[EPSM_OPT_WORKGROUP_SLOTS] = wsv > 0 ? wsv : 0;
     }
 } g_options_init;
 }  // namespace
@@ -153,12 +156,12 @@ int64_t fused_option(int option) { return g_options[option].load(std::memory_ord
 }
 extern "C" int epsm_set_option(int option, int64_t value) {
     epsm_host::err_buf()[0] = 0;
-    if (option < 0 || option > EPSM_OPT_ONE_LAUNCH || value < 0) return fail(EPSM_EINVAL, "epsm_set_option: unknown option or negative value");
+    if (option < 0 || option > EPSM_OPT_WORKGROUP_SLOTS || value < 0) return fail(EPSM_EINVAL, "epsm_set_option: unknown option or negative value");
     g_options[option].store(value, std::memory_order_relaxed);
     return EPSM_OK;
 }
 extern "C" int64_t epsm_get_option(int option) {
-    return (option < 0 || option > EPSM_OPT_ONE_LAUNCH) ? -1 : g_options[option].load(std::memory_order_relaxed);
+    return (option < 0 || option > EPSM_OPT_WORKGROUP_SLOTS) ? -1 : g_options[option].load(std::memory_order_relaxed);
 }
 
 extern "C" int epsm_release_workspace(void) {

@@ -99,10 +99,15 @@ struct AccFixed64 {
     // there and its optimiser loop scrubs that to 0, EPSM/optim.py:143-154).  Terms are clamped to +-clip <= 1 before any
     // weight multiplies them, so the slow way is taken by emitter weights beyond ~10^2 only.
     // The limit also bounds the SUM: a row holds |sum| < 2^19; between two flushes a table sees at most one window
-    // of <= 2048 paths (kernel: the table is flushed after every window when a workgroup walks several), and a path adds at
+    // of <= 2048 paths (kernel: the table is flushed after every window when a workgroup walks several; the last windows of a
+    // launch are shorter, never longer), and a path adds at
     // most 3 K + 1 = 16 terms to one row (position, end-point and emitter rows of its K <= 5 vertices + the occluder), each
-    // < 16 in magnitude: 2048 x 16 x 16 = 2^19, never reached -- the int64 cannot wrap.
-    static constexpr float kLimit = 16.f;
+    // < 16 in magnitude: 2048 x 16 x 16 = 2^19, never reached -- the int64 cannot wrap.  The backward kernel asserts
+    // window x 16 x kLimit <= 2^19 on its window constant: a build with windows of up to 4096 paths needs EPSM_FIXED_LIMIT=8.
+#ifndef EPSM_FIXED_LIMIT
+#define EPSM_FIXED_LIMIT 16
+#endif
+    static constexpr float kLimit = (float) EPSM_FIXED_LIMIT;
     __device__ __forceinline__ static bool fits(float x, float y, float z) {
         return fabsf(x) < kLimit && fabsf(y) < kLimit && fabsf(z) < kLimit;        // three compares, each false on NaN (a max3 would skip it)
     }

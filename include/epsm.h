@@ -323,7 +323,8 @@ int epsm_release_workspace(void);
 /* Launch options of the three fused entry points (process-wide; a launch reads them when it is issued).  Their initial values
  * come from the environment ONCE, when the library is loaded -- no entry point calls getenv.
  *   EPSM_OPT_SMALL_WAVEFRONT_PATHS  wavefronts of up to this many paths take the small form (windows of 128 .. 1024 paths,
- *                                   replicas); larger ones walk windows of 2048 paths.  Default 2^20; EPSM_SMALL_WAVEFRONT=<paths>.
+ *                                   replicas); larger ones walk windows of 2048 paths (EPSM_OPT_WORKGROUP_SLOTS: the last ones
+ *                                   of a launch shorter).  Default 2^20; EPSM_SMALL_WAVEFRONT=<paths>.
  *   EPSM_OPT_REPLICAS               1: small wavefronts accumulate into replicas (above); 0: straight into the caller's
  *                                   buffers.  Default 1; EPSM_NO_REPLICAS=1 sets 0.
  *   EPSM_OPT_ONE_LAUNCH             0: the replicas are summed by a second small kernel on the same stream; 1: inside the launch --
@@ -331,11 +332,19 @@ int epsm_release_workspace(void);
  *                                   Default 0 (EPSM_ONE_LAUNCH=1 sets 1): the agent-scope release every workgroup then needs
  *                                   before it is counted is an L2 write-back on this eight-XCD part -- 0.144 ms against 0.086 ms
  *                                   with two launches on the reference's own backward size (524 288 paths, K = 2).
+ *   EPSM_OPT_WORKGROUP_SLOTS        S > 0, the workgroups of the backward kernel the device holds at a time (three per compute
+ *                                   unit: 768 on MI355X): a large wavefront puts its last S x 512 paths into windows of 512 and
+ *                                   the S x 1024 before them into windows of 1024, so that the slots run dry together.  Default 0:
+ *                                   windows of 2048 to the end of the launch -- at S = 768 a slab of 2^24 paths measured 1.2 %
+ *                                   slower with the taper than without, a list of few surviving paths 8 % faster
+ *                                   (MEASUREMENTS.md 27).  EPSM_WORKGROUP_SLOTS=<S>; a small S lets a test meet all three window
+ *                                   sizes in a few thousand paths.
  * Results are the same sums either way (the parity tests run both forms at every size).
  * epsm_set_option returns EPSM_OK or -EINVAL (unknown option, negative value); epsm_get_option returns -1 for an unknown option. */
 #define EPSM_OPT_SMALL_WAVEFRONT_PATHS 0
 #define EPSM_OPT_REPLICAS 1
 #define EPSM_OPT_ONE_LAUNCH 2
+#define EPSM_OPT_WORKGROUP_SLOTS 3
 int epsm_set_option(int option, int64_t value);
 int64_t epsm_get_option(int option);
 
