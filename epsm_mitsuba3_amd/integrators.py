@@ -372,6 +372,15 @@ def _material_slots(scene, params: ParamGrads) -> int:
     return n
 
 
+def _env_pose(scene, params: ParamGrads) -> bool:
+    """Is the envmap's pose attached (``Scene.attach_envmap_pose``)?  ``params.env_rotation`` / ``env_scale`` must exist then."""
+    on = bool(getattr(scene, "env_pose_attached", False))         # (bench.py's SyntheticScene has none)
+    if on and params.env_pose is None:
+        raise ValueError("the envmap's pose is attached: the gradient buffer must come from Scene.param_grads() after "
+                         "attach_envmap_pose")
+    return on
+
+
 def _rigid_slot_count(rigid_slots, params: ParamGrads) -> int:
     """The number of rigid slots (``Scene.rigid_slots``, from ``Scene.attach_rigid``); ``params.rigid`` must hold them."""
     n = len(rigid_slots)
@@ -519,28 +528,30 @@ class PRBIntegrator:
         return _develop_forward(scene, sensor, [self._color_forward(scene, params, sensor, seed, spp)])
 
     def _color_attached(self, scene, params: ParamGrads):
-        """(anything for the colour pass?, textures attached?, number of roughness slots, number of conductor material slots).
-        Neither a colour, a texture, a roughness nor a conductor material attached is nothing this phase differentiates: skipped --
-        and refused by `prb` when geometry is attached instead."""
+        """(anything for the colour pass?, textures attached?, number of roughness slots, number of conductor material slots,
+        the envmap's pose attached?).  Neither a colour, a texture, a roughness, a conductor material nor the envmap's pose
+        attached is nothing this phase differentiates: skipped -- and refused by `prb` when geometry is attached instead."""
         texs = bool(scene.texture_slots)
         n_alpha = _alpha_slots(scene, params)
         n_mat = _material_slots(scene, params)
-        if not scene.color_slots and not texs and not n_alpha and not n_mat and not self.reparam and scene.has_attached_geometry():
+        pose = _env_pose(scene, params)
+        if not scene.color_slots and not texs and not n_alpha and not n_mat and not pose and not self.reparam and scene.has_attached_geometry():
             raise NotImplementedError(
                 "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
                 "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
                 "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
-        return bool(scene.color_slots or texs or n_alpha or n_mat), texs, n_alpha, n_mat
+        return bool(scene.color_slots or texs or n_alpha or n_mat or pose), texs, n_alpha, n_mat, pose
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
         primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``) and the
         roughness tangents ``params.alpha`` of the attached roughconductors (``Scene.trace_alpha_forward``) and the material tangents
-        ``params.conductor`` of the attached conductors (``Scene.trace_material_forward``).  Returns this rank's (primal film,
+        ``params.conductor`` of the attached conductors (``Scene.trace_material_forward``) and the envmap's pose tangent
+        ``params.env_rotation`` / ``env_scale`` (``Scene.trace_envpose_forward``).  Returns this rank's (primal film,
         tangent film), or None when none of them is attached.  (The tangent film is developed with the film's own float-atomic
         weights, while the backward pass of a call with a roughness or a material divides by their fixed-point sums: ~1e-7 apart,
         far inside the transpose identity's bound.)"""
-        any_attached, texs, n_alpha, n_mat = self._color_attached(scene, params)
+        any_attached, texs, n_alpha, n_mat, pose = self._color_attached(scene, params)
         if not any_attached:
             return None
         si, s, spp, _, accum, tiles = _pass_frame(scene, sensor, spp, "color")
@@ -551,6 +562,10 @@ class PRBIntegrator:
         rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
         alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
         mat_t = params.conductor[:n_mat].to(scene.device, torch.float32).contiguous() if n_mat else None
+        pose_t = None
+        if pose:                                                        # [omega, ln(scale)]: d ln(scale) = d scale / scale
+            pose_t = params.env_pose.to(scene.device, torch.float32).clone()
+            pose_t[3] /= scene.envmap_pose()[1]
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
@@ -563,14 +578,16 @@ class PRBIntegrator:
                 dL = dL + scene.trace_alpha_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), alpha_t)
             if n_mat:
                 dL = dL + scene.trace_material_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), mat_t)
+            if pose:
+                dL = dL + scene.trace_envpose_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), pose_t)
             film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        any_attached, texs, n_alpha, n_mat = self._color_attached(scene, params)
+        any_attached, texs, n_alpha, n_mat, pose = self._color_attached(scene, params)
         if not any_attached:
             return
-        exact = bool(n_alpha or n_mat)                                  # the call must repeat bit for bit: fixed-point film weights
+        exact = bool(n_alpha or n_mat or pose)                                # the call must repeat bit for bit: fixed-point film weights
         si, s, spp, world, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         kept, counts = [], None
         for lo, hi in tiles:
@@ -585,7 +602,7 @@ class PRBIntegrator:
             _dist.allreduce_param_grads(accum)
             if exact:
                 _dist.allreduce_param_grads(counts)
-        # (with a roughness or a conductor material attached the call repeats bit for bit: the weights the film adjoint divides by
+        # (with a roughness, a conductor material or the envmap's pose attached the call repeats bit for bit: the weights the film adjoint divides by
         # are the exact sums)
         weight_img = accum[..., 3] if not exact else (counts.double() / _WEIGHT_ONE).float()
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
@@ -595,6 +612,7 @@ class PRBIntegrator:
         rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
         d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
         d_mat = torch.zeros((n_mat, 3, 3), device=scene.device, dtype=torch.float32) if n_mat else None
+        d_pose = torch.zeros(4, device=scene.device, dtype=torch.float32) if pose else None
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
@@ -606,6 +624,8 @@ class PRBIntegrator:
                 scene.trace_alpha_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_alpha)
             if n_mat:                                                   # the conductor material adjoint: one more
                 scene.trace_material_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_mat)
+            if pose:                                                    # the envmap pose adjoint: one more
+                scene.trace_envpose_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_pose)
         contrib = contrib / values.clamp_min(1e-12)
         if world > 1:
             _dist.allreduce_param_grads(contrib)
@@ -623,6 +643,11 @@ class PRBIntegrator:
             if world > 1:
                 _dist.allreduce_param_grads(d_mat)                      # this call's material contribution, once
             params.conductor[:n_mat] += d_mat.to(params.conductor.device)
+        if pose:
+            if world > 1:
+                _dist.allreduce_param_grads(d_pose)                     # this call's pose contribution, once
+            d_pose[3] /= scene.envmap_pose()[1]                         # (the ABI's number is d / d ln(scale))
+            params.env_pose += d_pose.to(params.env_pose.device)
 
 
 class PRBReparamIntegrator(PRBIntegrator):

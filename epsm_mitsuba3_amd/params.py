@@ -42,12 +42,14 @@ class ParamGrads:
     (``Scene.attach_sensor(rotation=True)``).  These two sections exist only when asked for (``n_rigid``, ``cam_rotation``; None
     otherwise) and follow the textures: a buffer constructed without them has the size and the offsets it always had.
     ``conductor (M,3,3)``: d/d [eta, k, specular_reflectance] x rgb of the material slots (``Scene.attach_conductor``), likewise
-    only when asked for (``n_conductors``), at the very END, after ``cam_rotation``.  Vertex
+    only when asked for (``n_conductors``), after ``cam_rotation``.  ``env_rotation (3)``, ``env_scale (1)``: d/d omega of the
+    envmap's ``to_world <- Rot(omega) to_world`` (world axes, at omega = 0) and d/d its ``scale`` (``Scene.attach_envmap_pose``),
+    four floats at the very END, after ``conductor``, only when asked for (``env_pose``; None otherwise).  Vertex
     indices are global: meshes are concatenated and a mesh's rows are ``pos[offset : offset + n_vertices]`` (see ``mesh_slices``)."""
 
     def __init__(self, n_vertices: int, n_bsdfs: int = 0, device="cuda", mesh_slices: Optional[dict] = None, n_colors: int = 0,
                  tex_shapes: Optional[Sequence[Tuple[int, int]]] = None, n_rigid: int = 0, cam_rotation: bool = False,
-                 n_conductors: int = 0):
+                 n_conductors: int = 0, env_pose: bool = False):
         self.V, self.B, self.C = int(n_vertices), int(n_bsdfs), int(n_colors)
         self.tex_shapes = [tex_shape(t) for t in (tex_shapes or [])]
         n0 = 6 * self.V + self.B + 3 + 3 * self.C
@@ -55,7 +57,9 @@ class ParamGrads:
         n1 = n0 + sum(tex_numel(t) for t in self.tex_shapes)
         n = n1 + 6 * self.R + (3 if self.has_cam_rotation else 0)
         self.M = int(n_conductors)
-        self.flat = torch.zeros(n + 9 * self.M, device=device, dtype=torch.float32)
+        self.has_env_pose = bool(env_pose)
+        n2 = n + 9 * self.M
+        self.flat = torch.zeros(n2 + (4 if self.has_env_pose else 0), device=device, dtype=torch.float32)
         self.pos = self.flat[: 3 * self.V].view(self.V, 3)
         self.nrm = self.flat[3 * self.V: 6 * self.V].view(self.V, 3)
         self.alpha = self.flat[6 * self.V: 6 * self.V + self.B]
@@ -68,7 +72,10 @@ class ParamGrads:
             o += tex_numel(t)
         self.rigid = self.flat[n1: n1 + 6 * self.R].view(self.R, 6) if self.R else None
         self.cam_rotation = self.flat[n1 + 6 * self.R: n] if self.has_cam_rotation else None
-        self.conductor = self.flat[n:].view(self.M, 3, 3) if self.M else None
+        self.conductor = self.flat[n: n2].view(self.M, 3, 3) if self.M else None
+        self.env_pose = self.flat[n2: n2 + 4] if self.has_env_pose else None       # [env_rotation, env_scale]
+        self.env_rotation = self.flat[n2: n2 + 3] if self.has_env_pose else None
+        self.env_scale = self.flat[n2 + 3: n2 + 4] if self.has_env_pose else None
         self.mesh_slices = dict(mesh_slices or {})
         self._scratch: Optional[ParamGrads] = None             # scratch(): allocated on first use
 
@@ -83,7 +90,7 @@ class ParamGrads:
         if s is None:
             s = self._scratch = ParamGrads(self.V, self.B, device=self.flat.device, mesh_slices=self.mesh_slices, n_colors=self.C,
                                            tex_shapes=self.tex_shapes, n_rigid=self.R, cam_rotation=self.has_cam_rotation,
-                                           n_conductors=self.M)
+                                           n_conductors=self.M, env_pose=self.has_env_pose)
         return s.zero_()
 
     def texture(self, slot: int) -> torch.Tensor:

@@ -768,6 +768,7 @@ class Scene:
         self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it bounds prb_reparam's tiles (tile_plan)
         self.alpha_slots: Dict[int, int] = {}
         self.material_slots: Dict[int, int] = {}   # conductors attached for the material adjoint (attach_conductor): BSDF index -> slot
+        self.env_pose_attached = False             # the envmap's rotation and scale attached for the pose adjoint (attach_envmap_pose)
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
         self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoints: ("bsdf" | "envmap" | "alpha", index)
         self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
@@ -1269,6 +1270,54 @@ class Scene:
         for dst, src in zip(self._env_buf, new):
             dst.copy_(src)
 
+    def _envmap_index(self, what: str) -> int:
+        """The index of THE envmap in ``emitter_desc`` (what ``c_scene.env`` describes)."""
+        for i, e in enumerate(self.emitter_desc):
+            if e["type"] == 3:
+                return i
+        if any(e["type"] == 2 for e in self.emitter_desc):
+            raise ValueError(f"{what}: a `constant` environment has no pose (attach_radiance takes its radiance)")
+        raise ValueError(f"{what}: the scene has no envmap")
+
+    def attach_envmap_pose(self) -> None:
+        """``dr.enable_grad`` of the envmap's ``to_world`` rotation and of its ``scale`` for the pose adjoint of the colour pass
+        (``epsm_trace_paths_envpose_backward``; PRBIntegrator): ``ParamGrads.env_rotation`` (3) is d/d omega of
+        ``to_world <- Rot(omega) to_world`` (world axes, at omega = 0), ``ParamGrads.env_scale`` (1) d/d ``scale``."""
+        i = self._envmap_index("attach_envmap_pose")
+        if not float(self.emitter_desc[i].get("scale", 1.0)):
+            raise ValueError("attach_envmap_pose: an envmap with scale 0")
+        self.env_pose_attached = True
+
+    def envmap_pose(self):
+        """``(R, scale)``: the (3,3) float64 rotation of the envmap's ``to_world`` and its ``scale``."""
+        e = self.emitter_desc[self._envmap_index("envmap_pose")]
+        R = np.asarray(e["to_world"], np.float64)[:3, :3]
+        return R / np.cbrt(abs(np.linalg.det(R))), float(e.get("scale", 1.0))
+
+    def set_envmap_pose(self, rotation=None, scale=None) -> None:
+        """``params['<emitter>.to_world'] = rotation`` and / or ``params['<emitter>.scale'] = scale`` ``; params.update()``.  A
+        rotation (3,3) rewrites the emitter's ``to_world`` and the host struct's ``env.to_local`` only: no table is rebuilt and
+        nothing is uploaded (the sampling tables live in the emitter's frame).  A scale (> 0) multiplies the device texels in
+        place; the CDF and cell-density tables are normalised and do not change."""
+        e = self.emitter_desc[self._envmap_index("set_envmap_pose")]
+        if rotation is not None:
+            R = np.asarray(rotation.detach().cpu().numpy() if torch.is_tensor(rotation) else rotation, dtype=np.float64)
+            if R.shape != (3, 3) or not np.allclose(R @ R.T, np.eye(3), atol=1e-5) or np.linalg.det(R) < 0:
+                raise ValueError("set_envmap_pose: rotation must be a (3,3) rotation matrix")
+            tw = np.array(e["to_world"], np.float64)
+            tw[:3, :3] = R
+            e["to_world"] = tw
+            self.c_scene.env.to_local[:] = [float(x) for x in R.T.reshape(-1)]       # world -> emitter frame
+        if scale is not None:
+            new, old = float(scale), float(e.get("scale", 1.0))
+            if not (new > 0 and np.isfinite(new)):
+                raise ValueError("set_envmap_pose: scale must be positive and finite")
+            if not old:
+                raise ValueError("set_envmap_pose: an envmap with scale 0 (its bitmap is lost: set_texture gives it a new one)")
+            self._env_buf[0].mul_(new / old)
+            e["bitmap"] = np.ascontiguousarray(e["bitmap"] * np.float32(new / old))
+            e["scale"] = new
+
     def set_alpha(self, bsdf_name: str, alpha: float):
         """``params['<bsdf>.alpha.value'] = alpha; params.update()``: only the BSDF table is rewritten (in place)."""
         self.bsdf_desc[self._refuse_alpha_map("set_alpha", bsdf_name)]["alpha"] = float(alpha)
@@ -1372,7 +1421,7 @@ class Scene:
     def param_grads(self) -> ParamGrads:
         return ParamGrads(self.V, len(self.alpha_slots), device=self.device, mesh_slices=self.mesh_slices,
                           n_colors=len(self.color_slots), tex_shapes=self.texture_shapes(), n_rigid=len(self.rigid_slots),
-                          cam_rotation=self.sensor_rotation, n_conductors=len(self.material_slots))
+                          cam_rotation=self.sensor_rotation, n_conductors=len(self.material_slots), env_pose=self.env_pose_attached)
 
     # -- upload ----------------------------------------------------------------------------------
     def _upload(self):
@@ -1606,7 +1655,7 @@ class Scene:
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
-        if Cn == 0 and not self.texture_slots and not self.alpha_slots and not self.material_slots:
+        if Cn == 0 and not self.texture_slots and not self.alpha_slots and not self.material_slots and not self.env_pose_attached:
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
         film_pos = torch.empty((n, 2), device=dev, dtype=torch.float32)
         radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
@@ -1741,6 +1790,32 @@ class Scene:
         d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
         self._replay("epsm_trace_paths_material_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_material, int(M),
                      d_radiance)
+        return d_radiance
+
+    def trace_envpose_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
+                               grad_pose):
+        """``epsm_trace_paths_envpose_backward``: ADDS d loss / d [omega, ln(scale)] of the envmap over paths [lo, hi) to
+        ``grad_pose`` (4), given the radiance of the primal pass (``trace_color`` with the same seed) and its adjoint.  No
+        atomics: the same call gives the same bits."""
+        n = hi - lo
+        for t_ in (radiance, adj_radiance):
+            self._rows(t_, n, 3)
+        assert grad_pose.is_contiguous() and grad_pose.dtype == torch.float32 and tuple(grad_pose.shape) == (4,)
+        assert grad_pose.device.type == self.device.type
+        nbytes = int(self._runtime()[0].epsm_trace_envpose_workspace_bytes(C.c_int64(n)))
+        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_envpose_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_pose,
+                     work, C.c_size_t(work.numel() * 4))
+
+    def trace_envpose_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangent_pose):
+        """``epsm_trace_paths_envpose_forward``: the transpose of ``trace_envpose_backward`` -- for a tangent
+        [omega, ln(scale)] (4) returns d radiance (n, 3) of paths [lo, hi)."""
+        n = hi - lo
+        self._rows(radiance, n, 3)
+        assert tangent_pose.is_contiguous() and tangent_pose.dtype == torch.float32 and tuple(tangent_pose.shape) == (4,)
+        assert tangent_pose.device.type == self.device.type
+        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
+        self._replay("epsm_trace_paths_envpose_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_pose, d_radiance)
         return d_radiance
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,

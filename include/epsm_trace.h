@@ -487,6 +487,46 @@ int epsm_trace_paths_material_forward(const EpsmScene *scene, const EpsmSensor *
                                       const float *radiance, const float *tangent_material, int M,
                                       float *d_radiance, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * epsm_trace_paths_envpose_backward -- the ENVMAP POSE adjoint of `prb` (sampling, Russian roulette, the MIS weights and the
+ *   world directions detached): paths [path_offset, path_offset + N) are replayed under the primal seed as
+ *   epsm_trace_paths_color traced them, and d loss / d [omega, ln(scale)] of THE environment (EpsmScene.env, kind
+ *   EPSM_ENV_ENVMAP; EPSM_EINVAL for any other kind) is ADDED to grad_pose (4):
+ *     omega    parametrises to_world <- Rot(omega) to_world: world axes, right-handed, at omega = 0 (the sensor rotation's
+ *              convention);
+ *     scale    is the envmap's `scale` property (EpsmEnvironment.texels hold bitmap x scale); the number is d / d ln(scale).
+ *   A replayed path reads the map in the items the texel adjoint forms (epsm_trace_paths_texture_backward): a ray that leaves
+ *   the scene, coef = beta mis along its direction d, and an emitter sample on the map that is not occluded, coef =
+ *   beta bsdf(wo) mis_em / pdf along the sample's direction; its radiance contains sum_items coef_c L_c(d).  Per item
+ *     d / d omega     = sum_c adj_c coef_c (g_c x d), g_c = d L_c / d d of the bilinear lat-long lookup (the torque of the
+ *                       world-direction gradient: the local direction is to_local Rot(-omega) d);
+ *     d / d ln(scale) = sum_c adj_c coef_c L_c(d).
+ *   The map sits at infinity, so turning it moves no visibility boundary in direction space: the detachment loses nothing in
+ *   expectation.  A term that is not finite adds nothing.
+ *     radiance      (N,3) L of every path from the primal pass (epsm_trace_paths_color with the same seed / spp / depths)
+ *     adj_radiance  (N,3) d loss / d L
+ *     grad_pose     (EPSM_ENV_POSE_GRADS) f32 = [omega.x, omega.y, omega.z, ln(scale)], added to
+ *     workspace     device memory, 16-byte aligned, >= epsm_trace_envpose_workspace_bytes(N); scratch
+ *   No float atomics: each workgroup of 128 paths reduces its sums to one row of 4 floats of the workspace, a second launch
+ *   adds the rows in float64 in a fixed order -- two calls with the same arguments give the same bits.  No host
+ *   synchronisation.
+ * epsm_trace_paths_envpose_forward -- its exact transpose: the same replay WRITES d_radiance (N,3), per channel the sum over
+ *   the path's items of their four derivatives x tangent_pose (4), so that sum(adj_radiance * d_radiance) =
+ *   sum(grad_pose * tangent_pose).  One launch.
+ * ------------------------------------------------------------------------- */
+#define EPSM_ENV_POSE_GRADS 4   /* omega.x, omega.y, omega.z, ln(scale) */
+size_t epsm_trace_envpose_workspace_bytes(int64_t N);
+int epsm_trace_paths_envpose_backward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                      uint32_t seed, int spp, int max_depth, int rr_depth,
+                                      int64_t path_offset, int64_t N,
+                                      const float *radiance, const float *adj_radiance, float *grad_pose,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+int epsm_trace_paths_envpose_forward(const EpsmScene *scene, const EpsmSensor *sensor,
+                                     uint32_t seed, int spp, int max_depth, int rr_depth,
+                                     int64_t path_offset, int64_t N,
+                                     const float *radiance, const float *tangent_pose,
+                                     float *d_radiance, void *stream);
+
 /* epsm_film_splat -- ImageBlock::put + weight division (film.develop): accumulates
  * radiance with the reconstruction filter into accum (height,width,4) [r,g,b,w] (atomics);
  * epsm_film_develop divides into image (height,width,3). */
