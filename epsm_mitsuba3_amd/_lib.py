@@ -215,6 +215,11 @@ def declare_tracer(lib):
     lib.epsm_trace_paths_reparam.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    # scene, seed, path_offset, N, max_depth, rays, kappa, exponent, flags, forward, grad_pos, tan_pos, workspace, bytes, stream
+    if hasattr(lib, "epsm_probe_reparam_warps"):           # (the HIP library and tests/host_harness/trace_host.cpp; a host build without it still loads)
+        lib.epsm_probe_reparam_warps.restype = C.c_int
+        lib.epsm_probe_reparam_warps.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                 C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     if hasattr(lib, "epsm_trace_paths_reparam_forward"):   # (the HIP library; of the host builds, tests/host_harness/trace_fwd_host.cpp)
         lib.epsm_trace_reparam_forward_workspace_bytes.restype = C.c_size_t
         lib.epsm_trace_reparam_forward_workspace_bytes.argtypes = [C.c_int64]

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "epsm_trace_core.h"
+#include "epsm_trace_reparam.h"      // the dual-number restatements of the BSDF values (rp::bsdf_eval_t, rp::fresnel_conductor_t)
 
 namespace epsm {
 
@@ -75,6 +76,21 @@ EPSM_HD void probe_row(int what, const float *in, float *out, const EpsmBsdf *bs
         case EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD: {      // in: cos_theta_i, eta, k -> F, d F / d eta, d F / d k
             out[0] = fresnel_conductor_grad(in[0], in[1], in[2], &out[1], &out[2]);
         } break;
+        case EPSM_PROBE_REPARAM_BSDF: {                // in: wi (3), wo (3), which of them carries the seeds (0: wi, else wo) ->
+            // rp::bsdf_eval_t<float> (3), the value of rp::bsdf_eval_t<rp::Dual> (3), d value_c / d seeded_k (3 x 3, row c)
+            const F3 wi = f3(in[0], in[1], in[2]), wo = f3(in[3], in[4], in[5]);
+            const bool seed_wo = in[6] != 0.f;
+            const F3 v = rp::bsdf_eval_t<float>(*bsdf, wi, wo);
+            const V3<rp::Dual> d = rp::bsdf_eval_t<rp::Dual>(*bsdf, rp::seed3<rp::Dual>(wi, seed_wo ? -1 : 0), rp::seed3<rp::Dual>(wo, seed_wo ? 0 : -1));
+            out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = d.x.v; out[4] = d.y.v; out[5] = d.z.v;
+            for (int k = 0; k < 3; ++k) { out[6 + k] = d.x.d[k]; out[9 + k] = d.y.d[k]; out[12 + k] = d.z.d[k]; }
+        } break;
+        case EPSM_PROBE_REPARAM_FRESNEL: {             // in: cos_theta_i, eta, k -> rp::fresnel_conductor_t<rp::Dual>: F, d F / d cos
+            rp::Dual c(in[0]);
+            c.d[0] = 1.f;
+            const rp::Dual F = rp::fresnel_conductor_t<rp::Dual>(c, in[1], in[2]);
+            out[0] = F.v; out[1] = F.d[0];
+        } break;
         default: break;
     }
 }
@@ -111,7 +127,7 @@ EPSM_HD const char *probe_rays_refusal(const EpsmScene *scene, int form, int64_t
 
 EPSM_HD bool probe_needs_bsdf(int what) {
     return what == EPSM_PROBE_MICROFACET || what == EPSM_PROBE_MICROFACET_SAMPLE || what == EPSM_PROBE_BSDF_SAMPLE || what == EPSM_PROBE_BSDF_EVAL ||
-           what == EPSM_PROBE_MICROFACET_DALPHA || what == EPSM_PROBE_BSDF_DALPHA;
+           what == EPSM_PROBE_MICROFACET_DALPHA || what == EPSM_PROBE_BSDF_DALPHA || what == EPSM_PROBE_REPARAM_BSDF;
 }
 EPSM_HD bool probe_needs_sensor(int what) { return what == EPSM_PROBE_PRIMARY_RAY; }
 

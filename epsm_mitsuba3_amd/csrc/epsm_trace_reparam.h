@@ -19,9 +19,15 @@
 // the test probes), or left as a request for a second launch that gives every auxiliary ray its own lane (QueueSink:
 // epsm_trace_reparam.hip).  Every auxiliary ray has its own random stream, so both trace the same rays.
 //
-// PARITY UNPINNED by the reference (no Dr.Jit here): pinned by the reference's OWN recipe for this integrator
+// PARITY: no Dr.Jit here, so the pass as a whole is pinned by the reference's OWN recipe for this integrator
 // (src/integrators/tests/test_ad_integrators.py:833-871: backward gradient against finite differences of the primal
-// image), tests/test_reparam*.py, on the host build of this file and on the GPU.
+// image), tests/test_reparam*.py, on the host build of this file and on the GPU.  Pinned by an independent float64
+// restatement (tests/_warp_oracle.py), request by request in units of the sum of absolute terms: everything a warp computes
+// from its request -- the drawn rays, boundary term, weights, Z, dZ, warp_backward / warp_forward and, on the device, stage 2's
+// request list, lane groups, butterflies and per-triangle rounds (epsm_probe_reparam_warps; tests/test_warp_stage.py,
+// tests/test_gpu_warp_stage.py) -- and the partials of bsdf_eval_t / fresnel_conductor_t against float64 autograd
+// (EPSM_PROBE_REPARAM_BSDF / _FRESNEL).  Still unpinned by anything but the finite differences: surf_t and eval_lo as a whole,
+// the film's Jacobian, and which warps a path asks for (stage 1).
 #pragma once
 
 #include "epsm_trace_core.h"
@@ -148,7 +154,7 @@ template <class T> EPSM_HD T fresnel_conductor_t(T cos_i, float eta_r, float eta
     const T r_p = r_s * (term_3 - term_4) / (term_3 + term_4);
     return (r_s + r_p) * T(0.5f);
 }
-template <class T> EPSM_HD V3<T> bsdf_eval_t(const EpsmBsdf &b, V3<T> wi, V3<T> wo) {
+template <class T> EPSM_HD V3<T> bsdf_eval_restated_t(const EpsmBsdf &b, V3<T> wi, V3<T> wo) {
     if (b.twosided && val(wi.z) < 0.f) { wi.z = -wi.z; wo.z = -wo.z; }
     const T cti = wi.z, cto = wo.z;
     if (!(val(cti) > 0.f && val(cto) > 0.f)) return zero3<T>();
@@ -165,6 +171,16 @@ template <class T> EPSM_HD V3<T> bsdf_eval_t(const EpsmBsdf &b, V3<T> wi, V3<T> 
                       fresnel_conductor_t(c, b.eta[2], b.k[2]) * T(b.reflectance[2]) * result);
     }
     return zero3<T>();                                                    // conductor / dielectric: delta lobes
+}
+// The BSDF value the passes differentiate: the restatement above supplies the PARTIALS, the value is the primal's own --
+// bsdf_eval_pdf's float arithmetic at the same directions (dr.replace_grad(primal, x)).  The two copies round differently (up to
+// 10 ulp for GGX, 120 ulp in Beckmann's tail, whose exp multiplies an ulp of its argument by the argument): tied here, the dual
+// value is the number the tracer shaded with, and eval_lo's ratios f / f0 against bsdf_eval_pdf are exactly 1 in value.
+template <class T> EPSM_HD V3<T> bsdf_eval_t(const EpsmBsdf &b, V3<T> wi, V3<T> wo) {
+    const V3<T> r = bsdf_eval_restated_t<T>(b, wi, wo);
+    F3 primal; float pdf;
+    bsdf_eval_pdf(b, f3(val(wi.x), val(wi.y), val(wi.z)), f3(val(wo.x), val(wo.y), val(wo.z)), primal, pdf);
+    return mk3<T>(replace_value(r.x, primal.x), replace_value(r.y, primal.y), replace_value(r.z, primal.z));
 }
 
 // ---------------------------------------------------------------------------
@@ -950,6 +966,38 @@ EPSM_HD void reparam_forward_one_path(const ReparamFwdArgs &R, int64_t i, const 
     direction_to_film(A.C, pr, cam.dir, fx, fy);
     R.d_radiance[3 * i] = dLo.x; R.d_radiance[3 * i + 1] = dLo.y; R.d_radiance[3 * i + 2] = dLo.z;
     R.d_film[3 * i] = fx; R.d_film[3 * i + 1] = fy; R.d_film[3 * i + 2] = cam.div;
+}
+
+// ---------------------------------------------------------------------------
+// the workspace of both passes and what stage 2 alone needs (host side; device library and host twin alike)
+// ---------------------------------------------------------------------------
+// The requests of N paths (kMaxReq x N, n-major, rounded up to 256 bytes), then one count per path.
+inline size_t request_bytes(int64_t N) { return ((size_t) N * kMaxReq * sizeof(WarpReq) + 255) & ~(size_t) 255; }
+inline size_t workspace_bytes(int64_t N) { return N > 0 ? request_bytes(N) + (size_t) N * sizeof(int) : 0; }
+// The n-th requests of all paths that stage 2 looks at, n = 0 .. n_max - 1: the camera ray + two warps per vertex the depths allow
+inline int warp_stage_n_max(const TraceArgs &A) {
+    const int depth = path_max_depth(A);
+    return 1 + 2 * depth < kMaxReq ? 1 + 2 * depth : kMaxReq;
+}
+// epsm_probe_reparam_warps (include/epsm_trace.h): the arguments of stage 2 on requests the caller wrote.  NULL = fine, R.A (scene,
+// seed, path range, max_depth: what the warp stage reads of it) and R.cfg filled (R zeroed by the caller); otherwise what is
+// wrong.  N == 0 is fine whatever else is passed beside the scene.  `vertex_rows`: grad_pos or tan_pos.
+template <class Args>
+inline const char *probe_warps_fill(Args &R, const EpsmScene *scene, uint32_t seed, int64_t path_offset, int64_t N, int max_depth,
+                                    int reparam_rays, float kappa, float exponent, uint32_t flags, const void *vertex_rows,
+                                    const void *workspace, size_t workspace_size) {
+    if (!scene) return "NULL scene";
+    if (N == 0) return nullptr;
+    if (N < 0 || max_depth < 1 || path_offset < 0 || path_offset + N > 0xFFFFFFFFLL) return "bad N / max_depth / path_offset";
+    if (scene->n_triangles > 0 && (!scene->positions || !scene->normals || !scene->tri || !scene->tri_mesh || !scene->meshes ||
+                                   !scene->bvh || !scene->prim_index || !scene->tri_verts))
+        return "NULL scene array";
+    if (!vertex_rows) return "NULL grad_pos (backward) / tan_pos (forward)";
+    if (!workspace || workspace_size < workspace_bytes(N) || ((uintptr_t) workspace & 15u))
+        return "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
+    if (const char *why = reparam_cfg_fill(R.cfg, scene, 1, reparam_rays, kappa, exponent, flags)) return why;
+    R.A.S = *scene; R.A.seed = seed; R.A.max_depth = max_depth; R.A.path_offset = path_offset; R.A.N = N;
+    return nullptr;
 }
 
 }  // namespace rp

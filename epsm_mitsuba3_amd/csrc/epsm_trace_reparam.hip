@@ -224,10 +224,6 @@ __global__ __launch_bounds__(256) void epsm_reparam_fwd_warp_kernel(rp::ReparamF
     });
 }
 
-size_t req_bytes(int64_t N) { return ((size_t) N * rp::kMaxReq * sizeof(rp::WarpReq) + 255) & ~(size_t) 255; }
-
-size_t workspace_bytes_for(int64_t N) { return N > 0 ? req_bytes(N) + (size_t) N * sizeof(int) : 0; }
-
 // What an entry point launches on: the two halves of its workspace and the grid of the path kernels
 struct Stages { rp::WarpReq *req; int *count; dim3 path_grid; };
 
@@ -243,11 +239,11 @@ bool reparam_begin(const char *what, Args &R, Stages &L, int &rc, const EpsmScen
     const char *why = replay_args_fill(R.A, scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, 1);
     if (!why && N == 0) return false;
     if (!why) why = null_why;
-    if (!why && !workspace_ok(workspace, workspace_bytes, workspace_bytes_for(N))) why = "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
+    if (!why && !workspace_ok(workspace, workspace_bytes, rp::workspace_bytes(N))) why = "workspace: 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N)";
     if (!why) why = rp::reparam_cfg_fill(R.cfg, scene, reparam_max_depth, reparam_rays, kappa, exponent, flags);
     if (why) { rc = fail(EPSM_EINVAL, what, why); return false; }
     L.req = (rp::WarpReq *) workspace;
-    L.count = (int *) ((char *) workspace + req_bytes(N));
+    L.count = (int *) ((char *) workspace + rp::request_bytes(N));
     L.path_grid = dim3((unsigned) ((N + EPSM_RP_THREADS - 1) / EPSM_RP_THREADS));
     return true;
 }
@@ -255,9 +251,7 @@ bool reparam_begin(const char *what, Args &R, Stages &L, int &rc, const EpsmScen
 // Stage 2 of either pass: launch(G, grid, n_max) starts its warp kernel for groups of G = 16, 32 or 64 >= reparam_rays lanes.
 template <class Launch>
 int launch_warp_stage(const TraceArgs &A, int reparam_rays, Launch launch) {
-    // the n-th requests of all paths, n = 0 .. n_max - 1: the camera ray + two warps per vertex the depths allow
-    const int depth = path_max_depth(A);
-    const int n_max = 1 + 2 * depth < rp::kMaxReq ? 1 + 2 * depth : rp::kMaxReq;
+    const int n_max = rp::warp_stage_n_max(A);
     const dim3 grid((unsigned) ((A.N + 255) / 256));                       // one workgroup per 256 paths (N < 2^32: checked)
     if (reparam_rays <= 16) return launch(std::integral_constant<int, 16>(), grid, n_max);
     if (reparam_rays <= 32) return launch(std::integral_constant<int, 32>(), grid, n_max);
@@ -266,7 +260,7 @@ int launch_warp_stage(const TraceArgs &A, int reparam_rays, Launch launch) {
 
 }  // namespace
 
-extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t N) { return workspace_bytes_for(N); }
+extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t N) { return rp::workspace_bytes(N); }
 
 extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor *sensor,
                                         uint32_t seed, int spp, int max_depth, int rr_depth,
@@ -288,6 +282,36 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
     if (rc != EPSM_OK || reparam_max_depth == 0) return rc;
     return launch_warp_stage(R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
         return launch_checked(what, epsm_reparam_warp_kernel<decltype(G)::value>, grid, 256, stream, R, L.req, L.count, n_max);
+    });
+}
+
+// Stage 2 alone on requests the caller wrote (include/epsm_trace.h): the production warp kernels through launch_warp_stage.
+extern "C" int epsm_probe_reparam_warps(const EpsmScene *scene, uint32_t seed, int64_t path_offset, int64_t N, int max_depth, int reparam_rays,
+                                        float kappa, float exponent, uint32_t flags, int forward, float *grad_pos, const float *tan_pos,
+                                        void *workspace, size_t workspace_bytes, void *stream) {
+    static const char *what = "epsm_probe_reparam_warps";
+    epsm_host::err_buf()[0] = 0;
+    rp::WarpReq *req = (rp::WarpReq *) workspace;
+    int *count = (int *) ((char *) workspace + rp::request_bytes(N > 0 ? N : 0));
+    if (forward) {
+        rp::ReparamFwdArgs R = {};
+        if (const char *why = rp::probe_warps_fill(R, scene, seed, path_offset, N, max_depth, reparam_rays, kappa, exponent, flags, tan_pos,
+                                                   workspace, workspace_bytes))
+            return fail(EPSM_EINVAL, what, why);
+        if (N == 0) return EPSM_OK;
+        R.T.pos = tan_pos;
+        return launch_warp_stage(R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+            return launch_checked(what, epsm_reparam_fwd_warp_kernel<decltype(G)::value>, grid, 256, stream, R, req, count, n_max);
+        });
+    }
+    rp::ReparamArgs R = {};
+    if (const char *why = rp::probe_warps_fill(R, scene, seed, path_offset, N, max_depth, reparam_rays, kappa, exponent, flags, grad_pos,
+                                               workspace, workspace_bytes))
+        return fail(EPSM_EINVAL, what, why);
+    if (N == 0) return EPSM_OK;
+    R.G.pos = grad_pos;
+    return launch_warp_stage(R.A, reparam_rays, [&](auto G, dim3 grid, int n_max) {
+        return launch_checked(what, epsm_reparam_warp_kernel<decltype(G)::value>, grid, 256, stream, R, req, count, n_max);
     });
 }
 

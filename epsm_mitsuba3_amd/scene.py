@@ -1854,6 +1854,20 @@ class Scene:
                      d_radiance, d_film, ws, ws_size)
         return d_radiance, d_film
 
+    def probe_reparam_warps(self, seed: int, path_offset: int, n: int, max_depth: int, workspace: torch.Tensor, reparam_rays: int,
+                            kappa: float, exponent: float, antithetic: bool = False, grad_pos=None, tan_pos=None) -> int:
+        """``epsm_probe_reparam_warps`` (test infrastructure): stage 2 of the reparameterised passes alone on the requests and
+        counts the caller wrote into ``workspace`` (uint8, the layout of ``epsm_trace_reparam_workspace_bytes(n)``).  With
+        ``grad_pos`` (V,3) the backward kernel accumulates into it; with ``tan_pos`` (V,3) the forward kernel overwrites every live
+        request's gdir / gdiv with d', div'.  Returns the entry point's code (EPSM_OK or -EINVAL) instead of raising."""
+        assert (grad_pos is None) != (tan_pos is None)
+        lib, stream = self._runtime()
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        return int(lib.epsm_probe_reparam_warps(C.byref(self.c_scene), C.c_uint32(seed & 0xFFFFFFFF), C.c_int64(path_offset), C.c_int64(n),
+                                                int(max_depth), int(reparam_rays), C.c_float(kappa), C.c_float(exponent),
+                                                C.c_uint32(1 if antithetic else 0), 0 if tan_pos is None else 1, ptr(grad_pos), ptr(tan_pos),
+                                                ptr(workspace), C.c_size_t(workspace.numel() * workspace.element_size()), C.c_void_p(stream)))
+
     def film_splat(self, accum: torch.Tensor, sensor: Sensor, film_pos: torch.Tensor, radiance: torch.Tensor) -> None:
         """``epsm_film_splat``: adds the samples of a tile -- film positions (n,2), radiance (n,3) -- into the film accumulator
         ``accum`` (H,W,4) [r,g,b,w] of ``sensor`` with its reconstruction filter."""

@@ -570,12 +570,14 @@ int epsm_film_splat_tangent(int64_t N, const float *film_pos, const float *radia
  *   EPSM_PROBE_MICROFACET_DALPHA  in m (3), v (3); cfg = EpsmBsdf                out d ln D(m) / d alpha, d ln smith_g1(v, m) / d alpha, D(m), smith_g1(v, m)   the closed forms of the roughness adjoint (epsm_trace_paths_bsdf_backward)
  *   EPSM_PROBE_BSDF_DALPHA        in wi (3), wo (3); cfg = EpsmBsdf             out d value / d alpha (3), d ln value / d alpha   roughconductor; 0 for the others
  *   EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD  in cos_theta_i, eta, k                   out F, d F / d eta, d F / d k                the closed forms of the material adjoint (epsm_trace_paths_material_backward; fresnel.h:92-117)
+ *   EPSM_PROBE_REPARAM_BSDF       in wi (3), wo (3), seeded (0: wi, else wo); cfg = EpsmBsdf   out rp::bsdf_eval_t<float> (3), the value of rp::bsdf_eval_t<Dual> (3), d value_c / d seeded_k (3 x 3, row c)   the reparameterised passes' own BSDF values (csrc/epsm_trace_reparam.h), which restate eval_pdf()
+ *   EPSM_PROBE_REPARAM_FRESNEL    in cos_theta_i, eta, k                        out rp::fresnel_conductor_t<Dual>: F, d F / d cos_theta_i
  * in: (n, EPSM_PROBE_IN) floats, out: (n, EPSM_PROBE_OUT) floats, device pointers; cfg: HOST pointer to the struct named
  * above (NULL otherwise).  Not on any hot path. */
 enum { EPSM_PROBE_TEA = 0, EPSM_PROBE_PCG32 = 1, EPSM_PROBE_SAMPLER = 2, EPSM_PROBE_MICROFACET = 3, EPSM_PROBE_MICROFACET_SAMPLE = 4,
        EPSM_PROBE_FRESNEL = 5, EPSM_PROBE_FRESNEL_CONDUCTOR = 6, EPSM_PROBE_RFILTER = 7, EPSM_PROBE_PRIMARY_RAY = 8, EPSM_PROBE_BSDF_SAMPLE = 9,
        EPSM_PROBE_BSDF_EVAL = 10, EPSM_PROBE_MICROFACET_DALPHA = 11, EPSM_PROBE_BSDF_DALPHA = 12,
-       EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD = 13, EPSM_PROBE_COUNT = 14 };
+       EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD = 13, EPSM_PROBE_REPARAM_BSDF = 14, EPSM_PROBE_REPARAM_FRESNEL = 15, EPSM_PROBE_COUNT = 16 };
 #define EPSM_PROBE_IN 8
 #define EPSM_PROBE_OUT 16
 int epsm_probe(int what, int64_t n, const float *in, float *out, const void *cfg, void *stream);
@@ -602,6 +604,29 @@ enum { EPSM_RAYS_LANE = 0, EPSM_RAYS_LANE_ANY = 1, EPSM_RAYS_WAVEFRONT = 2, EPSM
 size_t epsm_probe_rays_workspace_bytes(int form, int64_t n);
 int epsm_probe_rays(const EpsmScene *scene, int form, int64_t n, const float *rays, uint32_t *out,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* epsm_probe_reparam_warps -- STAGE 2 of the reparameterised passes alone (csrc/epsm_trace_reparam.hip: the production kernels
+ * epsm_reparam_warp_kernel<G> / epsm_reparam_fwd_warp_kernel<G> through the launcher the passes use), on warp requests the CALLER
+ * wrote.  Test infrastructure like epsm_probe_rays: it exists so that what a group of lanes makes of one request -- the drawn
+ * auxiliary rays, the harmonic weights, Z, dZ, the adjoint or the tangent -- can be checked request by request against a float64
+ * restatement (tests/_warp_oracle.py, tests/test_gpu_warp_stage.py).  Not on any hot path.
+ *   workspace  device, 16-byte aligned, >= epsm_trace_reparam_workspace_bytes(N), FILLED BY THE CALLER in the layout stage 1 leaves:
+ *              13 x N requests of 16 words, n-major (request n of path i at word 16 (n N + i)):
+ *                o (3), gdiv, d (3), em_inv_dist, gdir (3), fb1, ftri (u32; 0xffffffff: the origin is glued to nothing), fb2, 2 pad
+ *              rounded up to 256 bytes, then N int32 counts.  Of path i the requests n < min(count[i], n_max) are live, n_max =
+ *              min(1 + 2 min(max_depth, 6), 13); nothing else is read or written.  ftri of a live request must be a triangle
+ *              of the scene or 0xffffffff: it is not checked.
+ *   seed, path_offset   the warp of request n of path i draws as WarpId{0xffffffff ^ seed, path_offset + i, n}
+ *   forward == 0  backward: every live request's gdir / gdiv are d loss / d direction, d loss / d divergence; the adjoint is
+ *                 ACCUMULATED into grad_pos (V,3) (rows of EPSM_MESH_POS_ATTACHED meshes).  tan_pos is not read.
+ *   forward != 0  tan_pos (V,3) is read; every live request's gdir / gdiv are overwritten with d', div'.  grad_pos is not read.
+ * EPSM_EINVAL, before any launch: a NULL scene, N < 0, max_depth < 1, path_offset < 0 or path_offset + N > 2^32, a NULL scene array,
+ * a NULL grad_pos (backward) / tan_pos (forward), a workspace that is NULL, misaligned or too small, reparam_rays outside 1..64,
+ * kappa or exponent <= 0, an unknown flag, a scene without triangles.  N = 0 returns EPSM_OK and touches nothing. */
+int epsm_probe_reparam_warps(const EpsmScene *scene, uint32_t seed, int64_t path_offset, int64_t N, int max_depth,
+                             int reparam_rays, float kappa, float exponent, uint32_t flags, int forward,
+                             float *grad_pos /* backward */, const float *tan_pos /* forward */,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * epsm_bvh_build -- the four-wide BVH of T triangles on the device (csrc/epsm_trace_bvh.hip).  Replaces the native scene

@@ -16,7 +16,7 @@ from epsm_mitsuba3_amd import scene as S
 from tests.golden import reference_vectors as RV
 
 PROBE = dict(TEA=0, PCG32=1, SAMPLER=2, MICROFACET=3, MICROFACET_SAMPLE=4, FRESNEL=5, FRESNEL_CONDUCTOR=6, RFILTER=7, PRIMARY_RAY=8,
-             BSDF_SAMPLE=9, BSDF_EVAL=10)
+             BSDF_SAMPLE=9, BSDF_EVAL=10, REPARAM_BSDF=14, REPARAM_FRESNEL=15)
 PROBE_IN, PROBE_OUT = 8, 16
 
 
@@ -231,8 +231,191 @@ def check_bsdf_plugins(probe):
     assert np.isclose(e[0, 3], 1 / math.pi, rtol=1e-5) and e[1, 3] == 0.0
 
 
+# ------------------------------------------------------------------------------------------------- the dual-number BSDF values
+# csrc/epsm_trace_reparam.h restates bsdf_eval_pdf, mf_eval, mf_smith_g1 and fresnel_conductor by hand for dual numbers
+# (rp::bsdf_eval_t, ..): the two copies are tied together here, and the partials checked against float64 autograd of a plain
+# restatement of diffuse.cpp:152-190 / roughconductor.cpp:302-400 / microfacet.h / fresnel.h:92-117.
+# Tolerance as in tests/_warp_stage.py: e32 = the worst |J32 - J64| / A of the SAME restatement run in float32, tol = 8 e32 with a
+# floor of 32 u, and tol <= 1e-3 is asserted; A of a channel's row of partials = its largest |partial| + |value|.  Measured on the
+# reference alone: MEASUREMENTS.md 29.
+REPARAM_ETA, REPARAM_K, REPARAM_REFL = (0.2, 0.9, 1.1), (3.9, 2.4, 2.2), (0.9, 0.8, 0.7)
+
+
+def _fresnel_conductor_torch(cos_i, eta, k):
+    c2 = cos_i * cos_i
+    s2 = 1 - c2
+    s4 = s2 * s2
+    t1 = eta * eta - k * k - s2
+    a2pb2 = torch.sqrt(t1 * t1 + 4 * k * k * eta * eta)
+    a = torch.sqrt(0.5 * (a2pb2 + t1))
+    term1, term2 = a2pb2 + c2, 2 * a * cos_i
+    rs = (term1 - term2) / (term1 + term2)
+    term3, term4 = a2pb2 * c2 + s4, term2 * s2
+    return 0.5 * (rs + rs * (term3 - term4) / (term3 + term4))
+
+
+def _g1_torch(v, m, alpha, distr):
+    tan2 = ((alpha * v[:, 0]) ** 2 + (alpha * v[:, 1]) ** 2) / v[:, 2] ** 2
+    if distr == "beckmann":
+        a = 1 / torch.sqrt(tan2)
+        r = torch.where(a >= 1.6, torch.ones_like(a), (3.535 * a + 2.181 * a * a) / (1 + 2.276 * a + 2.577 * a * a))
+    else:
+        r = 2 / (1 + torch.sqrt(1 + tan2))
+    return torch.where((v * m).sum(dim=1) * v[:, 2] <= 0, torch.zeros_like(r), r)
+
+
+def bsdf_value_torch(kind, distr, alpha, twosided, wi, wo):
+    """(n,3) value incl. the cosine of diffuse / roughconductor, in the dtype of wi"""
+    dt = wi.dtype
+    if twosided:
+        flip = torch.where(wi[:, 2:3] < 0, -1.0, 1.0).to(dt)
+        one = torch.ones_like(flip)
+        wi, wo = wi * torch.cat([one, one, flip], dim=1), wo * torch.cat([one, one, flip], dim=1)
+    live = ((wi[:, 2] > 0) & (wo[:, 2] > 0)).to(dt)[:, None]
+    refl = torch.tensor(REPARAM_REFL, dtype=dt)
+    if kind == "diffuse":
+        return live * refl[None, :] * wo[:, 2:3] / math.pi
+    H = wi + wo
+    H = H / torch.sqrt((H * H).sum(dim=1, keepdim=True))
+    ct2 = H[:, 2] ** 2
+    if distr == "beckmann":
+        D = torch.exp(-((H[:, 0] / alpha) ** 2 + (H[:, 1] / alpha) ** 2) / ct2) / (math.pi * alpha * alpha * ct2 * ct2)
+    else:
+        D = 1 / (math.pi * alpha * alpha * ((H[:, 0] / alpha) ** 2 + (H[:, 1] / alpha) ** 2 + ct2) ** 2)
+    D = torch.where(D * H[:, 2] > 1e-20, D, torch.zeros_like(D))            # microfacet.h: values that small count as zero
+    res = D * _g1_torch(wi, H, alpha, distr) * _g1_torch(wo, H, alpha, distr) / (4 * wi[:, 2])
+    c = (wi * H).sum(dim=1)
+    F = torch.stack([_fresnel_conductor_torch(c, torch.tensor(e, dtype=dt), torch.tensor(k, dtype=dt)) for e, k in zip(REPARAM_ETA, REPARAM_K)], dim=1)
+    return live * F * refl[None, :] * res[:, None]
+
+
+def _jacobian_torch(kind, distr, alpha, twosided, wi, wo, seed_wo, dt):
+    wi, wo = torch.tensor(wi, dtype=dt), torch.tensor(wo, dtype=dt)
+    x = (wo if seed_wo else wi).clone().requires_grad_(True)
+    f = bsdf_value_torch(kind, distr, alpha, twosided, wi if seed_wo else x, x if seed_wo else wo)
+    if not f.requires_grad:                                                 # (diffuse: the value does not depend on wi)
+        return f.double().numpy(), np.zeros((x.shape[0], 3, 3))
+    J = torch.stack([torch.autograd.grad(f[:, c].sum(), x, retain_graph=True)[0] for c in range(3)], dim=1)      # (n, channel, component)
+    return f.detach().double().numpy(), J.double().numpy()
+
+
+def reparam_directions(alpha, twosided, n=200):
+    """wi, wo (n,3) float32 unit vectors with |cos| >= 0.2, both below the surface for half of a twosided BSDF's rows; rows
+    within 1e-3 of Beckmann's a = 1.6 switch of smith_g1 (where the partial jumps) are left out"""
+    rng = np.random.default_rng(int(alpha * 100) + 7 * int(twosided))
+    def dirs(m):
+        z = rng.uniform(0.2, 1.0, size=m)
+        ph = rng.uniform(0, 2 * np.pi, size=m)
+        r = np.sqrt(1 - z * z)
+        return np.stack([r * np.cos(ph), r * np.sin(ph), z], axis=1)
+    wi, wo = dirs(4 * n), dirs(4 * n)
+    # half of the rows: wo = wi mirrored about a half vector inside the lobe (tan theta_h <= 2 alpha), where a rough conductor's
+    # value is not vanishingly small
+    th, ph = np.arctan(alpha * rng.uniform(0, 2, size=4 * n)), rng.uniform(0, 2 * np.pi, size=4 * n)
+    h = np.stack([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)], axis=1)
+    mirrored = 2 * (wi * h).sum(axis=1, keepdims=True) * h - wi
+    use = (np.arange(4 * n) % 2 == 0) & (mirrored[:, 2] >= 0.2)
+    wo[use] = mirrored[use]
+    a = lambda v: 1.0 / (alpha * np.sqrt(v[:, 0] ** 2 + v[:, 1] ** 2) / v[:, 2])
+    keep = (np.abs(a(wi) - 1.6) > 1e-3) & (np.abs(a(wo) - 1.6) > 1e-3)
+    wi, wo = wi[keep][:n], wo[keep][:n]
+    if twosided:
+        wi[::2, 2] *= -1; wo[::2, 2] *= -1
+    return wi.astype(np.float32), wo.astype(np.float32)
+
+
+def _ulps(a, b):
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    return np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32)).astype(np.float64)
+
+
+def _reparam_bsdf_cases():
+    for kind, distr in (("diffuse", "beckmann"), ("roughconductor", "beckmann"), ("roughconductor", "ggx")):
+        for alpha in ((0.3,) if kind == "diffuse" else (0.1, 0.3, 0.7)):
+            for twosided in (0, 1):
+                b = _plugin(kind, twosided=twosided)
+                b.distr, b.alpha = {"beckmann": 0, "ggx": 1}[distr], alpha
+                b.reflectance[:] = REPARAM_REFL; b.eta[:] = REPARAM_ETA; b.k[:] = REPARAM_K
+                wi, wo = reparam_directions(alpha, twosided)
+                assert wi.shape[0] >= 190
+                yield kind, distr, alpha, twosided, b, wi, wo
+
+
+def _reparam_rows(wi, wo, seed_wo):
+    return np.concatenate([wi, wo, np.full((wi.shape[0], 1), seed_wo, np.float32), np.zeros((wi.shape[0], 1), np.float32)], axis=1)
+
+
+def check_reparam_bsdf_values(probe):
+    """rp::bsdf_eval_t<float> and the value of rp::bsdf_eval_t<Dual> against bsdf_eval_pdf (EPSM_PROBE_BSDF_EVAL), bound 4 ulp.
+    Before the dual value was tied to the primal (csrc/epsm_trace_reparam.h, bsdf_eval_t over bsdf_eval_restated_t) the two
+    copies were up to 10 ulp apart for GGX, 28 ulp for Beckmann on values above 1e-3 and 121 ulp in the lobe's tail (x * (1 /
+    alpha) against x / alpha, another order of D G / (4 cos), and exp multiplying an ulp of its argument by the argument); since,
+    0 ulp on both builds (MEASUREMENTS.md 29)."""
+    late = []
+    for kind, distr, alpha, twosided, b, wi, wo in _reparam_bsdf_cases():
+        ev = probe(PROBE["BSDF_EVAL"], _reparam_rows(wi, wo, 0), b)[:, 0:3]
+        assert (ev > 1e-3).mean() >= 0.4                                    # not a table of zeros
+        out = probe(PROBE["REPARAM_BSDF"], _reparam_rows(wi, wo, 0), b)
+        uf, ud = _ulps(out[:, 0:3], ev), _ulps(out[:, 3:6], ev)
+        big = ev > 1e-3
+        print(f"{kind} {distr} alpha {alpha} twosided {twosided}: bsdf_eval_t<float> within {float(uf.max()):.0f} ulp of eval_pdf, <Dual> within "
+              f"{float(ud.max()):.0f} ulp; on values above 1e-3: {float(uf[big].max()):.0f}, {float(ud[big].max()):.0f} ulp")
+        if max(float(uf.max()), float(ud.max())) > 4:
+            late.append((kind, distr, alpha, twosided, float(uf.max()), float(ud.max())))
+    assert not late, late
+
+
+def check_reparam_bsdf_jacobian(probe):
+    """The 3 x 3 partials of rp::bsdf_eval_t<Dual> against float64 autograd of the plain restatement above."""
+    for kind, distr, alpha, twosided, b, wi, wo in _reparam_bsdf_cases():
+        ev = probe(PROBE["BSDF_EVAL"], _reparam_rows(wi, wo, 0), b)[:, 0:3]
+        for seed_wo in (0, 1):
+            out = probe(PROBE["REPARAM_BSDF"], _reparam_rows(wi, wo, seed_wo), b).astype(np.float64)
+            f64, J64 = _jacobian_torch(kind, distr, alpha, twosided, wi, wo, seed_wo, torch.float64)
+            _, J32 = _jacobian_torch(kind, distr, alpha, twosided, wi, wo, seed_wo, torch.float32)
+            A = np.abs(J64).max(axis=2, keepdims=True) + np.abs(f64)[:, :, None]
+            J = out[:, 6:15].reshape(-1, 3, 3)
+            some = np.broadcast_to(A > 0, J64.shape)
+            assert (J32[~some] == 0).all() and (J[~some] == 0).all()            # a value cut to zero has no partials
+            A = np.broadcast_to(A, J64.shape)
+            e32 = float((np.abs(J32 - J64)[some] / A[some]).max())
+            tol = max(8 * e32, 32 * 2.0 ** -24)
+            err = float((np.abs(J - J64)[some] / A[some]).max())
+            print(f"{kind} {distr} alpha {alpha} twosided {twosided} seeds on {'wo' if seed_wo else 'wi'}: e32 {e32:.3g}, tol {tol:.3g}, "
+                  f"worst Jacobian error {err:.3g} A")
+            assert tol <= 1e-3, (kind, distr, alpha, tol)
+            assert np.allclose(f64, ev, rtol=1e-4, atol=1e-12), "the restatement differentiated here is not the BSDF"
+            assert (float(np.abs(J64).max()) > 0 or (kind == "diffuse" and not seed_wo)) and err <= tol, (kind, distr, alpha, twosided, seed_wo, err, tol)
+
+
+def check_reparam_fresnel(probe):
+    cos = np.linspace(0.05, 1.0, 96)
+    for eta, k in zip(REPARAM_ETA + (1.5,), REPARAM_K + (0.0,)):
+        rows = rows_of([[c, eta, k] for c in cos])
+        out = probe(PROBE["REPARAM_FRESNEL"], rows).astype(np.float64)
+        plain = probe(PROBE["FRESNEL_CONDUCTOR"], rows).astype(np.float64)[:, 0]
+        # F = (r_s + r_p) / 2 with r = (x - y) / (x + y): the difference's rounding error is absolute in r (about u x / (x + y)), so
+        # near a zero of r_p (k = 0: Brewster's angle) F keeps no relative digits, and the two copies -- the same dozen float32
+        # operations, contracted differently -- are compared in units of u: 32 u, the floor of every tolerance here
+        gap = float(np.abs(out[:, 0] - plain).max())
+        print(f"fresnel_conductor_t eta {eta} k {k}: value within {gap / 2.0 ** -24:.1f} u of fresnel_conductor")
+        assert gap <= 32 * 2.0 ** -24, (eta, k, gap)
+        g = {}
+        for dt in (torch.float64, torch.float32):
+            x = torch.tensor(rows[:, 0], dtype=dt).requires_grad_(True)
+            F = _fresnel_conductor_torch(x, torch.tensor(eta, dtype=dt), torch.tensor(k, dtype=dt))
+            g[dt] = (F.detach().double().numpy(), torch.autograd.grad(F.sum(), x)[0].double().numpy())
+        A = np.abs(g[torch.float64][1]) + np.abs(g[torch.float64][0])
+        e32 = float((np.abs(g[torch.float32][1] - g[torch.float64][1]) / A).max())
+        tol = max(8 * e32, 32 * 2.0 ** -24)
+        err = float((np.abs(out[:, 1] - g[torch.float64][1]) / A).max())
+        print(f"fresnel_conductor_t eta {eta} k {k}: e32 {e32:.3g}, tol {tol:.3g}, worst d F / d cos error {err:.3g} A")
+        assert tol <= 1e-3 and err <= tol, (eta, k, err, tol)
+
+
 ALL_PROBE_CHECKS = (check_tea, check_pcg32, check_microfacet, check_microfacet_sample, check_fresnel, check_rfilter, check_camera,
-                    check_bsdf_plugins)
+                    check_bsdf_plugins, check_reparam_bsdf_values, check_reparam_bsdf_jacobian,
+                    check_reparam_fresnel)
 
 
 # ------------------------------------------------------------------------------------------------- tangent and scatter

@@ -91,6 +91,46 @@ extern "C" int epsm_trace_paths_reparam(const EpsmScene *scene, const EpsmSensor
 }
 extern "C" size_t epsm_trace_reparam_workspace_bytes(int64_t) { return 0; }
 
+// epsm_probe_reparam_warps (include/epsm_trace.h) on host pointers: the live requests of the caller's workspace one after the
+// other, each as InlineSink::warp / InlineFwdSink::warp treat a warp -- its auxiliary rays traced in turn, summed in double.
+extern "C" int epsm_probe_reparam_warps(const EpsmScene *scene, uint32_t seed, int64_t path_offset, int64_t N, int max_depth, int reparam_rays,
+                                        float kappa, float exponent, uint32_t flags, int forward, float *grad_pos, const float *tan_pos,
+                                        void *workspace, size_t workspace_bytes, void *) {
+    rp::ReparamArgs R = {};
+    if (rp::probe_warps_fill(R, scene, seed, path_offset, N, max_depth, reparam_rays, kappa, exponent, flags,
+                             forward ? (const void *) tan_pos : (const void *) grad_pos, workspace, workspace_bytes))
+        return -22;                                                        // (refused as the device library refuses it)
+    if (N == 0) return 0;
+    rp::WarpReq *req = (rp::WarpReq *) workspace;
+    const int *count = (const int *) ((const char *) workspace + rp::request_bytes(N));
+    const int n_max = rp::warp_stage_n_max(R.A);
+    const EpsmScene &S = R.A.S;
+    const rp::GradOut G{grad_pos, nullptr};
+    const rp::TanIn T{tan_pos, nullptr};
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t i = 0; i < N; ++i) {
+        uint32_t stack[kBvhStack];
+        rp::Warp W;
+        const int c = count[i] < n_max ? count[i] : n_max;
+        for (int n = 0; n < c; ++n) {
+            rp::WarpReq &q = rp::request_slot(req, N, n, i);
+            const F3 o = f3(q.o[0], q.o[1], q.o[2]), d = f3(q.d[0], q.d[1], q.d[2]);
+            rp::warp_collect(S, R.cfg, rp::WarpId{0xffffffffu ^ seed, (uint32_t) (path_offset + i), n}, o, d, BvhStack{stack, 1}, W);
+            if (forward) {
+                const F3 t_o = q.ftri != kNoIndex ? rp::follow_tangent(S, T, q.ftri, q.fb1, q.fb2) : zero3<float>();
+                const rp::WarpTan t = rp::warp_forward(S, T, W, t_o, q.em_inv_dist);
+                q.gdir[0] = t.dir.x; q.gdir[1] = t.dir.y; q.gdir[2] = t.dir.z; q.gdiv = t.div;
+            } else {
+                F3 g_o, g_d;
+                rp::warp_backward(S, G, W, f3(q.gdir[0], q.gdir[1], q.gdir[2]), q.gdiv, g_o, g_d);
+                if (q.em_inv_dist != 0.f) g_o = g_o - (g_d - d * dot(d, g_d)) * q.em_inv_dist;
+                if (q.ftri != kNoIndex) rp::add_follow_point(S, G, q.ftri, q.fb1, q.fb2, g_o);
+            }
+        }
+    }
+    return 0;
+}
+
 // Test probe: the warp field's value and divergence at one ray when only the ray ORIGIN moves with velocity `odot`
 // (forward mode of reparam.py:155-221): out = [V_theta (3), div V_theta, Z].
 extern "C" int epsm_debug_warp(const EpsmScene *scene, const float *o, const float *d, const float *odot, int rays, float kappa,

@@ -107,7 +107,7 @@ def test_fresnel_derivatives_match_float64_autograd():
 def test_header_and_python_agree():
     text = open(os.path.join(ROOT, "include", "epsm_trace.h")).read()
     for name in ("epsm_trace_paths_material_backward", "epsm_trace_paths_material_forward", "epsm_trace_material_workspace_bytes",
-                 f"EPSM_MAX_MATERIAL_GRADS {S.MAX_MATERIAL_GRADS}", "EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD = 13", "EPSM_PROBE_COUNT = 14"):
+                 f"EPSM_MAX_MATERIAL_GRADS {S.MAX_MATERIAL_GRADS}", "EPSM_PROBE_FRESNEL_CONDUCTOR_GRAD = 13", "EPSM_PROBE_COUNT = 16"):
         assert name in text, name
     assert S.MAX_MATERIAL_GRADS == 4 and C.sizeof(S.EpsmBsdf) == 80
     from epsm_mitsuba3_amd import _lib
