@@ -14,6 +14,8 @@ import subprocess
 
 import torch  # loaded before libepsm_hip.so on purpose, see above
 
+from .replays import REPLAYS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 7          # EPSM_ABI_VERSION of include/epsm.h
 LIB_PATH = os.path.join(_HERE, os.environ.get("EPSM_LIB_NAME", "libepsm_hip.so"))   # EPSM_LIB_NAME: A/B builds
@@ -229,22 +231,16 @@ def declare_tracer(lib):
                                                          C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                          C.c_void_p]
     # The colour adjoint's replays: scene, sensor, seed, spp, max_depth, rr_depth, path_offset, N, radiance, then the pass's own.
+    # The pass's own comes from the table of replays.py.
     # (hasattr: the HIP library has them all; of the host builds, tests/host_harness/trace_{tex,bsdf,material,alphamap,envpose}_host.cpp)
     replay_args = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
-    reduced = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]    # adj, grad, slots, workspace, bytes, stream
-    for entry, tail in (("texture_backward", [C.c_void_p] * 4), ("texture_forward", [C.c_void_p] * 4),
-                        ("bsdf_backward", reduced), ("bsdf_forward", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-                        ("material_backward", reduced), ("material_forward", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-                        ("alpha_texture_backward", [C.c_void_p] * 3), ("alpha_texture_forward", [C.c_void_p] * 3),
-                        # adj, grad_pose, workspace, bytes, stream / tangent_pose, d_radiance, stream
-                        ("envpose_backward", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-                        ("envpose_forward", [C.c_void_p] * 3)):
-        if hasattr(lib, "epsm_trace_paths_" + entry):
-            fn = getattr(lib, "epsm_trace_paths_" + entry)
-            fn.restype, fn.argtypes = C.c_int, replay_args + tail
-    for name in ("epsm_trace_bsdf_workspace_bytes", "epsm_trace_material_workspace_bytes", "epsm_trace_envpose_workspace_bytes"):
-        if hasattr(lib, name):
-            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_size_t, [C.c_int64]
+    for r in REPLAYS:
+        for direction in ("backward", "forward"):
+            if hasattr(lib, r.entry(direction)):
+                fn = getattr(lib, r.entry(direction))
+                fn.restype, fn.argtypes = C.c_int, replay_args + r.tail(direction)
+        if r.workspace and hasattr(lib, r.workspace):
+            getattr(lib, r.workspace).restype, getattr(lib, r.workspace).argtypes = C.c_size_t, [C.c_int64]
     lib.epsm_film_splat.restype = C.c_int
     lib.epsm_film_splat.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.epsm_film_develop.restype = C.c_int

@@ -24,10 +24,11 @@ import torch
 
 from . import dist as _dist
 from . import profiler as _prof
+from . import replays as _replays
 from .film import (_WEIGHT_ONE, develop_tangent, film_adjoint, film_adjoint_reparam, film_adjoint_reparam_torch,  # noqa: F401
                    film_splat_tangent, film_splat_tangent_torch, film_weight_counts)
 from .manifold_grad import OUTLIER_CLIP, calc_grad as _calc_grad, manifold_grad_packed
-from .params import ParamGrads, tex_numel, tex_shape, tex_view
+from .params import ParamGrads
 from .records import PackedLog, PackedRecords, PackedScatter
 from .tangent_scatter import (backward_pass, backward_pass_packed, first_vertex_tangent, manifold_grad_scatter,
                               scatter)
@@ -320,67 +321,6 @@ def _develop_forward(scene, sensor: int, films) -> torch.Tensor:
     return out
 
 
-class _TexelBuffers:
-    """One flat buffer of the texel gradients of a backward call, one view per texture slot: (H, W, 3), or (H, W) for a
-    roughness map (``shapes``: ``ParamGrads.tex_shapes``)."""
-
-    def __init__(self, shapes, device):
-        self.flat = torch.zeros(sum(tex_numel(t) for t in shapes), device=device, dtype=torch.float32)
-        self.views, o = [], 0
-        for t in shapes:
-            self.views.append(self.flat[o: o + tex_numel(t)].view(tex_view(t)))
-            o += tex_numel(t)
-
-
-def _texture_shapes(scene, params: ParamGrads, what: str):
-    """The shapes of the attached textures; ``params`` (``what``: "gradient buffer" / "tangent") must be laid out for them."""
-    shapes = [tex_shape(t) for t in scene.texture_shapes()]
-    if params.tex_shapes != shapes:
-        raise ValueError(f"texture slots are attached: the {what} must come from Scene.param_grads() after attach_texture")
-    return shapes
-
-
-def _texture_tangents(scene, params: ParamGrads):
-    """The texel tangents the forward replay reads, per slot: the bitmap's tangent (``ParamGrads.texture``) times its scale."""
-    shapes = _texture_shapes(scene, params, "tangent")
-    return [(params.texture(k).to(scene.device, torch.float32) * scene.texture_scale(k)).contiguous() for k in range(len(shapes))]
-
-
-def _texture_kinds(scene):
-    """(any RGB texture slot -- a diffuse bitmap, the envmap -- attached?, any roughness-map slot?): each has its own replay."""
-    n_alpha = len(scene.alpha_map_slots())
-    return len(scene.texture_slots) > n_alpha, n_alpha > 0
-
-
-def _alpha_slots(scene, params: ParamGrads) -> int:
-    """The number of roughness slots the colour adjoint serves (``Scene.attach_alpha``); ``params.alpha`` must hold them."""
-    n = len(scene.alpha_slots)
-    if n:
-        scene._alpha_slot_count()                   # (refuses more than EPSM_MAX_ALPHA_GRADS)
-        if params.B < n:
-            raise ValueError("roughness slots are attached: the gradient buffer must come from Scene.param_grads() after attach_alpha")
-    return n
-
-
-def _material_slots(scene, params: ParamGrads) -> int:
-    """The number of conductor material slots the colour adjoint serves (``Scene.attach_conductor``); ``params.conductor`` must
-    hold them."""
-    n = len(getattr(scene, "material_slots", ()))                 # (bench.py's SyntheticScene has none)
-    if n and (params.conductor is None or params.M < n):
-        raise ValueError("conductor materials are attached: the gradient buffer must come from Scene.param_grads() after "
-                         "attach_conductor")
-    return n
-
-
-def _env_pose(scene, params: ParamGrads) -> bool:
-    """Is the envmap's pose attached (``Scene.attach_envmap_pose``)?  ``params.env_rotation`` / ``env_scale`` must exist then."""
-    on = bool(getattr(scene, "env_pose_attached", False))         # (bench.py's SyntheticScene has none)
-    if on and params.env_pose is None:
-        raise ValueError("the envmap's pose is attached: the gradient buffer must come from Scene.param_grads() after "
-                         "attach_envmap_pose")
-    return on
-
-
 def _rigid_slot_count(rigid_slots, params: ParamGrads) -> int:
     """The number of rigid slots (``Scene.rigid_slots``, from ``Scene.attach_rigid``); ``params.rigid`` must hold them."""
     n = len(rigid_slots)
@@ -527,73 +467,57 @@ class PRBIntegrator:
         ``render_backward`` with the same seed and spp -- the exact transpose of ``render_backward``."""
         return _develop_forward(scene, sensor, [self._color_forward(scene, params, sensor, seed, spp)])
 
-    def _color_attached(self, scene, params: ParamGrads):
-        """(anything for the colour pass?, textures attached?, number of roughness slots, number of conductor material slots,
-        the envmap's pose attached?).  Neither a colour, a texture, a roughness, a conductor material nor the envmap's pose
-        attached is nothing this phase differentiates: skipped -- and refused by `prb` when geometry is attached instead."""
-        texs = bool(scene.texture_slots)
-        n_alpha = _alpha_slots(scene, params)
-        n_mat = _material_slots(scene, params)
-        pose = _env_pose(scene, params)
-        if not scene.color_slots and not texs and not n_alpha and not n_mat and not pose and not self.reparam and scene.has_attached_geometry():
+    def _color_attached(self, scene, params: ParamGrads, what: str):
+        """(anything for the colour pass?, the attached replays in the order of ``replays.REPLAYS``); ``params`` (``what``:
+        "gradient buffer" / "tangent") must be laid out for their sections -- refused before any pass runs.  Neither a colour nor
+        a replay attached is nothing this phase differentiates: skipped -- and refused by `prb` when geometry is attached
+        instead."""
+        active = _replays.attached(scene)
+        for section in _replays.sections(active):
+            section.check(scene, params, what)
+        if not scene.color_slots and not active and not self.reparam and scene.has_attached_geometry():
             raise NotImplementedError(
                 "prb: geometry is attached but no colour parameter is -- `prb` differentiates colours only (prb.py); the "
                 "gradients of vertex positions through visibility are what `prb_reparam` (its warp field: "
                 "csrc/epsm_trace_reparam.h) or the manifold integrators compute")
-        return bool(scene.color_slots or texs or n_alpha or n_mat or pose), texs, n_alpha, n_mat, pose
+        return bool(scene.color_slots or active), active
 
     def _color_forward(self, scene, params: ParamGrads, sensor=0, seed: int = 0, spp: int = 0):
         """The transpose of ``_color_backward``: per path dL = sum_c sums[:, c] * dcolor[c] / value[c], splatted with the
-        primal pass's film weights, plus the texel tangents of the attached textures (``Scene.trace_texture_forward``) and the
-        roughness tangents ``params.alpha`` of the attached roughconductors (``Scene.trace_alpha_forward``) and the material tangents
-        ``params.conductor`` of the attached conductors (``Scene.trace_material_forward``) and the envmap's pose tangent
-        ``params.env_rotation`` / ``env_scale`` (``Scene.trace_envpose_forward``).  Returns this rank's (primal film,
+        primal pass's film weights, plus d radiance of every attached replay (``Scene.replay_forward``) for its section's tangent:
+        the texels of the attached textures, ``params.alpha`` of the attached roughconductors, ``params.conductor`` of the attached
+        conductors, the envmap's pose ``params.env_rotation`` / ``env_scale``.  Returns this rank's (primal film,
         tangent film), or None when none of them is attached.  (The tangent film is developed with the film's own float-atomic
-        weights, while the backward pass of a call with a roughness or a material divides by their fixed-point sums: ~1e-7 apart,
+        weights, while the backward pass of a call with a reducing replay divides by their fixed-point sums: ~1e-7 apart,
         far inside the transpose identity's bound.)"""
-        any_attached, texs, n_alpha, n_mat, pose = self._color_attached(scene, params)
+        any_attached, active = self._color_attached(scene, params, "tangent")
         if not any_attached:
             return None
         si, s, spp, _, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         d_accum = torch.zeros_like(accum)
         values = scene.color_values()                                   # (C,3)
         t = params.color.to(scene.device, torch.float32)[: values.shape[0]] / values.clamp_min(1e-12)
-        tex_t = _texture_tangents(scene, params) if texs else None
-        rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
-        alpha_t = params.alpha[:n_alpha].to(scene.device, torch.float32).contiguous() if n_alpha else None
-        mat_t = params.conductor[:n_mat].to(scene.device, torch.float32).contiguous() if n_mat else None
-        pose_t = None
-        if pose:                                                        # [omega, ln(scale)]: d ln(scale) = d scale / scale
-            pose_t = params.env_pose.to(scene.device, torch.float32).clone()
-            pose_t[3] /= scene.envmap_pose()[1]
+        tangents = {section: section.tangent(scene, params) for section in _replays.sections(active)}
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
             dL = (sums * t[None]).sum(dim=1)                            # (n,3)
-            if rgb_maps:
-                dL = dL + scene.trace_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
-            if alpha_maps:
-                dL = dL + scene.trace_alpha_texture_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tex_t)
-            if n_alpha:
-                dL = dL + scene.trace_alpha_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), alpha_t)
-            if n_mat:
-                dL = dL + scene.trace_material_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), mat_t)
-            if pose:
-                dL = dL + scene.trace_envpose_forward(si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), pose_t)
+            for r in active:
+                dL = dL + scene.replay_forward(r, si, seed, spp, self._depth(), lo, hi, radiance.contiguous(), tangents[r.section])
             film_splat_tangent(d_accum, film_pos, radiance, dL, None, s.rfilter)
         return accum, d_accum
 
     def _color_backward(self, scene, params: ParamGrads, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
-        any_attached, texs, n_alpha, n_mat, pose = self._color_attached(scene, params)
+        any_attached, active = self._color_attached(scene, params, "gradient buffer")
         if not any_attached:
             return
-        exact = bool(n_alpha or n_mat or pose)                                # the call must repeat bit for bit: fixed-point film weights
+        exact = any(r.reduces for r in active)                          # the call must repeat bit for bit: fixed-point film weights
         si, s, spp, world, accum, tiles = _pass_frame(scene, sensor, spp, "color")
         kept, counts = [], None
         for lo, hi in tiles:
             film_pos, radiance, sums = scene.trace_color(si, seed, spp, self._depth(), lo, hi)
             scene.film_splat(accum, s, film_pos, radiance)
-            kept.append((film_pos, sums, radiance.contiguous() if texs or exact else None))
+            kept.append((film_pos, sums, radiance.contiguous() if active else None))
             if exact:
                 if counts is None:
                     counts = torch.zeros((s.height, s.width), device=scene.device, dtype=torch.int64)
@@ -602,52 +526,26 @@ class PRBIntegrator:
             _dist.allreduce_param_grads(accum)
             if exact:
                 _dist.allreduce_param_grads(counts)
-        # (with a roughness, a conductor material or the envmap's pose attached the call repeats bit for bit: the weights the film adjoint divides by
-        # are the exact sums)
+        # (with a reducing replay attached the call repeats bit for bit: the weights the film adjoint divides by are the exact sums)
         weight_img = accum[..., 3] if not exact else (counts.double() / _WEIGHT_ONE).float()
         g = grad_in.to(scene.device, torch.float32)[: s.height, : s.width, :3]
         values = scene.color_values()                                   # (C,3)
         contrib = torch.zeros_like(values)
-        tex = _TexelBuffers(_texture_shapes(scene, params, "gradient buffer"), scene.device) if texs else None
-        rgb_maps, alpha_maps = _texture_kinds(scene) if texs else (False, False)
-        d_alpha = torch.zeros(n_alpha, device=scene.device, dtype=torch.float32) if n_alpha else None
-        d_mat = torch.zeros((n_mat, 3, 3), device=scene.device, dtype=torch.float32) if n_mat else None
-        d_pose = torch.zeros(4, device=scene.device, dtype=torch.float32) if pose else None
+        # per section (the two texel replays share one): the tensor this call all-reduces, the buffer the replays accumulate into
+        bufs = {section: section.zeros(scene, params) for section in _replays.sections(active)}
         for (lo, hi), (film_pos, sums, radiance) in zip(tiles, kept):
             dL = film_adjoint(film_pos, g, weight_img, s.rfilter)       # (n,3)
             contrib += (sums * dL[:, None, :]).sum(dim=0)
-            if rgb_maps:                                                # the texel adjoint: a replay of the same paths
-                scene.trace_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
-            if alpha_maps:                                              # the roughness maps': its own replay, into the same flat buffer
-                scene.trace_alpha_texture_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), tex.views)
-            if n_alpha:                                                 # the roughness adjoint: another replay of them
-                scene.trace_alpha_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_alpha)
-            if n_mat:                                                   # the conductor material adjoint: one more
-                scene.trace_material_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_mat)
-            if pose:                                                    # the envmap pose adjoint: one more
-                scene.trace_envpose_backward(si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), d_pose)
+            for r in active:                                            # each a replay of the same paths
+                scene.replay_backward(r, si, seed, spp, self._depth(), lo, hi, radiance, dL.contiguous(), bufs[r.section][1])
         contrib = contrib / values.clamp_min(1e-12)
         if world > 1:
             _dist.allreduce_param_grads(contrib)
         params.color += contrib
-        if texs:
+        for section, (flat, buf) in bufs.items():
             if world > 1:
-                _dist.allreduce_param_grads(tex.flat)                   # this call's texel contribution, once
-            for k, v in enumerate(tex.views):
-                params.texture(k).add_(v, alpha=scene.texture_scale(k))   # (an envmap's: w.r.t. the bitmap before its scale)
-        if n_alpha:
-            if world > 1:
-                _dist.allreduce_param_grads(d_alpha)                    # this call's roughness contribution, once
-            params.alpha[:n_alpha] += d_alpha.to(params.alpha.device)
-        if n_mat:
-            if world > 1:
-                _dist.allreduce_param_grads(d_mat)                      # this call's material contribution, once
-            params.conductor[:n_mat] += d_mat.to(params.conductor.device)
-        if pose:
-            if world > 1:
-                _dist.allreduce_param_grads(d_pose)                     # this call's pose contribution, once
-            d_pose[3] /= scene.envmap_pose()[1]                         # (the ABI's number is d / d ln(scale))
-            params.env_pose += d_pose.to(params.env_pose.device)
+                _dist.allreduce_param_grads(flat)                       # this call's contribution to the section, once
+            section.deposit(scene, params, buf)
 
 
 class PRBReparamIntegrator(PRBIntegrator):

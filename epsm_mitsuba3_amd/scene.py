@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from . import dist as _dist
+from . import replays
 from .params import ParamGrads
 
 MESH_VERTEX_NORMALS, MESH_FLIP_NORMALS, MESH_POS_ATTACHED, MESH_NRM_ATTACHED, MESH_IS_MESH, MESH_HAS_UV = 1, 2, 4, 8, 16, 32
@@ -788,6 +789,7 @@ class Scene:
         # MEASUREMENTS.md 10.12)
         self.log_layout = "dense"
         self._wf_workspace = {}        # scratch of the wavefront tracer, one per stream it was used on
+        self._reparam_ws = None        # workspace of the reparameterised passes, kept between calls (_reparam_workspace)
         self._upload()
 
     @property
@@ -1636,9 +1638,33 @@ class Scene:
         """``t`` is what an entry point reads or writes as n rows of w floats."""
         assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (n, w) and t.device.type == self.device.type
 
+    def replay_backward(self, kind: replays.Replay, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance,
+                        adj_radiance, grads) -> None:
+        """The backward entry point of the colour adjoint's replay ``kind`` (replays.REPLAYS) on paths [lo, hi): ACCUMULATES into
+        ``grads`` -- shaped like ``kind.section``'s buffer -- given the radiance of the primal pass (``trace_color`` with the same
+        seed) and its adjoint.  A kind that takes a workspace gets one of the size its ``*_workspace_bytes`` entry asks for."""
+        n, own, work = hi - lo, kind.args(self, grads), ()
+        for t_ in (radiance, adj_radiance):
+            self._rows(t_, n, 3)
+        if kind.workspace:
+            nbytes = int(getattr(self._runtime()[0], kind.workspace)(C.c_int64(n)))
+            ws = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
+            work = (ws, C.c_size_t(ws.numel() * 4))
+        self._replay(kind.entry("backward"), sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, *own, *work)
+
+    def replay_forward(self, kind: replays.Replay, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance,
+                       tangents) -> torch.Tensor:
+        """The transpose of ``replay_backward``: for ``tangents`` -- shaped like ``kind.section``'s tangent -- returns d radiance
+        (n, 3) of paths [lo, hi)."""
+        own = kind.args(self, tangents)
+        self._rows(radiance, hi - lo, 3)
+        d_radiance = torch.empty((hi - lo, 3), device=self.device, dtype=torch.float32)
+        self._replay(kind.entry("forward"), sensor_index, seed, spp, max_depth, lo, hi, radiance, *own, d_radiance)
+        return d_radiance
+
     def _reparam_workspace(self, need: int, device) -> torch.Tensor:
         """The workspace of the reparameterised passes, kept between calls and grown on demand."""
-        ws = getattr(self, "_reparam_ws", None)
+        ws = self._reparam_ws
         if ws is None or ws.numel() < max(need, 16) or ws.device != device:
             ws = self._reparam_ws = torch.empty(max(need, 16), device=device, dtype=torch.uint8)
         return ws
@@ -1655,7 +1681,7 @@ class Scene:
         """``epsm_trace_paths_color``: film positions, radiance and the per-path colour sums (n, C, 3) of paths [lo, hi)."""
         dev = self.device
         n, Cn = hi - lo, len(self.color_slots)
-        if Cn == 0 and not self.texture_slots and not self.alpha_slots and not self.material_slots and not self.env_pose_attached:
+        if Cn == 0 and not replays.attached(self):
             raise ValueError("no colour parameter attached (Scene.attach_color / attach_radiance)")
         film_pos = torch.empty((n, 2), device=dev, dtype=torch.float32)
         radiance = torch.empty((n, 3), device=dev, dtype=torch.float32)
@@ -1670,7 +1696,7 @@ class Scene:
         """The (n_textures) pointer array and the envmap pointer of the texture entry points for per-slot buffers (one per slot of
         ``texture_slots``, shaped like ``_texture_shape``): the RGB slots' (H, W, 3) buffers, or with ``alpha`` the roughness
         maps' (H, W) ones -- each entry point is handed the buffers of its own kind only."""
-        n_tex = len(getattr(self, "_tex_buf", []))
+        n_tex = len(self._tex_buf)
         arr, env = (C.c_void_p * max(1, n_tex))(), None
         assert len(bufs) == len(self.texture_slots)
         for (kind, i), t_ in zip(self.texture_slots, bufs):
@@ -1697,38 +1723,24 @@ class Scene:
         """``epsm_trace_paths_alpha_texture_backward``: ACCUMULATES d loss / d texel of the attached roughness maps over paths
         [lo, hi) into ``grads`` -- one buffer per texture slot, of which the roughness maps' (H, W) ones are written -- given the
         radiance of the primal pass (``trace_color`` with the same seed) and its adjoint."""
-        for t_ in (radiance, adj_radiance):
-            self._rows(t_, hi - lo, 3)
-        arr, _ = self._texture_pointers(grads, alpha=True)
-        self._replay("epsm_trace_paths_alpha_texture_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, arr)
+        self.replay_backward(replays.ALPHA_TEXTURE, sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grads)
 
     def trace_alpha_texture_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangents):
         """``epsm_trace_paths_alpha_texture_forward``: the transpose of ``trace_alpha_texture_backward`` -- for one tangent per
         texture slot (the roughness maps' (H, W) ones are read) returns d radiance (n, 3) of paths [lo, hi)."""
-        self._rows(radiance, hi - lo, 3)
-        arr, _ = self._texture_pointers(tangents, alpha=True)
-        d_radiance = torch.empty((hi - lo, 3), device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_alpha_texture_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, arr, d_radiance)
-        return d_radiance
+        return self.replay_forward(replays.ALPHA_TEXTURE, sensor_index, seed, spp, max_depth, lo, hi, radiance, tangents)
 
     def trace_texture_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                                grads):
         """``epsm_trace_paths_texture_backward``: ACCUMULATES d loss / d texel of paths [lo, hi) into ``grads`` -- one (H, W, 3) buffer
         per texture slot, w.r.t. the texels the tracer reads (an envmap's: its bitmap times ``scale``) -- given the radiance of the
         primal pass (``trace_color`` with the same seed) and its adjoint."""
-        for t_ in (radiance, adj_radiance):
-            self._rows(t_, hi - lo, 3)
-        arr, env = self._texture_pointers(grads)
-        self._replay("epsm_trace_paths_texture_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, arr, env)
+        self.replay_backward(replays.TEXTURE, sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grads)
 
     def trace_texture_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangents):
         """``epsm_trace_paths_texture_forward``: the transpose of ``trace_texture_backward`` -- for one (H, W, 3) texel tangent per
         texture slot returns d radiance (n, 3) of paths [lo, hi)."""
-        self._rows(radiance, hi - lo, 3)
-        arr, env = self._texture_pointers(tangents)
-        d_radiance = torch.empty((hi - lo, 3), device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_texture_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, arr, env, d_radiance)
-        return d_radiance
+        return self.replay_forward(replays.TEXTURE, sensor_index, seed, spp, max_depth, lo, hi, radiance, tangents)
 
     def _alpha_slot_count(self) -> int:
         """The alpha slots the colour adjoint's replay serves: all of them, at most EPSM_MAX_ALPHA_GRADS."""
@@ -1743,80 +1755,37 @@ class Scene:
         """``epsm_trace_paths_bsdf_backward``: ADDS d loss / d alpha of paths [lo, hi) to ``grad_alpha`` (one float per alpha slot,
         ``attach_alpha``) given the radiance of the primal pass (``trace_color`` with the same seed) and its adjoint.  No atomics:
         the same call gives the same bits."""
-        n, B = hi - lo, self._alpha_slot_count()
-        for t_ in (radiance, adj_radiance):
-            self._rows(t_, n, 3)
-        assert grad_alpha.is_contiguous() and grad_alpha.dtype == torch.float32 and grad_alpha.numel() == B
-        assert grad_alpha.device.type == self.device.type
-        nbytes = int(self._runtime()[0].epsm_trace_bsdf_workspace_bytes(C.c_int64(n)))
-        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_bsdf_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_alpha,
-                     int(B), work, C.c_size_t(work.numel() * 4))
+        self.replay_backward(replays.ALPHA, sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_alpha)
 
     def trace_alpha_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangent_alpha):
         """``epsm_trace_paths_bsdf_forward``: the transpose of ``trace_alpha_backward`` -- for one tangent per alpha slot returns
         d radiance (n, 3) of paths [lo, hi)."""
-        n, B = hi - lo, self._alpha_slot_count()
-        self._rows(radiance, n, 3)
-        assert tangent_alpha.is_contiguous() and tangent_alpha.dtype == torch.float32 and tangent_alpha.numel() == B
-        assert tangent_alpha.device.type == self.device.type
-        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_bsdf_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_alpha, int(B), d_radiance)
-        return d_radiance
+        return self.replay_forward(replays.ALPHA, sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_alpha)
 
     def trace_material_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                                 grad_material):
         """``epsm_trace_paths_material_backward``: ADDS d loss / d [eta, k, specular_reflectance] x rgb of paths [lo, hi) to
         ``grad_material`` (M,3,3), one (3,3) per material slot (``attach_conductor``), given the radiance of the primal pass
         (``trace_color`` with the same seed) and its adjoint.  No atomics: the same call gives the same bits."""
-        n, M = hi - lo, len(self.material_slots)
-        for t_ in (radiance, adj_radiance):
-            self._rows(t_, n, 3)
-        assert grad_material.is_contiguous() and grad_material.dtype == torch.float32 and tuple(grad_material.shape) == (M, 3, 3)
-        assert grad_material.device.type == self.device.type
-        nbytes = int(self._runtime()[0].epsm_trace_material_workspace_bytes(C.c_int64(n)))
-        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_material_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance,
-                     grad_material, int(M), work, C.c_size_t(work.numel() * 4))
+        self.replay_backward(replays.MATERIAL, sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_material)
 
     def trace_material_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance,
                                tangent_material):
         """``epsm_trace_paths_material_forward``: the transpose of ``trace_material_backward`` -- for one (3,3) tangent per material
         slot returns d radiance (n, 3) of paths [lo, hi)."""
-        n, M = hi - lo, len(self.material_slots)
-        self._rows(radiance, n, 3)
-        assert tangent_material.is_contiguous() and tangent_material.dtype == torch.float32
-        assert tuple(tangent_material.shape) == (M, 3, 3) and tangent_material.device.type == self.device.type
-        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_material_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_material, int(M),
-                     d_radiance)
-        return d_radiance
+        return self.replay_forward(replays.MATERIAL, sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_material)
 
     def trace_envpose_backward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                                grad_pose):
         """``epsm_trace_paths_envpose_backward``: ADDS d loss / d [omega, ln(scale)] of the envmap over paths [lo, hi) to
         ``grad_pose`` (4), given the radiance of the primal pass (``trace_color`` with the same seed) and its adjoint.  No
         atomics: the same call gives the same bits."""
-        n = hi - lo
-        for t_ in (radiance, adj_radiance):
-            self._rows(t_, n, 3)
-        assert grad_pose.is_contiguous() and grad_pose.dtype == torch.float32 and tuple(grad_pose.shape) == (4,)
-        assert grad_pose.device.type == self.device.type
-        nbytes = int(self._runtime()[0].epsm_trace_envpose_workspace_bytes(C.c_int64(n)))
-        work = torch.empty((max(nbytes, 16) + 3) // 4, device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_envpose_backward", sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_pose,
-                     work, C.c_size_t(work.numel() * 4))
+        self.replay_backward(replays.ENVPOSE, sensor_index, seed, spp, max_depth, lo, hi, radiance, adj_radiance, grad_pose)
 
     def trace_envpose_forward(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, tangent_pose):
         """``epsm_trace_paths_envpose_forward``: the transpose of ``trace_envpose_backward`` -- for a tangent
         [omega, ln(scale)] (4) returns d radiance (n, 3) of paths [lo, hi)."""
-        n = hi - lo
-        self._rows(radiance, n, 3)
-        assert tangent_pose.is_contiguous() and tangent_pose.dtype == torch.float32 and tuple(tangent_pose.shape) == (4,)
-        assert tangent_pose.device.type == self.device.type
-        d_radiance = torch.empty((n, 3), device=self.device, dtype=torch.float32)
-        self._replay("epsm_trace_paths_envpose_forward", sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_pose, d_radiance)
-        return d_radiance
+        return self.replay_forward(replays.ENVPOSE, sensor_index, seed, spp, max_depth, lo, hi, radiance, tangent_pose)
 
     def trace_reparam(self, sensor_index: int, seed: int, spp: int, max_depth: int, lo: int, hi: int, radiance, adj_radiance,
                       adj_film, grad_pos, grad_nrm, reparam_max_depth: int, reparam_rays: int, kappa: float, exponent: float,

@@ -60,10 +60,10 @@ def smooth_map(W, H):
     return np.stack(out, -1).astype(np.float32)
 
 
-def env_scene(kind, size="4x3", device="cpu", res=RES, spp=SPP, to_world=None, bitmap=None, scale=SCALE0, cam=None):
+def env_scene(kind, size="4x3", device="cpu", res=RES, spp=SPP, to_world=None, bitmap=None, scale=SCALE0, cam=None, extra=None):
     """Envmap-only-lit scenes: "floor" a diffuse floor under an occluder, "ball" a roughconductor ball on a diffuse floor,
     "mirror" a `conductor` quad and the background (nothing smooth), "pole" the floor seen by a sensor that looks along the
-    map's polar axis.  16 x 16 @ 4 spp, gaussian filter with border."""
+    map's polar axis.  16 x 16 @ 4 spp, gaussian filter with border.  ``extra``: further entries of the scene dict."""
     W, H = MAPS[size]
     R = R0 if to_world is None else to_world
     tw = np.eye(4); tw[:3, :3] = R
@@ -94,6 +94,7 @@ def env_scene(kind, size="4x3", device="cpu", res=RES, spp=SPP, to_world=None, b
         raise ValueError(kind)
     up = (0, 0, 1) if kind != "pole" else (1, 0, 0)
     d["cam"] = cam or sensor(origin, target, up=up, res=res, spp=spp, rfilter="gaussian", sample_border=True)
+    d.update(extra or {})
     sc = S.Scene.from_dict(d, device=device)
     if str(device) == "cpu":
         on_host_envpose(sc)
