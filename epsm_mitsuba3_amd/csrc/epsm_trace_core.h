@@ -252,6 +252,24 @@ EPSM_HD TriHit intersect(const EpsmScene &S, Ray r, const BvhStack &st) {
 // ---------------------------------------------------------------------------
 // surface interaction (src/render/mesh.cpp:632-892 incl. the EPSM fields :712-720, 784-827)
 // ---------------------------------------------------------------------------
+// The cross product with every product rounded on its own: no fused multiply-add, whatever -ffp-contract says (under
+// -ffp-contract=fast the backend fuses across a `#pragma clang fp contract(off)`, so each product passes through an empty asm
+// statement, which emits nothing and which no combiner looks through).  The geometric normal of a hit is formed with it because
+// coordinate_system() BRANCHES on the sign of n.z: where that component is exactly zero (a triangle with a horizontal normal:
+// eight of an icosphere's 80) two rounded products cancel to +0 in every build, while one fma leaves the rounding error of the
+// other product, +-1e-9 -- and the shading frame's tangents, with them every direction sampled at such a hit, would turn about
+// the normal in the device build and not in the host build of the same code.
+EPSM_HD float rounded_product(float x, float y) {
+    float p = x * y;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(p));
+#endif
+    return p;
+}
+EPSM_HD F3 cross_rounded(F3 a, F3 b) {
+    return f3(rounded_product(a.y, b.z) - rounded_product(a.z, b.y), rounded_product(a.z, b.x) - rounded_product(a.x, b.z),
+              rounded_product(a.x, b.y) - rounded_product(a.y, b.x));
+}
 struct SurfHit {
     bool valid;
     float t;
@@ -292,7 +310,7 @@ EPSM_HD SurfHit surface_interaction(const EpsmScene &S, const Ray &r, const TriH
         h.uvx = t0[0] * h.b0 + t1[0] * h.b1 + t2[0] * h.b2; h.uvy = t0[1] * h.b0 + t1[1] * h.b1 + t2[1] * h.b2;
     }
     h.p = h.p0 * h.b0 + h.p1 * h.b1 + h.p2 * h.b2;                       // mesh.cpp:709
-    h.n = normalize3(cross(h.p1 - h.p0, h.p2 - h.p0));                   // mesh.cpp:729
+    h.n = normalize3(cross_rounded(h.p1 - h.p0, h.p2 - h.p0));           // mesh.cpp:729
     if (m.flags & EPSM_MESH_VERTEX_NORMALS) {                           // mesh.cpp:784-790
         h.n0 = ld3(S.normals + 3 * (int64_t) iv[0]);
         h.n1 = ld3(S.normals + 3 * (int64_t) iv[1]);
@@ -583,10 +601,15 @@ EPSM_HD void bsdf_eval_pdf(const EpsmBsdf &b, F3 wi, F3 wo, F3 &value, float &pd
 // point a ray sees slides over the texture -- its derivative w.r.t. (u, v)
 // ---------------------------------------------------------------------------
 EPSM_HD int tex_wrap(int i, int n) { int r = i % n; return r < 0 ? r + n : r; }
+// what kind of table an EpsmTexture is: an RGB bitmap, a scalar bitmap, or no bitmap but a per-vertex table (vertex_attr_eval)
+EPSM_HD bool tex_is_scalar(const EpsmTexture &T) { return T.channels == EPSM_TEXTURE_SCALAR; }
+EPSM_HD bool tex_is_vertex(const EpsmTexture &T) { return T.channels == EPSM_TEXTURE_VERTEX_RGB; }
+EPSM_HD bool tex_is_rgb(const EpsmTexture &T) { return !tex_is_scalar(T) && !tex_is_vertex(T); }      // (0 or 3)
 EPSM_HD F3 tex_eval(const EpsmTexture &T, float u, float v, F3 *du = nullptr, F3 *dv = nullptr) {
     const float x = u * (float) T.width - 0.5f, y = v * (float) T.height - 0.5f;
     if (du) *du = zero3<float>();
     if (dv) *dv = zero3<float>();
+    if (!tex_is_rgb(T)) return zero3<float>();                            // (not an RGB bitmap: never walked as one)
     if (T.nearest) {
         const int i = tex_wrap((int) floorf(x + 0.5f), T.width), j = tex_wrap((int) floorf(y + 0.5f), T.height);
         return ld3(T.texels + 3 * ((int64_t) j * T.width + i));
@@ -606,6 +629,7 @@ EPSM_HD float tex_eval_1(const EpsmTexture &T, float u, float v, float *du = nul
     const float x = u * (float) T.width - 0.5f, y = v * (float) T.height - 0.5f;
     if (du) *du = 0.f;
     if (dv) *dv = 0.f;
+    if (!tex_is_scalar(T)) return 0.f;                                    // (not a scalar bitmap: never walked as one)
     if (T.nearest) {
         const int i = tex_wrap((int) floorf(x + 0.5f), T.width), j = tex_wrap((int) floorf(y + 0.5f), T.height);
         return T.texels[(int64_t) j * T.width + i];
@@ -619,6 +643,24 @@ EPSM_HD float tex_eval_1(const EpsmTexture &T, float u, float v, float *du = nul
     if (du) *du = ((b - a) * (1.f - fy) + (e - c) * fy) * (float) T.width;
     if (dv) *dv = ((c - a) * (1.f - fx) + (e - b) * fx) * (float) T.height;
     return a * ((1.f - fx) * (1.f - fy)) + b * (fx * (1.f - fy)) + c * ((1.f - fx) * fy) + e * (fx * fy);
+}
+
+// ---------------------------------------------------------------------------
+// `mesh_attribute` textures (src/textures/mesh_attribute.cpp, the mesh's `vertex_color`): a per-vertex table
+// (EPSM_TEXTURE_VERTEX_RGB) read at the hit's three vertices and interpolated with its barycentrics (mesh.cpp eval_attribute_3)
+// ---------------------------------------------------------------------------
+// the table rows of the hit's vertices; false -- and the lookup is to be ignored -- unless all three lie inside the table
+EPSM_HD bool vertex_attr_rows(const EpsmTexture &T, const SurfHit &si, uint32_t &r0, uint32_t &r1, uint32_t &r2) {
+    const uint32_t first = (uint32_t) EPSM_TEXTURE_VERTEX_FIRST(T), count = EPSM_TEXTURE_VERTEX_COUNT(T) > 0 ? (uint32_t) EPSM_TEXTURE_VERTEX_COUNT(T) : 0u;
+    r0 = si.vi[0] - first; r1 = si.vi[1] - first; r2 = si.vi[2] - first;                   // (a row below `first` wraps past count)
+    return tex_is_vertex(T) && T.texels != nullptr && r0 < count && r1 < count && r2 < count;
+}
+// b0 c[vi0] + b1 c[vi1] + b2 c[vi2]; `ok` false where a vertex lies outside the table (the value is then zero and not to be used)
+EPSM_HD F3 vertex_attr_eval(const EpsmTexture &T, const SurfHit &si, bool &ok) {
+    uint32_t r0, r1, r2;
+    ok = vertex_attr_rows(T, si, r0, r1, r2);
+    if (!ok) return zero3<float>();
+    return ld3(T.texels + 3 * (int64_t) r0) * si.b0 + ld3(T.texels + 3 * (int64_t) r1) * si.b1 + ld3(T.texels + 3 * (int64_t) r2) * si.b2;
 }
 
 // ---------------------------------------------------------------------------
@@ -1165,6 +1207,10 @@ EPSM_HD void path_bounce(const TraceArgs &A, int64_t i, int iteration, PathState
         const EpsmTexture &T = S.textures[bsdf.texture];
         if (T.channels == 1) {                                            // (a texture of the other kind is ignored: a 1-channel array is never read as three)
             if (bsdf.type == EPSM_BSDF_ROUGHCONDUCTOR_T) bsdf.alpha = tex_eval_1(T, si.uvx, si.uvy);
+        } else if (tex_is_vertex(T)) {                                    // (a per-vertex table is never walked as a bitmap)
+            bool ok;
+            const F3 r = vertex_attr_eval(T, si, ok);
+            if (ok && bsdf.type == EPSM_BSDF_DIFFUSE_T) { bsdf.reflectance[0] = r.x; bsdf.reflectance[1] = r.y; bsdf.reflectance[2] = r.z; }
         } else if (bsdf.type == EPSM_BSDF_DIFFUSE_T) {
             const F3 r = tex_eval(T, si.uvx, si.uvy);
             bsdf.reflectance[0] = r.x; bsdf.reflectance[1] = r.y; bsdf.reflectance[2] = r.z;

@@ -568,22 +568,39 @@ EPSM_HD T eval_lo(const EpsmScene &S, const Vertex *prev, const Vertex &cur, con
     const V3<T> N0 = sd.template in<T>(c.n0 * fl, kInN), N1 = sd.template in<T>(c.n1 * fl, kInN + 1), N2 = sd.template in<T>(c.n2 * fl, kInN + 2);
     const SurfT<T> h = surf_t<T>(o, d, P0, P1, P2, N0, N1, N2, c.mesh_flags, cur.th.u, cur.th.v, cur.th.t);
     T s = T(0.f);
-    // ---- a `bitmap` reflectance follows the point the ray sees: rho(uv') / rho(uv) per channel multiplies both BSDF values below
+    // ---- a `bitmap` or per-vertex reflectance follows the point the ray sees: rho(uv') / rho(uv) per channel multiplies both BSDF values below
     //      (bitmap.cpp:366-418: the texture lookup is attached to si.uv, mesh.cpp:736-745)
     V3<T> tex = mk3<T>(T(1.f), T(1.f), T(1.f));
     if (cur.bsdf.texture >= 0 && cur.bsdf.texture < S.n_textures && cur.bsdf.type == EPSM_BSDF_DIFFUSE_T &&
         S.textures[cur.bsdf.texture].channels != 1) {
-        float a0[2] = {0.f, 0.f}, a1[2] = {1.f, 0.f}, a2[2] = {0.f, 1.f};                    // no texture coordinates: uv = (b1, b2)
-        if ((c.mesh_flags & EPSM_MESH_HAS_UV) && S.texcoords)
-            for (int j = 0; j < 2; ++j) { a0[j] = S.texcoords[2 * (int64_t) c.vi[0] + j]; a1[j] = S.texcoords[2 * (int64_t) c.vi[1] + j]; a2[j] = S.texcoords[2 * (int64_t) c.vi[2] + j]; }
-        const T b0 = T(1.f) - h.bu - h.bv;
-        const T uu = b0 * T(a0[0]) + h.bu * T(a1[0]) + h.bv * T(a2[0]), vv = b0 * T(a0[1]) + h.bu * T(a1[1]) + h.bv * T(a2[1]);
-        F3 du, dv;
-        const F3 r0 = tex_eval(S.textures[cur.bsdf.texture], c.uvx, c.uvy, &du, &dv);
-        const T eu = uu - T(c.uvx), ev = vv - T(c.uvy);                    // zero value, the derivative of uv
-        if (r0.x > 0.f) tex.x = T(1.f) + (eu * T(du.x) + ev * T(dv.x)) * T(1.f / r0.x);
-        if (r0.y > 0.f) tex.y = T(1.f) + (eu * T(du.y) + ev * T(dv.y)) * T(1.f / r0.y);
-        if (r0.z > 0.f) tex.z = T(1.f) + (eu * T(du.z) + ev * T(dv.z)) * T(1.f / r0.z);
+        F3 r0, du, dv;                                                     // rho at the primal hit, d rho / d (eu, ev)
+        T eu, ev;                                                          // zero value, the derivative of what rho is looked up at
+        bool on = true;
+        if (tex_is_vertex(S.textures[cur.bsdf.texture])) {
+            // ---- a per-vertex reflectance (mesh_attribute.cpp) follows it through the barycentrics themselves: rho = b0 c0 + b1 c1
+            //      + b2 c2 with b0 = 1 - b1 - b2, so (b0' - b0) c0 + (bu - b1) c1 + (bv - b2) c2 = eu (c1 - c0) + ev (c2 - c0)
+            const EpsmTexture &V = S.textures[cur.bsdf.texture];
+            uint32_t q0, q1, q2;
+            on = vertex_attr_rows(V, c, q0, q1, q2);                       // (outside the table: path_bounce kept the constant)
+            r0 = du = dv = zero3<float>();
+            if (on) {
+                const F3 c0 = ld3(V.texels + 3 * (int64_t) q0), c1 = ld3(V.texels + 3 * (int64_t) q1), c2 = ld3(V.texels + 3 * (int64_t) q2);
+                r0 = c0 * c.b0 + c1 * c.b1 + c2 * c.b2;                    // (vertex_attr_eval)
+                du = c1 - c0; dv = c2 - c0;
+            }
+            eu = h.bu - T(c.b1); ev = h.bv - T(c.b2);
+        } else {
+            float a0[2] = {0.f, 0.f}, a1[2] = {1.f, 0.f}, a2[2] = {0.f, 1.f};                    // no texture coordinates: uv = (b1, b2)
+            if ((c.mesh_flags & EPSM_MESH_HAS_UV) && S.texcoords)
+                for (int j = 0; j < 2; ++j) { a0[j] = S.texcoords[2 * (int64_t) c.vi[0] + j]; a1[j] = S.texcoords[2 * (int64_t) c.vi[1] + j]; a2[j] = S.texcoords[2 * (int64_t) c.vi[2] + j]; }
+            const T b0 = T(1.f) - h.bu - h.bv;
+            const T uu = b0 * T(a0[0]) + h.bu * T(a1[0]) + h.bv * T(a2[0]), vv = b0 * T(a0[1]) + h.bu * T(a1[1]) + h.bv * T(a2[1]);
+            r0 = tex_eval(S.textures[cur.bsdf.texture], c.uvx, c.uvy, &du, &dv);
+            eu = uu - T(c.uvx); ev = vv - T(c.uvy);
+        }
+        if (on && r0.x > 0.f) tex.x = T(1.f) + (eu * T(du.x) + ev * T(dv.x)) * T(1.f / r0.x);
+        if (on && r0.y > 0.f) tex.y = T(1.f) + (eu * T(du.y) + ev * T(dv.y)) * T(1.f / r0.y);
+        if (on && r0.z > 0.f) tex.z = T(1.f) + (eu * T(du.z) + ev * T(dv.z)) * T(1.f / r0.z);
     }
     // ---- Lr_dir = beta * mis * bsdf(wi, to_local(d_em')) * em_weight (prb_reparam.py:413-418)
     if (cur.active_em && (cur.Lr_dir.x != 0.f || cur.Lr_dir.y != 0.f || cur.Lr_dir.z != 0.f)) {

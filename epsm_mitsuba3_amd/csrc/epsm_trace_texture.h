@@ -1,5 +1,6 @@
 // epsm_trace_texture.h -- per-path code of the texel adjoint (include/epsm_trace.h, epsm_trace_paths_texture_backward /
-// epsm_trace_paths_texture_forward): d L / d texel of the `bitmap` reflectances of diffuse BSDFs and of the envmap's bitmap.
+// epsm_trace_paths_texture_forward): d L / d texel of the `bitmap` reflectances of diffuse BSDFs and of the envmap's bitmap, and
+// d L / d colour of the per-vertex reflectances (`mesh_attribute`, EPSM_TEXTURE_VERTEX_RGB: a footprint of three vertices).
 //
 // A path is replayed through path_bounce (epsm_trace_core.h) under the primal seed, as epsm_trace_paths_color traced it; an
 // observer (TexObserver) turns each bounce into at most two ITEMS -- a footprint of up to four texels of one buffer, their
@@ -7,7 +8,7 @@
 // (backward) or gathers sum(weight x tangent) x coef into the path's radiance tangent (forward): one is the other's transpose.
 // PRB's rules (prb.py), sampling, Russian roulette and MIS detached:
 //   * diffuse vertex k whose reflectance is a texture with a buffer: every term the path collects after its emission at k
-//     (NEE at k and everything downstream) is linear in rho_k = tex_eval(uv_k), channel by channel:
+//     (NEE at k and everything downstream) is linear in rho_k = tex_eval(uv_k) (vertex_attr_eval at a per-vertex table), channel by channel:
 //     coef = L_after_k / rho_k, L_after_k = radiance - (L up to and including Le_k).  Where rho_k,c = 0 the coefficient is 0
 //     (prb.py's inv_bsdf_val_det select): the terms through k are 0 in that channel and their derivative is not recovered.
 //   * a ray that leaves the scene: Le = beta env(d) mis, coef = beta mis.
@@ -49,24 +50,37 @@ EPSM_HD void item_clear(Item &it) {
     it.coef = zero3<float>();
 }
 
-// the texels tex_eval interpolates at (u, v), same wrap
+// the texels tex_eval interpolates at (u, v), same wrap.  A per-vertex table has no such footprint (vertex_footprint): it is read
+// as a 1 x 1 bitmap with zero weights, none of its words taken for a size.
 EPSM_HD void texture_footprint(const EpsmTexture &T, float u, float v, Item &it) {
-    const float x = u * (float) T.width - 0.5f, y = v * (float) T.height - 0.5f;
+    const bool bitmap = !tex_is_vertex(T);
+    const int W = bitmap ? T.width : 1, H = bitmap ? T.height : 1;
+    const float x = u * (float) W - 0.5f, y = v * (float) H - 0.5f;
     if (T.nearest) {
-        const int i = tex_wrap((int) floorf(x + 0.5f), T.width), j = tex_wrap((int) floorf(y + 0.5f), T.height);
+        const int i = tex_wrap((int) floorf(x + 0.5f), W), j = tex_wrap((int) floorf(y + 0.5f), H);
         it.i0 = (uint32_t) i; it.j0 = (uint32_t) j;
-        it.off[0] = it.off[1] = it.off[2] = it.off[3] = (uint32_t) (j * T.width + i);
-        it.w[0] = 1.f; it.w[1] = it.w[2] = it.w[3] = 0.f;
+        it.off[0] = it.off[1] = it.off[2] = it.off[3] = (uint32_t) (j * W + i);
+        it.w[0] = bitmap ? 1.f : 0.f; it.w[1] = it.w[2] = it.w[3] = 0.f;
         return;
     }
     const float fxf = floorf(x), fyf = floorf(y);
-    const int i0 = tex_wrap((int) fxf, T.width), j0 = tex_wrap((int) fyf, T.height), i1 = tex_wrap((int) fxf + 1, T.width),
-              j1 = tex_wrap((int) fyf + 1, T.height);
-    const float fx = x - fxf, fy = y - fyf;
+    const int i0 = tex_wrap((int) fxf, W), j0 = tex_wrap((int) fyf, H), i1 = tex_wrap((int) fxf + 1, W), j1 = tex_wrap((int) fyf + 1, H);
+    const float fx = x - fxf, fy = y - fyf, on = bitmap ? 1.f : 0.f;
     it.i0 = (uint32_t) i0; it.j0 = (uint32_t) j0;
-    it.off[0] = (uint32_t) (j0 * T.width + i0); it.off[1] = (uint32_t) (j0 * T.width + i1);
-    it.off[2] = (uint32_t) (j1 * T.width + i0); it.off[3] = (uint32_t) (j1 * T.width + i1);
-    it.w[0] = (1.f - fx) * (1.f - fy); it.w[1] = fx * (1.f - fy); it.w[2] = (1.f - fx) * fy; it.w[3] = fx * fy;
+    it.off[0] = (uint32_t) (j0 * W + i0); it.off[1] = (uint32_t) (j0 * W + i1);
+    it.off[2] = (uint32_t) (j1 * W + i0); it.off[3] = (uint32_t) (j1 * W + i1);
+    it.w[0] = (1.f - fx) * (1.f - fy) * on; it.w[1] = fx * (1.f - fy) * on; it.w[2] = (1.f - fx) * fy * on; it.w[3] = fx * fy * on;
+}
+// the three rows vertex_attr_eval interpolates at a hit, their weights its barycentrics; the fourth entry repeats the third with
+// weight 0.  The footprint's name is the TRIANGLE (i0 = triangle id, j0 = 0): lanes in two triangles may share a vertex, never a
+// footprint, and lanes merged under one name add under the last lane's rows.  False where a vertex lies outside the table.
+EPSM_HD bool vertex_footprint(const EpsmTexture &T, const SurfHit &si, Item &it) {
+    uint32_t r0, r1, r2;
+    if (!vertex_attr_rows(T, si, r0, r1, r2)) return false;
+    it.i0 = si.tri; it.j0 = 0u;
+    it.off[0] = r0; it.off[1] = r1; it.off[2] = r2; it.off[3] = r2;
+    it.w[0] = si.b0; it.w[1] = si.b1; it.w[2] = si.b2; it.w[3] = 0.f;
+    return true;
 }
 // the texels env_eval interpolates along the world direction d; column W of EpsmEnvironment.texels is column 0 of the bitmap
 EPSM_HD void env_footprint(const EpsmEnvironment &E, F3 d, Item &it) {
@@ -118,8 +132,11 @@ struct TexObserver {
                 const F3 after = radiance - (L + Le);                           // (the order in which InlineVis::direct sums)
                 a.coef = finite_or_zero3(f3(rho.x != 0.f ? after.x / rho.x : 0.f, rho.y != 0.f ? after.y / rho.y : 0.f,
                                             rho.z != 0.f ? after.z / rho.z : 0.f));
-                texture_footprint(S.textures[bsdf.texture], si.uvx, si.uvy, a);
+                const EpsmTexture &tex = S.textures[bsdf.texture];
                 a.b = (uint32_t) k; a.on = true;
+                // (a per-vertex table with a vertex outside it: path_bounce ignored the lookup, rho is not the table's)
+                if (tex_is_vertex(tex)) a.on = vertex_footprint(tex, si, a);
+                else texture_footprint(tex, si.uvx, si.uvy, a);
             }
         } else if (env_on) {                                                   // the ray left the scene (path_bounce's Le)
             float em_pdf = prev_bsdf_delta ? 0.f : env_pdf(S, dir);

@@ -28,6 +28,7 @@ from . import dist as _dist
 from . import replays
 from .params import ParamGrads
 
+TEXTURE_VERTEX_RGB = 4                                         # EPSM_TEXTURE_VERTEX_RGB
 MESH_VERTEX_NORMALS, MESH_FLIP_NORMALS, MESH_POS_ATTACHED, MESH_NRM_ATTACHED, MESH_IS_MESH, MESH_HAS_UV = 1, 2, 4, 8, 16, 32
 MAX_ALPHA_GRADS = 8          # EPSM_MAX_ALPHA_GRADS (include/epsm_trace.h; tests/test_alpha_abi.py holds the two together)
 MAX_MATERIAL_GRADS = 4       # EPSM_MAX_MATERIAL_GRADS (include/epsm_trace.h; tests/test_material_adjoint.py holds the two together)
@@ -234,10 +235,19 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def load_ply(path: str):
+def _srgb_to_linear(c: np.ndarray) -> np.ndarray:
+    """The sRGB decode of values in [0, 1] (the inverse of ``optim.linear_to_srgb``)."""
+    c = np.asarray(c, dtype=np.float64)
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+
+
+def load_ply(path: str, with_color: bool = False):
     """Minimal PLY reader (src/shapes/ply.cpp reads the same subset for the experiment files, e.g. EPSM/exp/glassslab.py:150):
     ascii / binary_little_endian / binary_big_endian; element ``vertex`` with x y z (and nx ny nz), element ``face`` with one list
-    property (``vertex_indices`` / ``vertex_index``), polygons triangulated as fans.  Returns (v (V,3), n (V,3) | None, f (F,3))."""
+    property (``vertex_indices`` / ``vertex_index``), polygons triangulated as fans.  Returns (v (V,3), n (V,3) | None, f (F,3)).
+    ``with_color``: a fourth value, the ``vertex_color`` attribute (V,3) float32 or None -- the vertex properties ``r g b`` or
+    ``red green blue`` as linear RGB: float properties as they are, integer ones normalised by their type's range and sRGB-decoded
+    (ply.cpp:561-563); an alpha property is ignored."""
     with open(path, "rb") as fh:
         if fh.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -261,6 +271,7 @@ def load_ply(path: str):
             raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
         end = "<" if fmt != "binary_big_endian" else ">"
         verts = faces = None
+        vertex_types = {}
         tokens = fh.read().split() if fmt == "ascii" else None
         pos = 0
         for el in elements:
@@ -278,6 +289,7 @@ def load_ply(path: str):
                     table = {nm: rec[nm].astype(np.float64) for nm in names}
                 if el["name"] == "vertex":
                     verts = table
+                    vertex_types = {p_[2]: p_[1] for p_ in el["props"]}
             else:
                 if len(el["props"]) != 1:
                     raise ValueError(f"{path}: element {el['name']} mixes list and scalar properties (unsupported)")
@@ -308,7 +320,21 @@ def load_ply(path: str):
         raise ValueError(f"{path}: needs a vertex element with x y z and a face element")
     v = np.stack([verts["x"], verts["y"], verts["z"]], axis=1)
     n = np.stack([verts["nx"], verts["ny"], verts["nz"]], axis=1) if all(k in verts for k in ("nx", "ny", "nz")) else None
-    return v, n, faces
+    if not with_color:
+        return v, n, faces
+    color = None
+    for names in (("r", "g", "b"), ("red", "green", "blue")):
+        if all(k in verts for k in names):
+            cols = []
+            for k in names:
+                ty = _PLY_TYPES[vertex_types[k]]
+                if ty[0] == "f":
+                    cols.append(verts[k])
+                else:                                              # Normalized | Gamma: the type's range to [0, 1], then linear
+                    cols.append(_srgb_to_linear(verts[k] / float(np.iinfo(np.dtype(ty)).max)))
+            color = np.stack(cols, axis=1).astype(np.float32)
+            break
+    return v, n, faces, color
 
 
 def vertex_normals(v: np.ndarray, f: np.ndarray) -> np.ndarray:
@@ -343,9 +369,12 @@ def vertex_normals_torch(v: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
 
 
 class Mesh:
-    def __init__(self, name, v, f, n=None, bsdf=0, emitter=-1, flip_normals=False, is_mesh=True, face_normals=False, uv=None):
+    def __init__(self, name, v, f, n=None, bsdf=0, emitter=-1, flip_normals=False, is_mesh=True, face_normals=False, uv=None,
+                 vertex_color=None):
         self.name = name
         self.uv = None if uv is None else np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+        # the `vertex_color` attribute (mesh.cpp add_attribute): (V,3) linear RGB, what a `mesh_attribute` reflectance reads
+        self.vertex_color = None if vertex_color is None else np.array(vertex_color, dtype=np.float32, copy=True).reshape(-1, 3)
         self.v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
         self.f = np.asarray(f, dtype=np.int64).reshape(-1, 3)
         self.face_normals = face_normals
@@ -607,6 +636,40 @@ def _bitmap_texture(val: dict, base_dir: str) -> dict:
     return {"bitmap": np.ascontiguousarray(a[:, :, :3]), "nearest": 1 if ft == "nearest" else 0}
 
 
+def _vertex_color_values(a, n_vertices: int, what: str) -> np.ndarray:
+    """(V,3) float32 colours of a mesh's ``vertex_color`` attribute from what the user gave; refuses what a reflectance cannot be."""
+    a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
+    if a.ndim == 3 and a.shape[1] == 1:                                # (V,1,3): a bitmap one texel wide, ParamGrads.texture's view
+        a = a[:, 0]
+    if a.shape != (n_vertices, 3):
+        raise ValueError(f"{what}: shape {tuple(a.shape)} is not ({n_vertices}, 3), one RGB colour per vertex")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: a vertex colour is not finite")
+    if (a < 0).any():
+        raise ValueError(f"{what}: a vertex colour is negative (the smallest is {float(a.min())!r})")
+    return np.array(a, dtype=np.float32, order="C", copy=True)
+
+
+def _mesh_attribute_texture(val: dict) -> dict:
+    """A ``mesh_attribute`` texture (src/textures/mesh_attribute.cpp) as the reflectance of a diffuse BSDF: the ``vertex_color``
+    attribute of the shape that nests the BSDF, times ``scale``."""
+    name = val.get("name")
+    if name != "vertex_color":
+        raise ValueError(f"mesh_attribute: only the attribute 'vertex_color' is read here, not {name!r} (no face_* attributes, "
+                         "no attributes other than the colour)")
+    sc = float(val.get("scale", 1.0))
+    if not np.isfinite(sc) or sc < 0:
+        raise ValueError(f"mesh_attribute: scale {sc!r} is negative or not finite")
+    return {"scale": sc}
+
+
+def _refuse_mesh_attribute(d: dict, where: str, allowed: str = None) -> None:
+    for k, v in d.items():
+        if k != allowed and isinstance(v, dict) and v.get("type") == "mesh_attribute":
+            raise ValueError(f"mesh_attribute: {where} {k!r} cannot be one (only the reflectance of a diffuse BSDF may be a mesh "
+                             "attribute here)")
+
+
 def _alpha_bitmap_values(a, what: str) -> np.ndarray:
     """(H, W) float32 texels of a roughness map from what the user gave; refuses what a roughness cannot be."""
     a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
@@ -771,7 +834,7 @@ class Scene:
         self.material_slots: Dict[int, int] = {}   # conductors attached for the material adjoint (attach_conductor): BSDF index -> slot
         self.env_pose_attached = False             # the envmap's rotation and scale attached for the pose adjoint (attach_envmap_pose)
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
-        self.texture_slots: List[tuple] = []       # bitmaps attached for the texel adjoints: ("bsdf" | "envmap" | "alpha", index)
+        self.texture_slots: List[tuple] = []       # bitmaps and per-vertex colours attached for the texel adjoints: ("bsdf" | "envmap" | "alpha" | "vertex", index)
         self.rigid_slots: List[dict] = []          # rigid bodies (attach_rigid): {"mesh": name, "pivot": [x, y, z]}, slot order
         self.sensor_attached = self.sensor_rotation = False     # attach_sensor
         self._rigid_tables = {}                    # (ranges, pivots) -> their device tensors
@@ -817,9 +880,13 @@ class Scene:
                 return out
             o = dict(type=BSDF_TYPES[t], twosided=0, distr=0, sample_visible=1, reflectance=_rgb(None, [1, 1, 1]),
                      alpha=0.1, eta=np.zeros(3, np.float32), k=np.ones(3, np.float32), int_ior=1.5046, ext_ior=1.000277)
+            _refuse_mesh_attribute(b, f"the {t} BSDF's", allowed="reflectance" if t == "diffuse" else None)
             if t == "diffuse":
                 r = b.get("reflectance")
-                if isinstance(r, dict) and r.get("type") == "bitmap":
+                if isinstance(r, dict) and r.get("type") == "mesh_attribute":
+                    o["vertex_texture"] = _mesh_attribute_texture(r)   # (the shape that nests this BSDF brings the colours)
+                    o["reflectance"] = _rgb(None, [0.5, 0.5, 0.5])      # (a stand-in: the attribute's mean once the shape is known)
+                elif isinstance(r, dict) and r.get("type") == "bitmap":
                     o["texture"] = _bitmap_texture(r, base_dir)
                     o["reflectance"] = o["texture"]["bitmap"].reshape(-1, 3).mean(0).astype(np.float32)      # (a stand-in: the tracer looks the texture up)
                 else:
@@ -863,6 +930,7 @@ class Scene:
             if t == "perspective":
                 sensors.append(Sensor(val))
             elif t == "point":
+                _refuse_mesh_attribute(val, "the point light's")
                 emitters.append(dict(type=1, mesh=-1, radiance=_rgb(val.get("intensity"), [1, 1, 1]),
                                      position=np.asarray(val.get("position", [0, 0, 0]), np.float32)))
                 emitter_names.append(key)
@@ -872,6 +940,7 @@ class Scene:
                 e = dict(type=2 if t == "constant" else 3, mesh=-1, radiance=_rgb(val.get("radiance"), [1, 1, 1]),
                          position=np.zeros(3, np.float32))
                 if t == "envmap":
+                    _refuse_mesh_attribute(val, "the envmap's")
                     e["bitmap"] = _envmap_bitmap(val, base_dir)
                     e["scale"] = float(val.get("scale", 1.0))            # (the texel adjoint's gradient is w.r.t. the bitmap before it)
                     e["to_world"] = np.asarray(val.get("to_world", np.eye(4)), dtype=np.float64)
@@ -879,17 +948,18 @@ class Scene:
                 emitter_names.append(key)
             elif t in ("obj", "ply", "mesh", "rectangle"):
                 tw = np.asarray(val.get("to_world", np.eye(4)), dtype=np.float64)
-                uv = None
+                uv = vc = None
                 if t == "obj":
                     v, n, f, uv = load_obj(os.path.join(base_dir, val["filename"]), with_uv=True)
                     if uv is None:                                       # (no vt lines: the plain reader's vertex merging)
                         v, n, f = load_obj(os.path.join(base_dir, val["filename"]))
                 elif t == "ply":
-                    v, n, f = load_ply(os.path.join(base_dir, val["filename"]))
+                    v, n, f, vc = load_ply(os.path.join(base_dir, val["filename"]), with_color=True)
                 elif t == "mesh":
                     v, f = np.asarray(val["vertices"], np.float64), np.asarray(val["faces"], np.int64)
                     n = np.asarray(val["normals"], np.float64) if "normals" in val else None
                     uv = np.asarray(val["texcoords"], np.float64) if "texcoords" in val else None
+                    vc = val.get("vertex_color")
                 else:
                     v = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float64)
                     f = np.array([[0, 1, 2], [0, 2, 3]], np.int64); n = None
@@ -907,6 +977,7 @@ class Scene:
                     elif v2.get("type") in list(BSDF_TYPES) + ["twosided"]:
                         bsdf_id = add_bsdf(f"{key}.{k2}", v2)
                     elif v2.get("type") == "area":
+                        _refuse_mesh_attribute(v2, "the area light's")
                         emitters.append(dict(type=0, mesh=len(meshes), radiance=_rgb(v2.get("radiance"), [1, 1, 1]),
                                              position=np.zeros(3, np.float32)))
                         emitter_names.append(key)
@@ -916,9 +987,11 @@ class Scene:
                         default_bsdf = add_bsdf("__default_diffuse", {"type": "diffuse"})
                     bsdf_id = default_bsdf
                 face_normals = bool(val.get("face_normals", False)) or t == "rectangle"
+                if vc is not None:
+                    vc = _vertex_color_values(vc, v.shape[0], f"shape {key!r}: vertex_color")
                 meshes.append(Mesh(key, v, f, n, bsdf=bsdf_id, emitter=emitter_id,
                                    flip_normals=bool(val.get("flip_normals", False)), is_mesh=(t != "rectangle"),
-                                   face_normals=face_normals, uv=uv))
+                                   face_normals=face_normals, uv=uv, vertex_color=vc))
         sc = Scene(meshes, bsdfs, emitters, sensors, device=device, bsdf_names=bsdf_names, bvh_builder=bvh_builder,
                    scene_tables=scene_tables)
         sc.emitter_names = emitter_names
@@ -1122,7 +1195,7 @@ class Scene:
     def attach_color(self, bsdf_name: str) -> int:
         """``dr.enable_grad(params['<bsdf>.reflectance.value'])`` for the colour adjoint (PRBIntegrator): diffuse BSDFs."""
         i = self.bsdf_names.index(bsdf_name)
-        if self.bsdf_desc[i]["type"] != 0 or "texture" in self.bsdf_desc[i]:
+        if self.bsdf_desc[i]["type"] != 0 or "texture" in self.bsdf_desc[i] or "vertex_texture" in self.bsdf_desc[i]:
             raise ValueError("attach_color: only the CONSTANT reflectance of a diffuse BSDF is a colour parameter here")
         if ("bsdf", i) not in self.color_slots:
             if len(self.color_slots) >= 4:
@@ -1183,6 +1256,8 @@ class Scene:
             i = self.bsdf_names.index(name)
             if self.bsdf_desc[i]["type"] != 0:
                 raise ValueError(f"attach_texture: {name!r} is not a diffuse BSDF (only a diffuse reflectance may be a bitmap here)")
+            if "vertex_texture" in self.bsdf_desc[i]:
+                raise ValueError(f"attach_texture: the reflectance of {name!r} is not a bitmap (attach_vertex_color takes a per-vertex one)")
             if "texture" not in self.bsdf_desc[i]:
                 raise ValueError(f"attach_texture: the reflectance of {name!r} is not a bitmap (attach_color takes a constant one)")
             key = ("bsdf", i)
@@ -1203,14 +1278,38 @@ class Scene:
             self.texture_slots.append(key)
         return self.texture_slots.index(key)
 
+    def attach_vertex_color(self, mesh_name: str) -> int:
+        """``dr.enable_grad(params['<mesh>.vertex_color'])`` -- the ``vertex_color`` attribute of a mesh whose diffuse BSDF reads it
+        through a ``mesh_attribute`` reflectance -- for the texel adjoint (``epsm_trace_paths_texture_backward``; PRBIntegrator).
+        Returns the slot, of ``attach_texture``'s numbering and limit: ``ParamGrads.texture(slot)`` is (V_mesh, 1, 3), a bitmap
+        one texel wide with one row per vertex."""
+        if mesh_name not in [m.name for m in self.meshes]:
+            raise ValueError(f"attach_vertex_color: {mesh_name!r} is not a shape of this scene")
+        m = self.mesh(mesh_name)
+        b = self.bsdf_desc[m.bsdf]
+        if "vertex_texture" not in b or b.get("vertex_mesh") != self.meshes.index(m):
+            raise ValueError(f"attach_vertex_color: the BSDF of {mesh_name!r} does not read its vertex_color (a diffuse reflectance of "
+                             "type 'mesh_attribute' does)")
+        if not float(b["vertex_texture"]["scale"]):
+            raise ValueError("attach_vertex_color: a mesh_attribute with scale 0")
+        key = ("vertex", m.bsdf)
+        if key not in self.texture_slots:
+            if len(self.texture_slots) >= 8:                        # EPSM_MAX_TEXTURE_GRADS
+                raise ValueError("at most 8 texture parameters")
+            self.texture_slots.append(key)
+        return self.texture_slots.index(key)
+
     def texture_shapes(self):
-        """(H, W) of every attached texture slot -- (H, W, 1) of a roughness-map slot -- slot order (ParamGrads' ``tex_shapes``)."""
+        """(H, W) of every attached texture slot -- (H, W, 1) of a roughness-map slot, (V_mesh, 1) of a per-vertex colour slot --
+        slot order (ParamGrads' ``tex_shapes``)."""
         return [self._texture_shape(k)[:2] + ((1,) if self.texture_slots[k][0] == "alpha" else ())
                 for k in range(len(self.texture_slots))]
 
     def _texture_shape(self, slot: int):
         """The shape of the slot's buffers: (H, W, 3), or (H, W) for a roughness map."""
         kind, i = self.texture_slots[slot]
+        if kind == "vertex":                                    # (V_mesh, 1, 3): a bitmap one texel wide
+            return (int(self.meshes[self.bsdf_desc[i]["vertex_mesh"]].v.shape[0]), 1, 3)
         a = (self.bsdf_desc[i]["texture"]["bitmap"] if kind == "bsdf" else self.bsdf_desc[i]["alpha_texture"]["bitmap"] if kind == "alpha"
              else self.emitter_desc[i]["bitmap"])
         return tuple(int(x) for x in a.shape)
@@ -1219,7 +1318,9 @@ class Scene:
         """(H, W, 3) current bitmap of texture slot ``slot`` -- an envmap's as the user gave it, before its ``scale``; (H, W) for
         a roughness map."""
         kind, i = self.texture_slots[slot]
-        if kind == "bsdf":
+        if kind == "vertex":                                    # (V_mesh, 3), before the attribute's scale
+            a = self.meshes[self.bsdf_desc[i]["vertex_mesh"]].vertex_color
+        elif kind == "bsdf":
             a = self.bsdf_desc[i]["texture"]["bitmap"]
         elif kind == "alpha":
             a = self.bsdf_desc[i]["alpha_texture"]["bitmap"]
@@ -1229,8 +1330,10 @@ class Scene:
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
 
     def texture_scale(self, slot: int) -> float:
-        """d texel / d bitmap of a slot: an envmap's ``scale``, 1 for a BSDF's bitmap."""
+        """d texel / d bitmap of a slot: an envmap's ``scale``, a per-vertex colour's ``scale``, 1 for a BSDF's bitmap."""
         kind, i = self.texture_slots[slot]
+        if kind == "vertex":
+            return float(self.bsdf_desc[i]["vertex_texture"]["scale"])
         return float(self.emitter_desc[i].get("scale", 1.0)) if kind == "envmap" else 1.0
 
     def set_texture(self, slot: int, array):
@@ -1246,6 +1349,16 @@ class Scene:
             b["alpha_texture"]["bitmap"] = a
             b["alpha"] = float(a.mean())                        # (the stand-in of from_dict)
             self._tex_buf[b["texture_index"]][0].copy_(torch.from_numpy(a).to(self.device))
+            self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
+            return
+        if kind == "vertex":                                   # (V_mesh, 3) or (V_mesh, 1, 3), every value >= 0 and finite, as from_dict asks
+            b = self.bsdf_desc[i]
+            m = self.meshes[b["vertex_mesh"]]
+            a = _vertex_color_values(array, m.v.shape[0], "set_texture")
+            m.vertex_color = a
+            sc = np.float32(b["vertex_texture"]["scale"])
+            b["reflectance"] = (a.mean(0) * sc).astype(np.float32)  # (the stand-in of _upload)
+            self._tex_buf[b["texture_index"]][0].copy_(torch.from_numpy(a * sc).to(self.device).reshape(-1, 1, 3))
             self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
             return
         a = np.asarray(array.detach().cpu().numpy() if torch.is_tensor(array) else array, dtype=np.float32)
@@ -1499,8 +1612,27 @@ class Scene:
                     raise ValueError(f"mesh {m.name}: {u.shape[0]} texture coordinates for {m.v.shape[0]} vertices")
             self.texcoords = f32(np.concatenate(uvs))
         self._tex_buf = []
-        for b in self.bsdf_desc:
-            if "texture" in b:
+        self._tex_vertex = {}                                  # texture index of a per-vertex table -> the first vertex row it covers
+        for bi, b in enumerate(self.bsdf_desc):
+            if "vertex_texture" in b:                          # a `mesh_attribute` reflectance: (Vm, 1, 3), EPSM_TEXTURE_VERTEX_RGB
+                users = [m for m in self.meshes if m.bsdf == bi]
+                if len(users) > 1:
+                    raise ValueError(f"mesh_attribute: the BSDF {self.bsdf_names[bi]!r} is used by more than one shape "
+                                     f"({', '.join(repr(m.name) for m in users)}): its reflectance is ONE shape's vertex_color, "
+                                     "each shape nests its own")
+                if not users:
+                    continue                                   # (nothing can be hit with it)
+                m = users[0]
+                if m.vertex_color is None:
+                    raise ValueError(f"mesh_attribute: the shape {m.name!r} has no 'vertex_color' attribute for its BSDF "
+                                     f"{self.bsdf_names[bi]!r} to read")
+                vc = _vertex_color_values(m.vertex_color, m.v.shape[0], f"shape {m.name!r}: vertex_color")
+                b["vertex_mesh"] = self.meshes.index(m)
+                b["reflectance"] = (vc.mean(0) * np.float32(b["vertex_texture"]["scale"])).astype(np.float32)    # (a stand-in, as a bitmap's)
+                b["texture_index"] = len(self._tex_buf)
+                self._tex_vertex[b["texture_index"]] = self.mesh_slices[m.name][0]
+                self._tex_buf.append((f32(vc * np.float32(b["vertex_texture"]["scale"])).reshape(-1, 1, 3), 0))
+            elif "texture" in b:
                 b["texture_index"] = len(self._tex_buf)
                 self._tex_buf.append((f32(b["texture"]["bitmap"]), b["texture"]["nearest"]))
             elif "alpha_texture" in b:                         # a roughness map: (H, W), EpsmTexture.channels = 1
@@ -1510,6 +1642,8 @@ class Scene:
         for i, (t_, nearest) in enumerate(self._tex_buf):
             tx[i].texels, tx[i].height, tx[i].width, tx[i].nearest = t_.data_ptr(), int(t_.shape[0]), int(t_.shape[1]), int(nearest)
             tx[i].channels = 1 if t_.dim() == 2 else 0          # (0: RGB, what every table held before there were roughness maps)
+            if i in self._tex_vertex:                           # width, height: the first vertex row and the number of rows
+                tx[i].width, tx[i].height, tx[i].channels = int(self._tex_vertex[i]), int(t_.shape[0]), TEXTURE_VERTEX_RGB
         bs = self._bsdf_structs()
         em = (EpsmEmitter * max(1, len(self.emitter_desc)))()
         for i, e in enumerate(self.emitter_desc):
@@ -1704,7 +1838,7 @@ class Scene:
             assert tuple(t_.shape) == self._texture_shape(self.texture_slots.index((kind, i)))
             if (kind == "alpha") != alpha:
                 continue
-            if kind in ("bsdf", "alpha"):
+            if kind in ("bsdf", "alpha", "vertex"):
                 arr[self.bsdf_desc[i]["texture_index"]] = t_.data_ptr()
             else:
                 env = C.c_void_p(t_.data_ptr())

@@ -116,7 +116,7 @@ typedef struct EpsmBsdf {
     int32_t color_slot;              /* diffuse: slot of `reflectance` in the colour adjoint of epsm_trace_paths_color,
                                         -1 = not optimised */
     int32_t texture;                 /* diffuse: index into EpsmScene.textures of the `bitmap` its reflectance is (a texture whose
-                                        channels are 0 or 3), -1 = `reflectance`.  roughconductor: index of the 1-channel `bitmap`
+                                        channels are 0 or 3) or of the per-vertex table it is (EPSM_TEXTURE_VERTEX_RGB), -1 = `reflectance`.  roughconductor: index of the 1-channel `bitmap`
                                         its alpha is (channels = 1), -1 = `alpha`; such a BSDF has alpha_slot = -1.  A texture of the
                                         other kind is ignored, never read through; no table written so far sets this word on
                                         anything but a diffuse BSDF */
@@ -126,12 +126,26 @@ typedef struct EpsmBsdf {
 
 /* A `bitmap` texture (src/textures/bitmap.cpp): linear RGB texels -- or scalar ones, the roughness map of a roughconductor
  * (roughconductor.cpp:195-198) -- looked up at si.uv as there: uv * (width, height) - 0.5, bilinear between the four texels
- * around it (or the nearest one), indices wrapped (`repeat`). */
+ * around it (or the nearest one), indices wrapped (`repeat`).
+ * Or, with channels = EPSM_TEXTURE_VERTEX_RGB, no bitmap at all but a per-vertex table: the `mesh_attribute` texture
+ * (src/textures/mesh_attribute.cpp) of ONE mesh's `vertex_color`, the reflectance of a diffuse BSDF.  texels is then (count, 3),
+ * the mesh's vertices in its own order (any `scale` applied), and the two size words say which rows of EpsmScene's vertex arrays
+ * the table covers: width = EPSM_TEXTURE_VERTEX_FIRST, the first row; height = EPSM_TEXTURE_VERTEX_COUNT, how many.  A hit on
+ * triangle (vi0, vi1, vi2) with barycentrics (b0, b1, b2) reads b0 c[vi0 - first] + b1 c[vi1 - first] + b2 c[vi2 - first]; a row
+ * outside [first, first + count) makes the lookup ignored (EpsmBsdf.reflectance stays).  nearest is 0.  Such a table is never
+ * walked as a bitmap: every bitmap reader ignores it, as a 1-channel texture is ignored where three are expected. */
+#define EPSM_TEXTURE_RGB 3u          /* channels: RGB texels (0 means the same) */
+#define EPSM_TEXTURE_SCALAR 1u       /* channels: scalar texels */
+#define EPSM_TEXTURE_VERTEX_RGB 4u   /* channels: not a bitmap -- a per-vertex RGB table (above) */
+#define EPSM_TEXTURE_VERTEX_FIRST(T) ((T).width)     /* per-vertex table: first row of the scene's vertex arrays it covers */
+#define EPSM_TEXTURE_VERTEX_COUNT(T) ((T).height)    /* per-vertex table: number of rows */
 typedef struct EpsmTexture {
-    const float *texels;             /* (height, width, 3), or (height, width) when channels = 1; row 0 at v = 0 */
-    int32_t width, height;
+    const float *texels;             /* (height, width, 3), or (height, width) when channels = 1; row 0 at v = 0.  Per-vertex table:
+                                        (count, 3) */
+    int32_t width, height;           /* per-vertex table: first row, count */
     uint32_t nearest;                /* filter_type: 0 bilinear, 1 nearest */
-    uint32_t channels;               /* 0 or 3: RGB texels; 1: scalar texels (the word that was padding: 0 in every table) */
+    uint32_t channels;               /* 0 or 3: RGB texels; 1: scalar texels (the word that was padding: 0 in every table);
+                                        EPSM_TEXTURE_VERTEX_RGB: a per-vertex RGB table, width / height as above */
 } EpsmTexture;
 
 typedef struct EpsmEmitter {
@@ -360,6 +374,9 @@ int epsm_trace_paths_reparam_forward(const EpsmScene *scene, const EpsmSensor *s
  *       EpsmScene.textures[t].  A diffuse vertex k looked up at uv_k adds adj . L_after_k / rho_k x w to each texel of its
  *       footprint (4 bilinear, 1 nearest; wrap as the lookup), L_after_k = radiance - L collected up to and including the
  *       emission at k; a channel with rho_k = 0 adds nothing (prb.py's inv_bsdf_val_det);
+ *     - the per-vertex reflectance of a diffuse BSDF (EpsmScene.textures[t].channels == EPSM_TEXTURE_VERTEX_RGB): grad_tex[t],
+ *       (count_t, 3) f32 shaped like the table.  The same term goes to the three rows of the hit's vertices with the
+ *       barycentrics (b0, b1, b2) as weights; a hit with a vertex outside the table adds nothing;
  *     - the envmap (EpsmScene.env.kind == EPSM_ENV_ENVMAP): grad_env, (height, width, 3) f32 -- the bitmap's shape: column
  *       `width` of EpsmEnvironment.texels folds into column 0.  A ray that leaves the scene adds adj . beta mis x w, an emitter
  *       sample on the map adj . beta bsdf mis / pdf x w when it is not occluded; the sampling tables are detached.
