@@ -402,15 +402,26 @@ __device__ __forceinline__ void geo_issue_rest(GeoFetch &X, const FusedArgs &F, 
     const float *nx = R.end_next ? R.rec + kRecWords : B.sub_rec;
     X.n0 = ldq(nx, 0); X.n1 = ldq(nx, 1); X.n2 = ldq(nx, 2);
 }
+// The emission's words of the lane's record of the NEXT round.  No guards (own_issue): a load inside a branch that a wave may
+// skip is one the compiler cannot count, and a wait for the scene-table rows issued before it -- vmcnt counts in order -- then
+// has to assume the branch was NOT taken and waits for that many of own_issue's loads, an HBM trip in the middle of the emission,
+// in every wave that did take it.  So every lane loads all three words, every path through the prefetch issues the same nine
+// loads, and the count is exact.  q6 and q7 come from the lane's record where it is `live` -- the sector its o4, o5 already
+// read -- and from the window's substitute record otherwise; sh from the lane's occluder record where `d1 && shadow`, otherwise
+// from the substitute record too (an address every launch of the packed form may read, with or without occluder records).
+// Nobody relies on a zero in a word that was not wanted.  The readers, all in the round loop:
+//   q6, q7, sh -> the stash (plain copies into the lane's own 32 bytes of LDS, read back by the same lane);
+//   q7.x -> X.o_lz (light.z of the emitter sample) under `live && (F.galpha || wN)`, 0 otherwise, as a guarded load left it;
+//   q7.yzw -> dhf under `live && F.galpha`;
+//   q6 -> etri, eb0, eb1, ew under `live && wN` (the stash hands a lane q6 only where `!(d1 && F.pk_shadow)`);
+//   sh -> the occluder record under `d1 && F.pk_shadow`.
 template <int VARIANT, bool LIST>
-__device__ __forceinline__ void addr_issue(AddrFetch &A, const FusedArgs &F, const LaneId &L, const WinBase &B) {
-    const LaneRole R = role_of<LIST>(F, L, B);
-    if (R.live) {
-        const bool wN = VARIANT == EPSM_VARIANT_MANIFOLD && cp::plan_a(L.word, L.k);
-        if (F.galpha || wN) A.q7 = ldq(R.rec, 7);                  // d hf / d alpha, and light.z of the emitter sample
-        if (wN) A.q6 = ldq(R.rec, 6);
-    }
-    if (R.d1 && R.shadow) A.sh = load_u4(R.shadow, 0);
+__device__ __forceinline__ void addr_issue(AddrFetch &A, const LaneRole &R, const WinBase &B) {
+    const float *rec67 = R.live ? R.rec : B.sub_rec;
+    A.q7 = ldq(rec67, 7);                                          // d hf / d alpha, and light.z of the emitter sample
+    A.q6 = ldq(rec67, 6);
+    const uint32_t *occ = (R.d1 && R.shadow) ? R.shadow : (const uint32_t *) B.sub_rec;
+    A.sh = load_u4(occ, 0);
 }
 
 // ---- round 5: the lane's OWN record of the wave's NEXT round -- quads 0..5 and the
@@ -429,7 +440,42 @@ __device__ __forceinline__ void own_issue(GeoFetch &X, AddrFetch &A, const Fused
     const float *rec012 = (R.live || R.d1) ? R.rec : B.sub_rec, *rec345 = R.live ? R.rec : B.sub_rec;
     X.o0 = ldq(rec012, 0); X.o1 = ldq(rec012, 1); X.o2 = ldq(rec012, 2);
     X.o3 = ldq(rec345, 3); X.o4 = ldq(rec345, 4); X.o5 = ldq(rec345, 5);
-    addr_issue<VARIANT, LIST>(A, F, L, B);
+    // (the lane's role is handed on: formed a second time, the slot -> path load of the list forms was issued a second time and
+    // waited for with vmcnt(0) -- behind the six loads above, an HBM trip in the middle of the prefetch)
+    addr_issue<VARIANT, LIST>(A, R, B);
+}
+// ---- the rows of the scene table a lane's emission names -- its own triangle, the next vertex's, the emitter sample's, the
+// occluder's -- requested TOGETHER: one trip to memory.  table_row() (epsm_scatter_core.h) guards its load with `id < T` and
+// fills the default row otherwise; four of them in a row compiled to four exec-masked blocks, each with its load and, because
+// the first uses of the loaded words sink into the block, a wait for it: four serial round trips through the vector L1.  Here
+// the four loads carry no guard -- a lane whose id names no row reads row 0 instead, and where the launch has no table at all
+// every lane reads `sub`, a window-uniform address the launch may read (WinBase::sub_rec) -- and the default row
+// {kNoIndex, kNoIndex, kNoIndex, 0} is selected AFTER all four are on their way.  What comes back for every id is what
+// table_row() returns; no lane reads outside the table.  `sub` may be null where the launch has none (the per-field form): the
+// loads then stand behind a launch-uniform branch, which costs no exec-masked block.
+struct TableRows { U4 own, next, emit, occ; };
+__device__ __forceinline__ U4 row_or_none(bool valid, const U4 &r) {
+    U4 o;
+    o.x = valid ? r.x : kNoIndex; o.y = valid ? r.y : kNoIndex; o.z = valid ? r.z : kNoIndex; o.w = valid ? r.w : 0u;
+    return o;
+}
+template <bool HAVE_SUB>
+__device__ __forceinline__ TableRows table_rows(const TriTable &tab, const float *sub, uint32_t id_own, uint32_t id_next,
+                                                uint32_t id_emit, uint32_t id_occ) {
+    const bool have = tab.T > 0 && tab.rows != nullptr;          // launch-uniform
+    const bool v_own = have && (int64_t) id_own < tab.T, v_next = have && (int64_t) id_next < tab.T;
+    const bool v_emit = have && (int64_t) id_emit < tab.T, v_occ = have && (int64_t) id_occ < tab.T;
+    TableRows o;
+    const U4 none = {kNoIndex, kNoIndex, kNoIndex, 0u};
+    o.own = o.next = o.emit = o.occ = none;
+    if (HAVE_SUB || have) {
+        const uint32_t *rows = have ? tab.rows : (const uint32_t *) sub;
+        const U4 r_own = load_u4(rows, v_own ? (int64_t) id_own : 0), r_next = load_u4(rows, v_next ? (int64_t) id_next : 0);
+        const U4 r_emit = load_u4(rows, v_emit ? (int64_t) id_emit : 0), r_occ = load_u4(rows, v_occ ? (int64_t) id_occ : 0);
+        o.own = row_or_none(v_own, r_own); o.next = row_or_none(v_next, r_next);
+        o.emit = row_or_none(v_emit, r_emit); o.occ = row_or_none(v_occ, r_occ);
+    }
+    return o;
 }
 __device__ __forceinline__ void fetch_zero(GeoFetch &X, AddrFetch &A) {
     const F4v z4 = {0.f, 0.f, 0.f, 0.f};
@@ -689,7 +735,8 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     const bool has_sh = d1 && F.pk_shadow;
                     const F4v shv = {__uint_as_float(A0.sh.x), __uint_as_float(A0.sh.y), __uint_as_float(A0.sh.z), __uint_as_float(A0.sh.w)};
                     *(LdsF4w *) st = has_sh ? shv : A0.q6; *(LdsF4w *) (st + 4) = A0.q7;
-                    X.o_lz = A0.q7.x;                                // light.z: word 28
+                    // light.z: word 28 -- where the lane wanted quad 7 (addr_issue loads it for every lane), 0 elsewhere
+                    X.o_lz = (live && (F.galpha || wN)) ? A0.q7.x : 0.f;
                 }
                 {   // every lane, whatever it holds (a plain assignment instead of a zero fill and a copy under the exec mask per word): a
                     // lane without a constraint forms its vertex from the words own_issue gave it -- the substitute record's -- and nobody
@@ -873,8 +920,8 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     if (has_next && k < c) { nb0 = db0; nb1 = db1; tid_next = dt; }
                 }
             }
-            const U4 t_own = table_row(F.tab, tid_own), t_next = table_row(F.tab, tid_next);
-            const U4 er = table_row(F.tab, etri), t_sh = table_row(F.tab, sh.x);
+            const TableRows TR = table_rows<PACKED>(F.tab, PACKED ? WB.sub_rec : nullptr, tid_own, tid_next, etri, sh.x);
+            const U4 t_own = TR.own, t_next = TR.next, er = TR.emit, t_sh = TR.occ;
             asm volatile("; EPSM_MARK prefetch");
             // (Until round 4's counter run a "touch" stood here: one word per cache line of the NEXT round's records, so that the
             // lines travelled HBM -> L2 during the emission.  It cost more than it hid: a CU's vector L1 keeps ~64 misses in
