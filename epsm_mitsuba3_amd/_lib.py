@@ -275,15 +275,17 @@ def check(rc: int, what: str):
 
 
 OPT_SMALL_WAVEFRONT_PATHS, OPT_REPLICAS, OPT_ONE_LAUNCH, OPT_WORKGROUP_SLOTS = 0, 1, 2, 3       # include/epsm.h EPSM_OPT_*
+OPT_IOR_GRADS = 5                                                                                # (4 is not assigned)
 
 
 class options:
     """``with options(small_wavefront_paths=0, replicas=False): ...`` -- launch options of the fused entry points
     (include/epsm.h, epsm_set_option) for the duration of a block; the previous values come back on exit."""
 
-    def __init__(self, small_wavefront_paths=None, replicas=None, one_launch=None, workgroup_slots=None):
+    def __init__(self, small_wavefront_paths=None, replicas=None, one_launch=None, workgroup_slots=None, ior_grads=None):
         self.want = {OPT_SMALL_WAVEFRONT_PATHS: small_wavefront_paths, OPT_REPLICAS: None if replicas is None else int(bool(replicas)),
-                     OPT_ONE_LAUNCH: None if one_launch is None else int(bool(one_launch)), OPT_WORKGROUP_SLOTS: workgroup_slots}
+                     OPT_ONE_LAUNCH: None if one_launch is None else int(bool(one_launch)), OPT_WORKGROUP_SLOTS: workgroup_slots,
+                     OPT_IOR_GRADS: None if ior_grads is None else int(bool(ior_grads))}
 
     def __enter__(self):
         self.saved = {k: lib().epsm_get_option(k) for k, v in self.want.items() if v is not None}

@@ -172,10 +172,13 @@ template <typename Table> struct Emitter {
     // `on`: this lane has a vertex whose parameter rows exist; `live`: it has a constraint (its end-point rows exist);
     // `d1`: it carries diffuse_grad[0] = dldp of a path whose first hit is diffuse (epsm.py:791-792, 998-1000) and the
     // occluder term (609-620).  n, e1, e2, b0, b1: geometry of the lane's vertex (b0, b1 also for a d1 lane without constraint).
+    // IOR (EPSM_OPT_IOR_GRADS): the scalar row of a vertex whose record has eta != 1 -- a refraction, a delta lobe without a
+    // roughness term -- takes geta = d/d eta_k times dhf.x = d eta / d int_ior instead of gm . dhf.
+    template <bool IOR>
     __device__ __forceinline__ void vertex(bool on, bool live, bool d1, V3<float> Gx, V3<float> gn, V3<float> gm, V3<float> glight,
                                            V3<float> gdiff, V3<float> dp, V3<float> n, V3<float> e1, V3<float> e2, float b0, float b1,
                                            float nb0, float nb1, uint32_t bid, V3<float> dhf, float eb0, float eb1, float ew,
-                                           const U4 &t, const U4 &tn, const U4 &er, const U4 &sh, const U4 &ts) const {
+                                           const U4 &t, const U4 &tn, const U4 &er, const U4 &sh, const U4 &ts, float geta, float eta) const {
         const V3<float> z = zero3<float>();
         const bool idx_ok = tri_ok(t, F.V), pos_ok = idx_ok && (t.w & kModePos);
         gn = fin(gn);
@@ -218,8 +221,13 @@ template <typename Table> struct Emitter {
         {   // ---- alpha row: bsdf_sample.hf * path_grad[5it+4]  (epsm.py:645); a handful of materials
             gm = fin(gm);
             bool v = on && nz3(gm) && bid < (uint64_t) F.B;
+            const bool refr = IOR && eta != 1.f;                 // (IOR off: the row is formed exactly as it always was)
+            if (refr) {
+                geta = finalize(geta, F.g.clip);
+                v = on && geta != 0.f && bid < (uint64_t) F.B;
+            }
             if (__ballot(v) != 0ull) {
-                V3<float> val[1] = {mk3<float>(v ? dot(gm, dhf) : 0.f, 0.f, 0.f)};
+                V3<float> val[1] = {mk3<float>(v ? (refr ? geta * dhf.x : dot(gm, dhf)) : 0.f, 0.f, 0.f)};
                 const uint32_t aid[3] = {2u * (uint32_t) F.V + bid, 0u, 0u};
                 push<1>(v, aid, val);
             }
@@ -519,8 +527,13 @@ __device__ __attribute__((noinline)) WindowRange window_range(int64_t n, int slo
 }
 
 // DROP: paths without any term take no lane (see kSortKeys below)
-template <int VARIANT, int DMODE, bool PACKED, bool FLOAT_ROWS, int kWindow, bool DROP>
-__global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel(FusedArgs F, int dcols, int slots, int bulk_window) {
+// IOR: the scalar row of a refraction vertex is the gradient of its index of refraction (Emitter::vertex; in-kernel tangents only)
+// (its own register bound: geta and eta live through the emission up to the scalar row, and at three waves per SIMD four of the
+// 32 IOR instantiations spilled one register more than their twins and two spilled three and four where the twin has no scratch
+// at all -- at two waves per SIMD none has any; MEASUREMENTS.md 32.  The default instantiation is launched FIRST in launch():
+// tools/isa_waits.py reads the first kernel of the assembly whose name matches its key.)
+template <int VARIANT, int DMODE, bool PACKED, bool FLOAT_ROWS, int kWindow, bool DROP, bool IOR>
+__global__ __launch_bounds__(kThreads, IOR ? 2 : EPSM_CP_OCC) void epsm_backward_cp_kernel(FusedArgs F, int dcols, int slots, int bulk_window) {
     // float rows where the window's distinct rows need the larger table (epsm_wave_scatter.h, AccFixed64)
     // Rows of the accumulator table: 64-bit fixed point (epsm_wave_scatter.h, AccFixed64: the LDS integer atomic inserts an
     // order of magnitude faster than ds_add_f32, and same-address lanes do not serialise as badly) unless the caller disabled
@@ -814,6 +827,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
 
             asm volatile("; EPSM_MARK solve");
             V3<float> Gx = zero3<float>(), gn = Gx, gm = Gx, glight = Gx, gdiff = Gx;
+            float geta = 0.f;
             bool emit_vertex = live;
             AddrFetch A;
             {
@@ -865,6 +879,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     const V3<float> from_next = down1(o.GP);         // d/dx_k through constraint k+1
                     Gx = k < c ? o.Gx - from_next : o.Gx;
                     gn = o.gn; gm = o.gm; glight = o.glight; gdiff = o.gdiff;
+                    if (IOR) geta = o.geta;
                 }
             } else {
                 cp::CFwd<float> f = cp::cfwd_zero<float>();
@@ -901,6 +916,7 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
                     const V3<float> from_next = down1(o.gxp_prev);
                     Gx = k < c ? o.Gx + from_next : o.Gx;
                     gn = o.gn; gm = o.gm; gdiff = o.gdiff;
+                    if (IOR) geta = o.geta;
                     emit_vertex = live && k <= idstar && !poisoned;
                 }
             }
@@ -935,8 +951,8 @@ __global__ __launch_bounds__(kThreads, EPSM_CP_OCC) void epsm_backward_cp_kernel
             // ---- emission
             asm volatile("; EPSM_MARK emit");
             if (PACKED) bid = (t_own.w >> 8) - 1u;                    // packed log: alpha slot + 1 in the table row
-            E.vertex(emit_vertex && q > 0, live, d1, Gx, gn, gm, glight, gdiff, dp, pts.n, keep_e1, keep_e2, fb0, fb1,
-                     nb0, nb1, bid, dhf, eb0, eb1, ew, t_own, t_next, er, sh, t_sh);
+            E.template vertex<IOR>(emit_vertex && q > 0, live, d1, Gx, gn, gm, glight, gdiff, dp, pts.n, keep_e1, keep_e2, fb0, fb1,
+                                   nb0, nb1, bid, dhf, eb0, eb1, ew, t_own, t_next, er, sh, t_sh, geta, pts.eta);
             asm volatile("; EPSM_MARK round_end");
             L = Ln;
         }
@@ -1060,9 +1076,15 @@ hipError_t launch(const FusedArgs &F0, int dcols, hipStream_t s) {
     const bool float_rows = !(F.g.clip <= 1.f);
     // (the small form's instantiation plans at most 1024 paths per window: the planning loops are unrolled over kWindow / 256)
     const bool drop = DMODE != kTangentsInKernel || F.grad_o_sum == nullptr;      // (paths without a term take no lane: kernel, kSortKeys)
-#define EPSM_CP_LAUNCH(FLOAT_ROWS_, WINDOW_, DROP_) \
-    hipLaunchKernelGGL((epsm_backward_cp_kernel<VARIANT, DMODE, PACKED, FLOAT_ROWS_, WINDOW_, (DROP_) || DMODE != kTangentsInKernel>), \
+    // EPSM_OPT_IOR_GRADS: the IOR instantiations exist with in-kernel tangents only (the entry points that take the caller's
+    // tangents refuse the option: epsm_grad_scatter.hip)
+    const bool ior = DMODE == kTangentsInKernel && fused_option(EPSM_OPT_IOR_GRADS) == 1;
+#define EPSM_CP_LAUNCH_(FLOAT_ROWS_, WINDOW_, DROP_, IOR_) \
+    hipLaunchKernelGGL((epsm_backward_cp_kernel<VARIANT, DMODE, PACKED, FLOAT_ROWS_, WINDOW_, (DROP_) || DMODE != kTangentsInKernel, \
+                                                (IOR_) && DMODE == kTangentsInKernel>), \
                        dim3((unsigned) blocks), dim3(kThreads), 0, s, F, dcols, slots, window)
+#define EPSM_CP_LAUNCH(FLOAT_ROWS_, WINDOW_, DROP_) \
+    do { if (!ior) EPSM_CP_LAUNCH_(FLOAT_ROWS_, WINDOW_, DROP_, false); else EPSM_CP_LAUNCH_(FLOAT_ROWS_, WINDOW_, DROP_, true); } while (0)
     if (float_rows) {
         if (small) { if (drop) EPSM_CP_LAUNCH(true, kSmall, true); else EPSM_CP_LAUNCH(true, kSmall, false); }
         else { if (drop) EPSM_CP_LAUNCH(true, kLarge, true); else EPSM_CP_LAUNCH(true, kLarge, false); }
@@ -1071,6 +1093,7 @@ hipError_t launch(const FusedArgs &F0, int dcols, hipStream_t s) {
         else { if (drop) EPSM_CP_LAUNCH(false, kLarge, true); else EPSM_CP_LAUNCH(false, kLarge, false); }
     }
 #undef EPSM_CP_LAUNCH
+#undef EPSM_CP_LAUNCH_
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && F.rep && !F.rep_done) {
         const int64_t n = 6 * F.V + F.B + 3;

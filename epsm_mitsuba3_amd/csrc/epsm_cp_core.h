@@ -267,8 +267,9 @@ template <typename R> EPSM_HD M2<R> blk_own(const Jac<R> &j, const Own<R> &o) {
 // ----------------------------------------------------------------------------
 // seeded reverse sweeps: s . J for a 2-vector s, without the unit-seed rows (s . gxp, s . gxn, s . gn of the Jac above)
 // ----------------------------------------------------------------------------
-template <typename R> struct Swp { V3<R> p, n, g; };      // d/dx_{k-1}, d/dx_{k+1}, d/dn_k;  d/dx_k = -(p + n)
-template <typename R> EPSM_HD Swp<R> zero_swp() { Swp<R> w; w.p = w.n = w.g = zero3<R>(); return w; }
+// e = s . dC/d eta: the constraint's derivative with respect to the record's eta (u = wi + eta wo, du/d eta = wo), before the sign
+template <typename R> struct Swp { V3<R> p, n, g; R e; };      // d/dx_{k-1}, d/dx_{k+1}, d/dn_k;  d/dx_k = -(p + n)
+template <typename R> EPSM_HD Swp<R> zero_swp() { Swp<R> w; w.p = w.n = w.g = zero3<R>(); w.e = R(0); return w; }
 template <typename R> EPSM_HD V3<R> frame_grad_seeded(const Frm<R> &f, V3<R> w, R cx, V2<R> s) {
     const R x = f.nn.x, q = f.nn.y * w.y + f.nn.z * w.z, xi = x * f.isg, qi = q * f.isg;
     const V3<R> G0 = mk3<R>(R(0), (w.z - cx * f.tz) * f.isg, (cx * f.ty - w.y) * f.isg);
@@ -286,6 +287,7 @@ template <typename R> EPSM_HD Swp<R> halfvec_seeded(const Frm<R> &f, const Dir<R
     o.p = (P - wi.w * dot(wi.w, P)) * wi.inv;
     o.n = (P - wo.w * dot(wo.w, P)) * (eta * wo.inv);
     o.g = frame_grad_seeded(f, uh, cx, s);
+    o.e = dot(P, wo.w);
     return o;
 }
 template <typename R> EPSM_HD Swp<R> wo2_seeded(const Frm<R> &f, const Dir<R> &wo, V2<R> s) {      // p == 0
@@ -294,6 +296,7 @@ template <typename R> EPSM_HD Swp<R> wo2_seeded(const Frm<R> &f, const Dir<R> &w
     o.p = zero3<R>();
     o.n = (mk3<R>(R(0), f.ty, f.tz) * s.x + f.bt * s.y - wo.w * (cx * s.x + cy * s.y)) * wo.inv;
     o.g = frame_grad_seeded(f, wo.w, cx, s);
+    o.e = R(0);                                   // wo2 does not depend on eta
     return o;
 }
 
@@ -393,7 +396,8 @@ EPSM_HD MSeeds<R> manifold_bwd(const MBlocks<R> &e, const MFwd<R> &f, const MBwd
     return s;
 }
 // results of lane k.  Gx lacks d/dx_k through constraint k+1: the caller subtracts GP of lane k+1.
-template <typename R> struct MOut { V3<R> Gx, gn, gm, glight, gdiff, GP; };
+// geta: d/d eta_k, the record's eta as a parameter of both versions of constraint k (the index of refraction's gradient)
+template <typename R> struct MOut { V3<R> Gx, gn, gm, glight, gdiff, GP; R geta; };
 // Pass 2: both versions swept once more, seeded with the lane's final seeds.
 template <typename R> EPSM_HD MOut<R> manifold_contract(const Pts<R> &p, const MSeeds<R> &s, bool has_next) {
     MOut<R> out;
@@ -407,6 +411,7 @@ template <typename R> EPSM_HD MOut<R> manifold_contract(const Pts<R> &p, const M
     }
     out.Gx = (a.p + a.n) + (c.p + c.n);                       // -(a.gxc + c.gxc) with gxc = -(gxp + gxn)
     out.gn = -(a.g + c.g);
+    out.geta = -(a.e + c.e);
     out.gm = has_next ? mk3<R>(s.sC.x, s.sC.y, R(0)) : z3;    // dC/dm = -I on continuing rows (epsm.py:883)
     out.glight = -a.n;
     out.gdiff = s.fC ? -c.n : z3;                             // carry == 0 whenever fC (a diffuse x_{k+1} ends the chain)
@@ -455,13 +460,14 @@ EPSM_HD CFwd<R> caustic_fwd(const CBlocks<R> &e, V2<R> dk, bool first, const CFw
     o.fin = finite2(o.u) && finite2(o.v);
     return o;
 }
-template <typename R> struct COut { V3<R> Gx, gn, gm, gdiff, gxp_prev; };
+template <typename R> struct COut { V3<R> Gx, gn, gm, gdiff, gxp_prev; R geta; };      // geta: d/d eta_k through constraint k (k >= 2)
 // lane k once the recursion has reached it (pass 2: seeded sweeps); `inP` = k <= id*, `star` = k == id*, wD = plan_b(k).
 // gxp_prev: -(d/dx_{k-1}) through constraint k, to be ADDED to Gx of lane k-1.
 template <typename R> EPSM_HD COut<R> caustic_finish(const Pts<R> &p, const CFwd<R> &f, bool first, bool inP, bool star, bool wD) {
     COut<R> o;
     const V3<R> z3 = zero3<R>();
     o.Gx = o.gn = o.gm = o.gdiff = o.gxp_prev = z3;
+    o.geta = R(0);
     const Frm<R> fr = make_frm(p.n);
     const Dir<R> wo = make_dir(p.x, p.xn);
     Swp<R> cs = zero_swp<R>();
@@ -470,6 +476,7 @@ template <typename R> EPSM_HD COut<R> caustic_finish(const Pts<R> &p, const CFwd
         o.Gx = cs.p + cs.n;                       // -cs.gxc
         o.gn = -cs.g;
         if (!first) o.gm = mk3<R>(f.v.x, f.v.y, R(0));
+        o.geta = -cs.e;                           // cs == 0 for the first vertex
         o.gxp_prev = -cs.p;
         if (star) {
             const Swp<R> ws = wo2_seeded(fr, wo, f.u);

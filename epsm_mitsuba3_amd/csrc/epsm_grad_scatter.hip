@@ -134,9 +134,10 @@ static int fill_args(FusedArgs &F, const char *who, int variant, int64_t N, int 
     return EPSM_OK;
 }
 
-// ---- launch options: four process-wide integers, set from the environment by a static initialiser (never by an entry point)
+// ---- launch options: five process-wide integers (EPSM_OPT_IOR_GRADS is never read from the environment: the integrators set it per call), set from the environment by a static initialiser (never by an entry point)
 namespace {
-std::atomic<int64_t> g_options[EPSM_OPT_WORKGROUP_SLOTS + 1];
+std::atomic<int64_t> g_options[EPSM_OPT_IOR_GRADS + 1];
+bool known_option(int option) { return (option >= 0 && option <= EPSM_OPT_WORKGROUP_SLOTS) || option == EPSM_OPT_IOR_GRADS; }
 struct OptionsInit {
     OptionsInit() {
         const char *e = getenv("EPSM_SMALL_WAVEFRONT");
@@ -148,6 +149,7 @@ struct OptionsInit {
         const char *ws = getenv("EPSM_WORKGROUP_SLOTS");
         const int64_t wsv = ws ? atoll(ws) : 0;
         g_options[EPSM_OPT_WORKGROUP_SLOTS] = wsv > 0 ? wsv : 0;
+        g_options[EPSM_OPT_IOR_GRADS] = 0;
     }
 } g_options_init;
 }  // namespace
@@ -156,12 +158,13 @@ int64_t fused_option(int option) { return g_options[option].load(std::memory_ord
 }
 extern "C" int epsm_set_option(int option, int64_t value) {
     epsm_host::err_buf()[0] = 0;
-    if (option < 0 || option > EPSM_OPT_WORKGROUP_SLOTS || value < 0) return fail(EPSM_EINVAL, "epsm_set_option: unknown option or negative value");
+    if (!known_option(option) || value < 0) return fail(EPSM_EINVAL, "epsm_set_option: unknown option or negative value");
+    if (option == EPSM_OPT_IOR_GRADS && value > 1) return fail(EPSM_EINVAL, "epsm_set_option: EPSM_OPT_IOR_GRADS is 0 or 1");
     g_options[option].store(value, std::memory_order_relaxed);
     return EPSM_OK;
 }
 extern "C" int64_t epsm_get_option(int option) {
-    return (option < 0 || option > EPSM_OPT_WORKGROUP_SLOTS) ? -1 : g_options[option].load(std::memory_order_relaxed);
+    return !known_option(option) ? -1 : g_options[option].load(std::memory_order_relaxed);
 }
 
 extern "C" int epsm_release_workspace(void) {
@@ -185,6 +188,8 @@ extern "C" int epsm_manifold_grad_scatter(int variant, int64_t N, int K,
     const int rc = fill_args(F, "epsm_manifold_grad_scatter", variant, N, K, cam, verts, sc, tri_table, T, clip, grad_pos, grad_nrm, grad_alpha, V, B);
     if (rc != EPSM_OK) return rc;
     if (!dlduv || !dldp) return fail(EPSM_EINVAL, "epsm_manifold_grad_scatter: NULL argument");
+    if (fused_option(EPSM_OPT_IOR_GRADS) != 0)
+        return fail(EPSM_EINVAL, "epsm_manifold_grad_scatter: EPSM_OPT_IOR_GRADS needs the tangents computed in the kernel (epsm_backward_pass, epsm_backward_pass_packed)");
     if (dlduv_cols < 0 || dlduv_stride < (dlduv_cols < 2 * K ? dlduv_cols : 2 * K))
         return fail(EPSM_EINVAL, "epsm_manifold_grad_scatter: dlduv_stride smaller than the columns to read");
     F.g.dlduv = dlduv;

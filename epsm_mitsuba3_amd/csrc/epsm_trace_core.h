@@ -570,6 +570,9 @@ EPSM_HD BsdfSample bsdf_sample(const EpsmBsdf &b, F3 wi_in, float s1, float s2x,
             o.eta = selected_r ? 1.f : eta_it;
             o.weight = selected_r ? R : f3(1.f, 1.f, 1.f) * (eta_ti * eta_ti);   // radiance transport: * sqr(eta_ti)
             o.valid = o.pdf > 0.f;
+            // a dielectric with a slot (Scene.attach_ior): a refraction logs d eta_it / d int_ior where a rough lobe logs
+            // d hf / d alpha -- eta_it = int / ext entering, ext / int leaving; a reflection logs eta = 1 and 0
+            if (b.alpha_slot >= 0 && !selected_r) o.dhf.x = wi_in.z >= 0.f ? 1.f / b.ext_ior : -eta_it / b.int_ior;
             return o;                                                     // never two-sided
         }
     }

@@ -22,6 +22,7 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
+from . import _lib
 from . import dist as _dist
 from . import profiler as _prof
 from . import replays as _replays
@@ -76,6 +77,7 @@ class PathTrace:
     path_offset: int = 0          # first path of this shard within the full wavefront
     n_paths_total: Optional[int] = None
     log: Optional[PackedLog] = None   # the native log (then path_info / scatter_info may be None)
+    ior_grads: bool = False           # the tracer had an IOR slot (Scene.attach_ior): aux[1] of a refraction is d eta / d int_ior
 
 
 def _max_depth_property(props: dict):
@@ -157,7 +159,11 @@ class EPSMIntegrator:
                         sensor=0, seed: int = 0, spp: int = 0) -> None:
         """epsm.py:84-306.  ``sensor`` and ``spp`` are ignored exactly as the reference
         ignores them (epsm.py:142,145): the backward pass uses ``backward_sensor`` and
-        ``backward_spp``.  Gradients are ACCUMULATED into ``params`` (as dr.backward does)."""
+        ``backward_spp``.  Gradients are ACCUMULATED into ``params`` (as dr.backward does).
+
+        An index of refraction attached with ``Scene.attach_ior`` gets its gradient HERE, in the 5-channel branch, and only here:
+        the refraction direction depends on the IOR, which the detached sampling of the colour adjoint cannot see,
+        so the 3-channel branch, ``prb`` and ``prb_reparam`` leave its slot of ``params.alpha`` at zero."""
         if grad_in.shape[-1] == 3:
             # epsm.py:230-234: a 3-channel gradient image is the colour adjoint deltaL = grad_in of the PRB replay, on
             # the sensor and sample count the caller names (the 5-channel branch alone ignores them, epsm.py:142-145).
@@ -182,8 +188,17 @@ class EPSMIntegrator:
             # this branch transports d / d ray.o alone (epsm.py:260-261): the sensor's rotation has no term in it
             raise NotImplementedError("the 5-channel manifold branch differentiates the sensor's position only (epsm.py:260-261); the "
                                       "gradient of its rotation is `prb_reparam`'s (attach_sensor(rotation=True))")
+        # An attached index of refraction (Scene.attach_ior): the backward kernel takes the scalar row of a refraction vertex for
+        # d / d eta_k x d eta / d int_ior (EPSM_OPT_IOR_GRADS).  The option is process-wide: set on EVERY call, 1 or 0,
+        # from the scene in hand, and back at 0 when the call ends (_ior_option); only the launches with in-kernel tangents have
+        # that instantiation.
+        ior = bool(getattr(scene, "ior_slots", ()))
+        if ior and not (self.fused and self.fuse_tangent):
+            raise NotImplementedError("an index of refraction is attached (attach_ior): its gradient is formed by the fused backward "
+                                      "pass alone (fused=True, fuse_tangent=True); the unfused stages and the entry point that "
+                                      "takes precomputed tangents cannot fill the slot")
         rank, world = _dist.world()
-        with _call_contribution(scene, params, _rigid_slot_count(rigid_slots, params)) as target:
+        with _ior_option(ior), _call_contribution(scene, params, _rigid_slot_count(rigid_slots, params)) as target:
             kw = {}
             if self.fused and self.fuse_tangent and self.packed_log and packed_log:
                 kw["packed_log"] = True        # the tracer writes the backward kernel's native layout (EpsmPackedLog)
@@ -229,8 +244,21 @@ class EPSMIntegrator:
                             fused: Optional[bool] = None):
         """Tangent -> gradient -> scatter for one tile.  ``packed`` = (PackedRecords, PackedScatter)
         built once for records that stay resident; ``out`` = reusable output tensors; ``mark(name)`` is
-        called after each stage (bench.py records HIP events there)."""
+        called after each stage (bench.py records HIP events there).
+
+        A trace of a scene with an IOR slot (``trace.ior_grads``, set by ``Scene``) carries d eta / d int_ior in ``aux[1]`` of its
+        refractions: it must be read under EPSM_OPT_IOR_GRADS, or the roughness rule would add ``gm.x * aux[1]`` -- garbage -- to
+        the IOR slot.  So the option is taken from the trace here, for the launch, and the routes without the ``IOR``
+        instantiations (unfused stages, precomputed tangents) refuse such a trace."""
         mark = mark or (lambda name: None)
+        fused_now = self.fused if fused is None else fused
+        if trace.ior_grads and not (isinstance(packed, PackedLog) or trace.log is not None or (fused_now and self.fuse_tangent)):
+            raise NotImplementedError("the trace carries an index-of-refraction slot (attach_ior): only the fused backward pass with "
+                                      "in-kernel tangents can fill it")
+        with _ior_option(trace.ior_grads):
+            return self._backward_from_trace(trace, params, grad_in, packed, out, mark, fused)
+
+    def _backward_from_trace(self, trace, params, grad_in, packed, out, mark, fused):
         if isinstance(packed, PackedLog) or trace.log is not None:
             # the native log (one 128-byte record per path vertex): one launch, nothing else
             log = packed if isinstance(packed, PackedLog) else trace.log
@@ -277,6 +305,19 @@ class EPSMIntegrator:
 
 class ManifoldIntegrator(EPSMIntegrator):
     variant = "manifold"
+
+
+@contextmanager
+def _ior_option(on: bool):
+    """EPSM_OPT_IOR_GRADS = ``on`` for the launches of a block, and 0 -- its default -- behind it, whatever it was and however
+    the block ends: the option is process-wide, belongs to the integrators, and must not outlive the call (a later launch with
+    precomputed tangents would be refused, a later default launch would run the slower ``IOR`` instantiations)."""
+    lib = _lib.lib()
+    _lib.check(lib.epsm_set_option(_lib.OPT_IOR_GRADS, int(bool(on))), "epsm_set_option")
+    try:
+        yield
+    finally:
+        lib.epsm_set_option(_lib.OPT_IOR_GRADS, 0)
 
 
 class ManifoldCausticIntegrator(EPSMIntegrator):

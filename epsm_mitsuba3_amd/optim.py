@@ -55,6 +55,8 @@ def run(method: str, exp: str, device="cuda", iterations=None, lr=None, log=prin
         log(f"hybrid: phase 2 = {integrator2} after {thres} iterations")
     scene = tasks.load_scene(device)
     integrator = load_dict({"type": method, "max_depth": tasks.max_depth})
+    if hasattr(tasks, "backward_spp") and hasattr(integrator, "backward_spp"):   # an experiment may ask for more samples per backward pass
+        integrator.backward_spp = int(tasks.backward_spp)
     sensor_id = 1 if method.startswith("manifold") else 0                      # optim.py:103-106
     gt = tasks.gt_scene(device).render_primal(sensor=0, seed=0, spp=512, max_depth=tasks.max_depth)
     gt_low = resize(to_ldr(gt), tasks.match_res)                               # optim.py:66

@@ -831,6 +831,7 @@ class Scene:
         self._tile_paths = int(tile_paths)
         self.tile_paths_explicit = False           # set when the caller assigns Scene.tile_paths: then it bounds prb_reparam's tiles (tile_plan)
         self.alpha_slots: Dict[int, int] = {}
+        self._ior_bsdfs: set = set()               # BSDF indices whose slot of alpha_slots is an index of refraction (attach_ior)
         self.material_slots: Dict[int, int] = {}   # conductors attached for the material adjoint (attach_conductor): BSDF index -> slot
         self.env_pose_attached = False             # the envmap's rotation and scale attached for the pose adjoint (attach_envmap_pose)
         self.color_slots: List[tuple] = []         # colour parameters attached for the colour adjoint: ("bsdf" | "emitter", index)
@@ -1149,10 +1150,57 @@ class Scene:
         return i
 
     def attach_alpha(self, bsdf_name: str) -> int:
+        """The slot of ``ParamGrads.alpha`` for the roughness of ``bsdf_name``.  Any BSDF type is accepted, as ever; one without a
+        roughness gets a slot that stays at zero.  For a ``dielectric`` the slot is kept out of the tracer's BSDF table
+        (``_bsdf_structs``): the tracer reads a dielectric's slot as an IOR slot (``attach_ior``), so its per-field log now says
+        ``aux[0] = no slot`` where it said the slot next to ``d hf / d alpha = 0`` -- the same gradients, zero."""
         i = self._refuse_alpha_map("attach_alpha", bsdf_name)
         self.alpha_slots.setdefault(i, len(self.alpha_slots))
         self._upload()
         return self.alpha_slots[i]
+
+    def attach_ior(self, bsdf_name: str) -> int:
+        """``dr.enable_grad(params['<bsdf>.int_ior'])`` of a ``dielectric`` -- a gradient the reference does not form (``eta`` enters
+        its ``calc_grad`` as a constant).  The slot comes from the per-BSDF scalar table of ``attach_alpha``: ``ParamGrads.alpha[slot]``
+        is d loss / d int_ior, filled by the 5-channel branch of ``manifold`` / ``manifold_caustic`` on the fused routes
+        (EPSM_OPT_IOR_GRADS); ``ior_slots`` tells which slots are indices of refraction."""
+        i = self.bsdf_names.index(bsdf_name)
+        b = self.bsdf_desc[i]
+        if b["type"] != BSDF_TYPES["dielectric"]:
+            raise ValueError(f"attach_ior: {bsdf_name!r} is not a dielectric")
+        if float(np.float32(b["int_ior"])) == float(np.float32(b["ext_ior"])):
+            raise ValueError(f"attach_ior: {bsdf_name!r} has int_ior == ext_ior -- its refractions log eta = 1 and would be taken for "
+                             "reflections; start from another value (set_ior)")
+        if i in self.alpha_slots and i not in self._ior_bsdfs:
+            raise ValueError(f"attach_ior: {bsdf_name!r} already holds a slot of attach_alpha")
+        self._ior_bsdfs.add(i)
+        if i not in self.alpha_slots:
+            self.alpha_slots[i] = len(self.alpha_slots)
+            self._upload()
+        return self.alpha_slots[i]
+
+    @property
+    def ior_slots(self) -> List[int]:
+        """The slots of ``ParamGrads.alpha`` that are indices of refraction (attach_ior), ascending."""
+        return sorted(self.alpha_slots[i] for i in self._ior_bsdfs)
+
+    def ior_values(self) -> torch.Tensor:
+        """(n,) current ``int_ior`` of the attached dielectrics, in the order of ``ior_slots``."""
+        by_slot = sorted((self.alpha_slots[i], float(self.bsdf_desc[i]["int_ior"])) for i in self._ior_bsdfs)
+        return torch.tensor([v for _, v in by_slot], dtype=torch.float32, device=self.device)
+
+    def set_ior(self, bsdf_name: str, int_ior: float):
+        """``params['<bsdf>.int_ior'] = int_ior; params.update()``: only the BSDF table is rewritten (in place), as set_alpha does."""
+        i = self.bsdf_names.index(bsdf_name)
+        b = self.bsdf_desc[i]
+        if b["type"] != BSDF_TYPES["dielectric"]:
+            raise ValueError(f"set_ior: {bsdf_name!r} is not a dielectric")
+        if not (float(int_ior) > 0 and np.isfinite(float(int_ior))):
+            raise ValueError("set_ior: int_ior must be positive and finite")
+        if i in self._ior_bsdfs and float(np.float32(int_ior)) == float(np.float32(b["ext_ior"])):
+            raise ValueError(f"set_ior: int_ior == ext_ior on {bsdf_name!r}, whose index of refraction is attached (attach_ior)")
+        b["int_ior"] = float(int_ior)
+        self._bsdf_buf.copy_(torch.frombuffer(bytearray(bytes(self._bsdf_structs())), dtype=torch.uint8))
 
     def attach_conductor(self, bsdf_name: str) -> int:
         """``dr.enable_grad`` of ``params['<bsdf>.eta.value']``, ``['<bsdf>.k.value']`` and ``['<bsdf>.specular_reflectance.value']`` of
@@ -1448,6 +1496,8 @@ class Scene:
             c.eta[:] = [float(x) for x in b["eta"]]; c.k[:] = [float(x) for x in b["k"]]
             c.int_ior, c.ext_ior = float(b["int_ior"]), float(b["ext_ior"])
             c.alpha_slot = self.alpha_slots.get(i, -1)
+            if b["type"] == BSDF_TYPES["dielectric"] and i not in self._ior_bsdfs:
+                c.alpha_slot = -1          # (a dielectric has no alpha: the tracer reads a dielectric's slot as an IOR slot, attach_ior)
             c.color_slot = self.color_slots.index(("bsdf", i)) if ("bsdf", i) in self.color_slots else -1
             c.texture = b.get("texture_index", -1)
             c.material = self.material_slots.get(i, -1) + 1
@@ -2079,7 +2129,7 @@ class Scene:
             recs[0].first_hit = C.addressof(fh)
         self._launch_trace(sensor, seed, spp, max_depth, K, lo, n, (rays, None, None, None), film_pos, radiance, valid, recs,
                            EPSM_TRACE_SPARSE_LOG | EPSM_TRACE_PACKED_LOG | (EPSM_TRACE_FUSE_FIRST_HIT if fuse else 0), gradient_only)
-        tr = PathTrace(res=sensor.width, spp=spp, ray_o=rays[:, 0:3], ray_d=rays[:, 3:6], ray_dx=rays[:, 6:9], ray_dy=rays[:, 9:12],
+        tr = PathTrace(ior_grads=bool(self._ior_bsdfs), res=sensor.width, spp=spp, ray_o=rays[:, 0:3], ray_d=rays[:, 3:6], ray_dx=rays[:, 6:9], ray_dy=rays[:, 9:12],
                        path_info=None, scatter_info=None, path_offset=lo, n_paths_total=sensor.wavefront_size(spp))
         tr.film_pos, tr.radiance, tr.valid = film_pos, radiance, valid
         tr.log = PackedLog(rays, flags, verts, shadow, self.tri_table, K)
@@ -2132,7 +2182,7 @@ class Scene:
                           "table": self.tri_table})
         self._launch_trace(sensor, seed, spp, max_depth, K, lo, n, ray, film_pos, radiance, valid, recs,
                            EPSM_TRACE_SPARSE_LOG if sparse_log else 0, gradient_only)
-        tr = PathTrace(res=sensor.width, spp=spp, ray_o=ray[0], ray_d=ray[1], ray_dx=ray[2], ray_dy=ray[3],
+        tr = PathTrace(ior_grads=bool(self._ior_bsdfs), res=sensor.width, spp=spp, ray_o=ray[0], ray_d=ray[1], ray_dx=ray[2], ray_dy=ray[3],
                        path_info=info, scatter_info=sinfo, path_offset=lo,
                        n_paths_total=sensor.wavefront_size(spp))
         tr.film_pos, tr.radiance, tr.valid = film_pos, radiance, valid

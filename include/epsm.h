@@ -175,7 +175,11 @@ typedef struct EpsmScatterRecord {
     const uint32_t *aux;    /* (N,4)      [bsdf_id u32, d hf / d alpha as 3 x f32 bits]: slot in grad_alpha
                                           (EPSM_NO_INDEX = none) and the derivative of the sampled microfacet normal
                                           w.r.t. the BSDF's alpha (roughconductor.cpp:249-255); may be NULL (no BSDF
-                                          parameter attached) */
+                                          parameter attached).  On a vertex whose record has eta != 1 -- a refraction
+                                          through a dielectric with a slot -- aux[1] is d eta / d parameter instead
+                                          (d eta / d int_ior: 1 / ext_ior entering, -eta / int_ior leaving) and
+                                          aux[2..3] are 0; the backward passes read it that way under
+                                          EPSM_OPT_IOR_GRADS (quad 7 of the packed record likewise) */
     const uint32_t *emit;   /* (N,4)      [etri u32, eb0, eb1, eweight f32]: triangle hit by the emitter-sample shadow
                                           ray (epsm.py:622-625), its barycentrics and sum_rgb(Lr_dir) (epsm.py:627);
                                           may be NULL */
@@ -339,12 +343,23 @@ int epsm_release_workspace(void);
  *                                   slower with the taper than without, a list of few surviving paths 8 % faster
  *                                   (MEASUREMENTS.md 27).  EPSM_WORKGROUP_SLOTS=<S>; a small S lets a test meet all three window
  *                                   sizes in a few thousand paths.
+ *   EPSM_OPT_IOR_GRADS              1: epsm_backward_pass / epsm_backward_pass_packed take the grad_alpha row of a vertex whose
+ *                                   record has eta != 1 for the gradient of an index of refraction: clamp(d/d eta_k) * aux[1]
+ *                                   instead of aux[1..3] . clamp(d/d m_k) -- a refraction is a delta lobe without a roughness
+ *                                   term, and aux[1] then holds d eta / d int_ior (EpsmScatterRecord.aux).  Every other row and
+ *                                   every other vertex is what it is with 0, the default.  No environment variable: the
+ *                                   integrators set it per call from the scene.  With 1, epsm_manifold_grad_scatter (the
+ *                                   caller's tangents) returns -EINVAL; values above 1 are refused.  (Option 4 is not assigned.)
+ *                                   A log traced with an IOR slot MUST be consumed with 1: with 0 the roughness rule adds
+ *                                   gm.x * aux[1] of every refraction to the IOR's entry of grad_alpha, which is no gradient of
+ *                                   anything; epsm_scatter and epsm_manifold_grad + epsm_scatter, which know no option, likewise.
  * Results are the same sums either way (the parity tests run both forms at every size).
  * epsm_set_option returns EPSM_OK or -EINVAL (unknown option, negative value); epsm_get_option returns -1 for an unknown option. */
 #define EPSM_OPT_SMALL_WAVEFRONT_PATHS 0
 #define EPSM_OPT_REPLICAS 1
 #define EPSM_OPT_ONE_LAUNCH 2
 #define EPSM_OPT_WORKGROUP_SLOTS 3
+#define EPSM_OPT_IOR_GRADS 5
 int epsm_set_option(int option, int64_t value);
 int64_t epsm_get_option(int option);
 
