@@ -133,6 +133,7 @@ def _declare(lib):
     declare_bvh(lib)
     declare_scene_tables(lib)
     declare_rigid(lib)
+    declare_smooth(lib)
     return lib
 
 
@@ -146,6 +147,22 @@ def declare_rigid(lib):
     lib.epsm_rigid_expand.restype = C.c_int
     lib.epsm_rigid_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
+    return lib
+
+
+def declare_smooth(lib):
+    """Prototypes of the large-steps entry points of include/epsm_trace.h (device library only)."""
+    lib.epsm_mesh_laplacian_bytes.restype = C.c_size_t
+    lib.epsm_mesh_laplacian_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.epsm_mesh_laplacian.restype = C.c_int
+    lib.epsm_mesh_laplacian.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.epsm_laplacian_apply.restype = C.c_int
+    lib.epsm_laplacian_apply.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.epsm_laplacian_solve_bytes.restype = C.c_size_t
+    lib.epsm_laplacian_solve_bytes.argtypes = [C.c_int64]
+    lib.epsm_laplacian_solve.restype = C.c_int
+    lib.epsm_laplacian_solve.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     return lib
 
 

@@ -18,6 +18,7 @@
 
 #include "epsm_common.h"
 #include "epsm_trace_scan.h"
+#include "epsm_trace_topology.h"
 #include "../../include/epsm_trace.h"
 
 using epsm_host::fail;
@@ -29,8 +30,7 @@ constexpr int64_t kMaxTriangles = int64_t(1) << 28;    // 3 T corner entries and
 constexpr int64_t kMaxVertices = int64_t(1) << 31;
 constexpr int kMaxEnvTexels = 1 << 26;                 // H (W + 1) 3 stays in int32
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+size_t align_up(size_t x) { return epsm::table_align_up(x); }
 unsigned grid(int64_t n, int per = kBlock) { return (unsigned) ((n + per - 1) / per); }
 
 // Inclusive scan of load(i), i in [0, n), by one workgroup of kBlock threads, kBlock items per round: in-wave shuffles, the
@@ -94,12 +94,9 @@ __device__ __forceinline__ double tri_area(const float *pos, const uint32_t *tri
 }
 
 // ------------------------------------------------------------------------------------------------ topology
-struct Topology { uint32_t *row, *adj; };               // row (V + 1), adj (3 T): corner entries 3 t + c
-
-Topology topology_carve(int64_t V, char *base) {
-    return Topology{(uint32_t *) base, base ? (uint32_t *) (base + align_up(4 * (size_t) (V + 1))) : nullptr};
-}
-size_t topology_size(int64_t V, int64_t T) { return align_up(4 * (size_t) (V + 1)) + align_up(12 * (size_t) T); }
+using epsm::Topology;                                   // (epsm_trace_topology.h: the Laplacian table reads it too)
+using epsm::topology_carve;
+using epsm::topology_size;
 
 struct SortSpace { uint32_t *keys0, *keys1, *vals; int *hist, *off, *scan_scratch, *total; };
 

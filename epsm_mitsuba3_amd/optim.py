@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from . import load_dict
 from .integrators import render_seeds
 from .matcher import Matcher
+from .smooth import AdamUniform
 
 
 def to_ldr(img: torch.Tensor) -> torch.Tensor:
@@ -40,6 +41,9 @@ def chain_vertex_grads(vertices: torch.Tensor, vertex_grad: torch.Tensor) -> Non
     """EPSM/optim_human.py:118-121: per-vertex position gradients chained into whatever torch module
     produced the vertices (SMPL there): ``loss = sum(verts * grad); loss.backward()``."""
     (vertices * vertex_grad.detach().to(vertices.device, vertices.dtype)).sum().backward()
+
+
+OPTIMIZERS = {"Adam": torch.optim.Adam, "AdamUniform": AdamUniform}        # an experiment's ``optimizer`` attribute; default Adam
 
 
 def run(method: str, exp: str, device="cuda", iterations=None, lr=None, log=print):
@@ -62,7 +66,8 @@ def run(method: str, exp: str, device="cuda", iterations=None, lr=None, log=prin
     gt_low = resize(to_ldr(gt), tasks.match_res)                               # optim.py:66
     matcher = Matcher(tasks.match_res, device)
     opt, apply_transformation, backward, output = tasks.optim_settings(scene)
-    optimizer = torch.optim.Adam(list(opt.values()), lr=lr)
+    make_optimizer = OPTIMIZERS[getattr(tasks, "optimizer", "Adam")]            # an experiment may name smooth.AdamUniform
+    optimizer = make_optimizer(list(opt.values()), lr=lr)
     params = scene.param_grads()
     history = [output(opt)]
     rep = tasks.resolution // tasks.match_res
@@ -73,7 +78,7 @@ def run(method: str, exp: str, device="cuda", iterations=None, lr=None, log=prin
             integ, sid = integrator, sensor_id
         else:
             if it == thres:                                                     # optim.py:116-118: opt.reset(key)
-                optimizer = torch.optim.Adam(list(opt.values()), lr=lr)
+                optimizer = make_optimizer(list(opt.values()), lr=lr)
             integ, sid = integrator2, 0
         seed, seed_grad = render_seeds(it)                                      # util.py:505-513: de-correlated passes
         img = integ.render(scene, sensor=sid, seed=seed, spp=tasks.spp)         # (H,W,5) or (H,W,3)

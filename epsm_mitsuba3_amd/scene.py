@@ -1137,6 +1137,16 @@ class Scene:
         from . import rigid
         rigid.expand(self.positions, self.normals, ranges, pivots, twists, d_pos, d_nrm, host=self._backend is not None)
 
+    def mesh_laplacian(self, mesh_name: str, lam: float):
+        """``smooth.MeshLaplacian`` of one mesh -- I + lam L over its own vertex range, its triangles in the mesh's local indices --
+        for the large-steps update of its vertices: ``x = lap.from_differential(u); scene.set_vertex_positions(name, x); ...;
+        chain_vertex_grads(x, params.pos[lo:hi])``.  Build it again when the mesh's triangles change."""
+        from . import smooth
+        if mesh_name not in self.mesh_slices:
+            raise ValueError(f"mesh_laplacian: no mesh named {mesh_name!r} in this scene")
+        (lo, hi), (t0, t1) = self.mesh_slices[mesh_name], self.mesh_tri_slices[mesh_name]
+        return smooth.MeshLaplacian((self.tri[t0:t1] - lo).contiguous(), hi - lo, lam, host=self._backend is not None)
+
     def has_attached_geometry(self) -> bool:
         """Any mesh whose vertex positions / normals receive gradients?"""
         return any(m.pos_attached or m.nrm_attached for m in self.meshes)

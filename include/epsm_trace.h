@@ -777,6 +777,70 @@ int epsm_rigid_reduce(const float *positions, const float *normals, const float 
 int epsm_rigid_expand(const float *positions, const float *normals, int64_t V, const int64_t *ranges, const float *pivots,
                       const float *twists, int32_t n_slots, float *d_pos, float *d_nrm, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Large-steps vertex updates (csrc/epsm_trace_smooth.hip): the matrix I + lambda L of a mesh on the device, L its unique-edge
+ * combinatorial Laplacian, and conjugate gradients on it -- the re-parameterisation u = (I + lambda L) x of Nicolet, Jakob and
+ * Jacobson (2021), under which the gradient of u is (I + lambda L)^-1 g_x.  All entries run on `stream` with no host
+ * synchronisation and no allocation, use no float atomics and sum in float64 in a fixed order: two calls on the same input give
+ * identical bits.  EPSM_EINVAL (with epsm_last_error()) for a NULL pointer, a negative count, a non-finite or negative lambda,
+ * max_iters < 1 (or above 65536), a rel_tol outside (0, 1), an unknown form, b == x, or a table / workspace that is too small or
+ * not 16-byte aligned -- checked before anything touches the device.  V == 0: EPSM_OK, nothing is done.
+ *
+ * epsm_mesh_laplacian -- the neighbour table of L from the topology of the same tri (epsm_scene_topology): L_vw = -1 for every
+ *   undirected edge {v, w}, v != w, that some triangle has -- once, however many triangles share it (boundary and non-manifold
+ *   edges, duplicated triangles) -- and L_vv = the number of distinct neighbours.  `laplacian` (device, 16-byte aligned,
+ *   >= epsm_mesh_laplacian_bytes(V, T)) is a CSR table over the topology's own row offsets, two candidate slots per corner: one
+ *   thread per vertex keeps the first occurrence of every neighbour at the front of its row, in corner order, fills the rest of
+ *   the row with 0xFFFFFFFF (a candidate that repeats an earlier one, equals v or is >= V) and stores the row's degree; that
+ *   walk is quadratic in a vertex's valence.  The table's first 32-bit word is the maximum degree, for the host to read once
+ *   after the build.  Rebuild it when the triangles change, not when the vertices move.  A vertex no triangle names has degree
+ *   0.  tri (T,3) u32.  1 <= T < 2^28, 1 <= V < 2^31.
+ * epsm_laplacian_apply -- y = (I + lambda L) x for (V,3) f32 rows: y_v = x_v + lambda (deg_v x_v - sum_w x_w), each row summed
+ *   in float64 in table order and rounded to float32 once.  V must be the V the table was built with (the kernels compare it
+ *   with the table's own and do nothing otherwise; the solve then writes its info as 0 iterations, not converged, residual -1).
+ *   x and y must not overlap.
+ * epsm_laplacian_solve -- conjugate gradients on (I + lambda L) x = b, the three columns sharing the gather, each with its own
+ *   alpha, beta and convergence state.  x is read as the initial guess and overwritten with the result; b is not written.
+ *   Vectors are float32; every dot product is a float64 sum in a fixed order (a lane's rows, the wave by shuffles, the waves in
+ *   order, then the chunks of 1024 vertices in order); the CG scalars are float64 in device memory.  A column stops when
+ *   |r| / |b| <= rel_tol (r the recurrence's residual); a column with b == 0 gets x == 0 exactly; p.q == 0 makes the column's
+ *   step 0.  Convergence is a device word: the launches queued after it is set return at once.  No grid-wide barrier, no
+ *   cooperative launch, nothing waits on a flag: where a launch's last workgroup to arrive adds up the chunk rows, it is
+ *   found by an integer arrival counter and the order of the sum does not depend on which one it is.
+ *   info (device, 3 entries, one per column): the iterations used, whether the column met rel_tol, and the final |r| / |b|
+ *   (0 for a zero column).  Not converged after max_iters is no error: EPSM_OK, info says so.  A warm start from the result
+ *   of an earlier solve at the same rel_tol may take a few iterations more: the residual recomputed from the float32 x differs
+ *   from the recurrence's by up to about kappa 2^-23 |b|, kappa = 1 + 2 lambda max_degree.
+ *   form: EPSM_SMOOTH_GRID      any V; one launch per vertex chunk row, two launches per iteration (the gather recomputes
+ *                               its neighbours' new search direction r + beta p from the previous one) and two before the first;
+ *         EPSM_SMOOTH_ONE_GROUP the whole solve in one launch of one workgroup of 1024 lanes, __syncthreads its only barrier
+ *                               (five per iteration: two in each of the two dot products, one after the new direction),
+ *                               the search direction in LDS, a lane's rows of r and A p (of x too up to 4 rows per lane) in
+ *                               registers.  V <= EPSM_SMOOTH_ONE_GROUP_MAX_V, EPSM_EINVAL above: 12 bytes of LDS per vertex
+ *                               next to 768 bytes of reduction rows, (163840 - 768) / 12 = 13589, cut to whole rows of 1024;
+ *         EPSM_SMOOTH_AUTO      ONE_GROUP up to the measured crossover (MEASUREMENTS 33), GRID above.
+ *   workspace: device, 16-byte aligned, >= epsm_laplacian_solve_bytes(V), whatever the form.
+ * ------------------------------------------------------------------------- */
+#define EPSM_SMOOTH_AUTO 0
+#define EPSM_SMOOTH_GRID 1
+#define EPSM_SMOOTH_ONE_GROUP 2
+#define EPSM_SMOOTH_ONE_GROUP_MAX_V 13312
+
+typedef struct EpsmSmoothInfo {
+    int32_t iterations;     /* CG iterations the column used */
+    int32_t converged;      /* 1: |r| / |b| <= rel_tol (or b == 0) */
+    double residual;        /* the final |r| / |b| */
+} EpsmSmoothInfo;
+
+size_t epsm_mesh_laplacian_bytes(int64_t V, int64_t T);
+int epsm_mesh_laplacian(const uint32_t *tri, int64_t V, int64_t T, const void *topology, void *laplacian,
+                        size_t laplacian_bytes, void *stream);
+int epsm_laplacian_apply(const void *laplacian, int64_t V, double lambda, const float *x, float *y, void *stream);
+size_t epsm_laplacian_solve_bytes(int64_t V);
+int epsm_laplacian_solve(const void *laplacian, int64_t V, double lambda, const float *b, float *x, int32_t max_iters,
+                         double rel_tol, int32_t form, EpsmSmoothInfo *info, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
